@@ -1,7 +1,15 @@
 #!/usr/bin/env python3
 """bench.py — headline benchmark of the rt-neural-generic hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run does what the headline needs and nothing else: it sets up, pre-rolls the clocks, warms up, times the K steps, writes
+the last step's output when --dump-outputs is given, and prints the line. Everything else it can measure or check comes with --full.
+
+--dump-outputs DIR: after the timed steps, the [streams][256] fp32 block the last timed step wrote (what a caller of
+aidax_pool_process_device receives) as DIR/output.npy; rank r of N > 1 writes DIR/output_rank<r>.npy. A block over the size cap is
+sampled: a fixed set of streams (seed 0), their indices in DIR/output_streams.npy. Inputs are seeded, and the clock pre-roll runs on
+a pool of its own, so that the same arguments give the same outputs from run to run.
 
 N > 1: one process per GPU. Either the caller starts the ranks (python -m torch.distributed.run --nnodes=1
 --nproc-per-node N ... bench.py --gpus N ...: RANK / LOCAL_RANK / WORLD_SIZE in the environment), or — when they
@@ -17,15 +25,18 @@ already resident in HBM.
 Streams are independent, so N GPUs run N x 1024 streams with no data-path collective ("weak" scaling); RCCL
 carries one MAX(elapsed) / SUM(samples) reduction at the end.
 
-Prints ONE json line (rank 0) with the driver's contract keys plus
+Prints ONE json line (rank 0) with the driver's contract keys (metric, value, unit, higher_is_better, dtype, ms_per_step = wall
+time of the timed region / K) plus
   roofline          HBM roofline of the pass from ALGORITHMIC bytes (8 B per sample per stream: 4 in + 4 out,
                     SURVEY §8(d)) over the average launch duration measured with HIP events on the launch stream
   roofline_compute  the same pass against the fp32 peak from ALGORITHMIC flops — the roofline
                     that actually binds this path (1064 flop/B against a machine balance of ~20)
+  ranks             world size, collective backend and every rank's own elapsed time of the headline region
+and, with --full only (each of them can still be turned off there by its --no-* switch):
   other_workloads   short timed regions of the other BASELINE configs at their per-GPU sizes in the same process,
                     each with its rooflines, max-abs error and its own cpu_baseline (N = 1: cfg3, cfg4, cfg5; N > 1:
                     cfg4 and cfg5 — BASELINE's 8-GPU workloads — on every rank, reduced like the headline)
-  ranks             world size, collective backend and every rank's own elapsed time of the headline region
+  stream_sweep      cfg2's model at 4096 and 16 384 streams per GPU
   realtime_case     the LV2 case of SURVEY §8(d): ONE stream, 256-frame blocks — wall time per
                     aidax_pool_process call (pinned staging + launch + wait) next to the CPU oracle on one thread
   realtime_paced    the same call made the way a host makes it — ONE call per audio period (1 333 / 2 667 / 5 333 us = 64 / 128 / 256
@@ -42,8 +53,8 @@ Prints ONE json line (rank 0) with the driver's contract keys plus
   per_launch_us     one HIP event pair per launch after the timed region: min / p50 / p95 / max, launches over 1.2 x p50
   gpu_state_while_running   shader clock / socket power read by rocm-smi while the workload's kernel runs
   roofline.traffic  HBM bytes per launch from rocprofv3 PMC passes (FETCH_SIZE, WRITE_SIZE: two child runs of this
-                    script under the profiler, N = 1 only); when the profiler is not usable, the committed profile of
-                    the same kernel sources (hash-checked), else null
+                    script under the profiler, N = 1 only); when the profiler is not usable — and in a plain run,
+                    which starts no profiler — the committed profile of the same kernel sources (hash-checked), else null
 """
 import argparse
 import importlib
@@ -69,6 +80,7 @@ N_SIMDS = 1024            # 256 CUs x 4
 NOMINAL_GHZ = 2.4
 ALGO_BYTES_PER_SAMPLE = 8
 PREROLL_S = 0.35          # un-timed passes before the warm-up: clocks ramp, caches and TLBs fill
+DUMP_MAX_BYTES = 60 * 2**20   # --dump-outputs writes at most this much (all ranks)
 
 # The headline line is cfg2 (BASELINE.json configs[1]). The other GPU configs run as short regions after it
 # (other_workloads) or on their own with --workload; they are parity-test cases, not the line the driver records.
@@ -627,9 +639,16 @@ def slow_call_pattern(t):
     return out
 
 
-def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, launch_stream, preroll_s=PREROLL_S, dist_steps=True):
+def input_ring(W, S: int, lo: int = 0):
+    """The RING seeded [S][N_FRAMES] input blocks of a rank whose streams start at `lo`; step i of every region reads block i % RING."""
+    return [W.signal(S, N_FRAMES, seed=0xA1DA + 7919 * r + lo) for r in range(RING)]
+
+
+def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, launch_stream, preroll_s=PREROLL_S, dist_steps=True,
+            preroll_pool=False, keep_last=False):
     """One timed region of one workload on this rank. Returns a dict with the local elapsed time, the average pass
-    duration from HIP events on the launch stream, the pool's kernel name, the parity spot-check and the json."""
+    duration from HIP events on the launch stream, the pool's kernel name, the parity spot-check and the json
+    (keep_last: and a host copy of the block the last timed step wrote)."""
     import numpy as np
     wl = WORKLOADS[name]
     path, j = workload_model_path(W, name)
@@ -640,7 +659,7 @@ def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, lau
 
     # synthetic inputs of this rank's stream range, resident in HBM before timing starts
     lo, _hi = stream_range(rank, world, S * world)
-    host_ring = [W.signal(S, N_FRAMES, seed=0xA1DA + 7919 * r + lo) for r in range(RING)]
+    host_ring = input_ring(W, S, lo)
     d_in = [torch.from_numpy(b).cuda() for b in host_ring]
     d_out = [torch.empty_like(t) for t in d_in]
     stream = launch_stream.cuda_stream
@@ -668,15 +687,25 @@ def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, lau
         parity = {"max_abs_err": max_err, "kernel": pool.kernel_name, "pool": "the timed pool (its first blocks, before the pre-roll)",
                   "streams_checked": rows, "blocks": nb, "against": "CPU oracle (oracle/), same inputs", "bar": 1e-5}
 
-    # clock pre-roll: un-timed, not part of `warmup`; a short driver run then sees the same clocks as a long one
+    # clock pre-roll: un-timed, not part of `warmup`; a short driver run then sees the same clocks as a long one. preroll_pool (the
+    # headline): on a second pool of the same workload, made after the timed one and closed before the warm-up — how many passes fit
+    # the pre-roll then leaves the timed pool's state alone, and its last step computes the same block in every run of the same arguments
+    pre = pool
+    if preroll_pool:
+        pre = ax.Pool(S, N_FRAMES, 48000.0, device=local)
+        pre.set_model(model, ax.START_WARMUP)
+        pre.set_controls(ax.default_controls(**wl["controls"]))
     t0 = time.perf_counter()
     i = 0
     while time.perf_counter() - t0 < preroll_s:
         for _ in range(32):
-            step(i)
+            k = i % RING
+            pre.process_device(d_in[k].data_ptr(), d_out[k].data_ptr(), N_FRAMES, stream)
             i += 1
         launch_stream.synchronize()
     preroll_ms = (time.perf_counter() - t0) * 1e3
+    if pre is not pool:
+        pre.close()
 
     for i in range(warmup):
         step(i)
@@ -699,6 +728,7 @@ def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, lau
         torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     kernel_ms = ev0.elapsed_time(ev1) / max(steps, 1)            # avg pass duration on the launch stream
+    last = d_out[(steps - 1) % RING].cpu().numpy() if keep_last else None      # (before anything below reuses the ring)
     kernel = pool.kernel_name
     if parity is not None and parity["kernel"] != kernel:
         raise SystemExit(f"bench.py: the parity check ran on {parity['kernel']}, the timed region on {kernel}")
@@ -706,7 +736,7 @@ def measure(ax, W, torch, name, S, steps, warmup, rank, world, local, check, lau
     gpu_state = gpu_state_while(step, launch_stream) if (dist_steps and rank == 0) else None
     pool.close()
     return dict(elapsed=elapsed, kernel_ms=kernel_ms, kernel=kernel, max_err=max_err, parity=parity, json=j, preroll_ms=preroll_ms,
-                per_launch_us=per_launch, gpu_state=gpu_state)
+                per_launch_us=per_launch, gpu_state=gpu_state, last=last)
 
 
 def launch_distribution(torch, step, launch_stream, n):
@@ -802,6 +832,21 @@ def rooflines(name, S, kernel_ms, kernel):
     return hbm, comp
 
 
+def dump_outputs(out_dir: str, block, rank: int, world: int):
+    """--dump-outputs: the block the last timed step wrote, as float32 .npy files (see the module docstring). All ranks together
+    stay under DUMP_MAX_BYTES: a rank's larger block is cut to a fixed, seeded sample of its streams."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    tag = "" if world == 1 else f"_rank{rank}"
+    budget = DUMP_MAX_BYTES // world
+    if block.nbytes > budget:
+        row_bytes = block.shape[1] * block.itemsize + 8              # a sampled stream: its frames + its index (float64)
+        rows = np.sort(np.random.default_rng(0).choice(block.shape[0], budget // row_bytes, replace=False))
+        np.save(os.path.join(out_dir, f"output_streams{tag}.npy"), rows.astype(np.float64))
+        block = block[rows]
+    np.save(os.path.join(out_dir, f"output{tag}.npy"), np.ascontiguousarray(block, dtype=np.float32))
+
+
 def dry_run(args):
     """CPU stand-in for the multi-rank plumbing (tests): same rank logic and the same reduction over gloo, the
     'pass' is a sleep. Never used for a reported number."""
@@ -846,6 +891,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=500)
     ap.add_argument("--workload", choices=sorted(WORKLOADS), default="cfg2")
     ap.add_argument("--streams", type=int, default=0, help="streams per GPU (default: the workload's, cfg2 = 1024)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write the block the last one computed to DIR/output.npy")
+    ap.add_argument("--full", action="store_true",
+                    help="measure and check everything beyond the headline: parity against the CPU oracle, per-launch distribution and "
+                         "clock sample, live HBM traffic, the other workloads and the stream sweep, the real-time and host-memory "
+                         "cases, the CPU baselines (a plain run does none of it; the --no-* switches below turn parts of it off)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-check", action="store_true")
     ap.add_argument("--no-others", action="store_true", help="skip the short cfg3/cfg4/cfg5 regions and the one-stream case")
@@ -860,6 +910,10 @@ def main():
                          "init_process_group('nccl'), the reductions as RCCL collectives on cuda tensors, cfg4 / cfg5 regions per rank "
                          "(--gpus 1 --force-dist is how the multi-GPU branch runs on a one-GPU box)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dry_run and args.dump_outputs:
+        ap.error("--dump-outputs needs the real pass: a --dry-run computes nothing")
 
     if "RANK" not in os.environ and (args.gpus > 1 or args.force_dist):
         # before anything touches the GPU: this process only starts the ranks and relays their line
@@ -892,8 +946,11 @@ def main():
     launch_stream = torch.cuda.Stream()              # a real (non-null) HIP stream: the events sit on it too
     torch.cuda.set_stream(launch_stream)
 
-    m = measure(ax, W, torch, args.workload, S, args.steps, args.warmup, rank, world, local, not args.no_check, launch_stream,
-                dist_steps=not args.no_dist)
+    full = args.full
+    m = measure(ax, W, torch, args.workload, S, args.steps, args.warmup, rank, world, local, full and not args.no_check, launch_stream,
+                dist_steps=full and not args.no_dist, preroll_pool=True, keep_last=bool(args.dump_outputs))
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, m["last"], rank, world)
     samples = float(S) * N_FRAMES * args.steps
     red_dev = "cpu" if args.share_device else "cuda"
     elapsed_max, samples_all = reduce_results(m["elapsed"], samples, world, backend_device=red_dev, force=use_dist)
@@ -904,11 +961,11 @@ def main():
         dist.all_gather(every, mine)
         rank_elapsed = [float(t.item()) for t in every]
 
-    # N > 1: BASELINE's 8-GPU workloads (cfg4: 1024 streams per GPU, cfg5: 2048) on EVERY rank, each region bracketed
+    # --full, N > 1: BASELINE's 8-GPU workloads (cfg4: 1024 streams per GPU, cfg5: 2048) on EVERY rank, each region bracketed
     # and reduced like the headline (not with --share-device: ranks that share one GPU are rank plumbing, and two
     # processes cannot both hold the CUs k_mfma_lp needs)
     multi_others = []
-    if use_dist and not args.no_others and not args.share_device:
+    if full and use_dist and not args.no_others and not args.share_device:
         for name in ("cfg4", "cfg5"):
             if name == args.workload:
                 continue
@@ -923,7 +980,7 @@ def main():
         hbm, comp = rooflines(args.workload, S, m["kernel_ms"], m["kernel"])
         traffic, how = None, None
         if args.workload == "cfg2" and S == wl["streams"] and not args.no_traffic and "+" not in m["kernel"]:
-            if not use_dist:
+            if full and not use_dist:
                 traffic, how = measure_traffic_live(args.workload, m["kernel"], 4.0 * S * N_FRAMES), "measured by this run"
             if traffic is None:
                 traffic, how = pmc_traffic_bytes(m["kernel"], 4.0 * S * N_FRAMES), "committed profile of the same kernel sources, not measured in this run"
@@ -954,7 +1011,7 @@ def main():
         if args.share_device:
             out["share_device"] = True                        # all ranks on device 0: the rank plumbing with real kernels, not a scaling number
             out["config"]["note"] = f"{world} ranks share ONE GPU (--share-device): no scaling measurement"
-        if not use_dist and not args.no_others:
+        if full and not use_dist and not args.no_others:
             others = []
             for name in ("cfg3", "cfg4", "cfg5"):
                 if name == args.workload:
@@ -987,7 +1044,7 @@ def main():
             out["realtime_case"] = realtime_case(ax, W, local)
             out["realtime_paced"] = realtime_paced(ax, W, torch, local, launch_stream)
             out["host_inclusive"] = host_inclusive(ax, W, local)
-        if world == 1 and not args.no_cpu_baseline:
+        if full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(W, m["json"], args.workload)
         if multi_others:
             out["other_workloads"] = []

@@ -4,7 +4,7 @@ cd "$(dirname "$0")/.."
 for v in "$@"; do
   export AIDAX_LIB=$PWD/${v#*=}
   echo "=== ${v%%=*}"
-  python bench.py --workload cfg2 --no-others --no-cpu-baseline --no-traffic --no-dist --steps 3000 --warmup 100 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['config']['kernel'], round(d['roofline']['kernel_ms']*1e3,2), 'us', d['max_abs_err'])"
+  python bench.py --full --workload cfg2 --no-others --no-cpu-baseline --no-traffic --no-dist --steps 3000 --warmup 100 2>/dev/null | python -c "import sys,json; d=json.loads(sys.stdin.read().strip().splitlines()[-1]); print(d['config']['kernel'], round(d['roofline']['kernel_ms']*1e3,2), 'us', d['max_abs_err'])"
   python - <<'PY'
 import importlib, os, sys, glob
 sys.path.insert(0, os.getcwd())

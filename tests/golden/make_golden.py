@@ -14,6 +14,9 @@ What each fixture pins:
     common/ValueSmoother.hpp (compiled into oracle/_ref by oracle/Makefile):
     filter designs, impulse/noise responses incl. a coefficient change
     mid-stream, smoother ramps incl. a target change mid-ramp.
+  * dsp_ref_random.json — SHA-256 digests of the same Biquad's output for 200
+    random designs over random audio (the live test's cases, for machines
+    where oracle/_ref cannot be built).
 The six bundled model files under tests/golden/models/ carry the reference's own
 input_batch/output_batch vectors and need no generation.
 """
@@ -154,6 +157,46 @@ def make_dsp_ref():
     print("dsp_ref.npz", coeffs.shape, imp_out.shape)
 
 
+def random_biquad_cases(n_designs=200, n_samples=2000, seed=123):
+    """The random designs + random audio of tests/test_oracle.py::test_live_reference_library_when_present, in the order drawn there."""
+    rs = np.random.RandomState(seed)
+    x = rs.uniform(-1, 1, n_samples).astype(np.float32)
+    designs = []
+    for _ in range(n_designs):
+        t = int(rs.randint(0, 7))
+        fc = float(rs.uniform(0.0005, 0.49))
+        q = float(rs.uniform(0.2, 5.0))
+        gain = float(rs.uniform(-12, 12))
+        designs.append((t, fc, q, gain))
+    return x, designs
+
+
+def make_dsp_ref_random():
+    """dsp_ref_random.json — SHA-256 of the reference Biquad's output for each random design of random_biquad_cases(): the
+    restatement is held to it bit for bit where oracle/_ref cannot be built."""
+    import ctypes as C
+    import hashlib
+    import json
+    from oracle import oracle as O
+    R = O.ref_lib()
+    if R is None:
+        raise SystemExit("oracle/_ref not built (make -C oracle _ref, with the reference sources present)")
+    fp = C.POINTER(C.c_float)
+    x, designs = random_biquad_cases()
+    digests = []
+    for t, fc, q, gain in designs:
+        h = R.ref_biquad_new(t, fc, q, gain)
+        y = np.empty_like(x)
+        R.ref_biquad_block(h, y.ctypes.data_as(fp), x.ctypes.data_as(fp), x.size)
+        R.ref_biquad_free(h)
+        digests.append(hashlib.sha256(y.tobytes()).hexdigest())
+    with open(os.path.join(HERE, "dsp_ref_random.json"), "w") as f:         # one case per line: [type, Fc, Q, gain, sha256]
+        f.write('{"seed": 123, "n_samples": %d, "cases": [\n' % x.size)
+        f.write(",\n".join(json.dumps(list(d) + [h]) for d, h in zip(designs, digests)))
+        f.write("\n]}\n")
+    print("dsp_ref_random.json", len(digests), "designs")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("--ref", action="store_true")
@@ -164,3 +207,4 @@ if __name__ == "__main__":
         make_nn(a.force)
     if a.ref:
         make_dsp_ref()
+        make_dsp_ref_random()

@@ -129,7 +129,7 @@ def test_two_ranks_with_the_real_kernels_on_one_gpu():
     a box with one GPU), the only collective — MAX(elapsed), SUM(samples) — goes over gloo, rank 0 prints the line and
     marks it as no scaling measurement. The rank plumbing of SURVEY §8(e) end to end on hardware."""
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-device", "--steps", "40", "--warmup", "5",
-                        "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stderr[-2000:]
     line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
     j = json.loads(line)
@@ -162,7 +162,7 @@ def test_the_rccl_branch_runs_at_world_size_one():
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--force-dist", "--steps", "200", "--warmup", "20",
-                        "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
+                        "--full", "--no-cpu-baseline"], cwd=ROOT, env=env, capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stdout[-1000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]
