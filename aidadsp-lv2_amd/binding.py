@@ -155,6 +155,10 @@ def lib() -> C.CDLL:
     L.aidax_hub_faults_unmapped.restype = C.c_uint64
     L.aidax_hub_set_deadline_us.argtypes = [vp, C.c_int64]
     L.aidax_hub_flush.argtypes = [vp]
+    L.aidax_ir_load_wav.argtypes = [C.c_char_p, _fp, u32, C.POINTER(u32), C.POINTER(C.c_double)]
+    L.aidax_pool_prepare_ir.argtypes = [vp, _fp, u32, C.c_double, C.POINTER(vp)]
+    L.aidax_pool_commit_ir.argtypes = [vp, vp]
+    L.aidax_pool_set_ir.argtypes = [vp, _fp, u32, C.c_double]
     _lib = L
     return L
 
@@ -190,6 +194,15 @@ def biquad_design(kind: int, fc: float, q: float, gain_db: float) -> np.ndarray:
     out = (C.c_double * 5)()
     _check(lib().aidax_biquad_design(kind, fc, q, gain_db, out))
     return np.array(list(out), np.float64)
+
+
+def load_ir_wav(path: str):
+    """aidax_ir_load_wav: (taps as float32, samplerate) of channel 0 of a WAV file."""
+    n, sr = C.c_uint32(0), C.c_double(0.0)
+    _check(lib().aidax_ir_load_wav(os.fsencode(path), None, 0, C.byref(n), C.byref(sr)))
+    taps = np.empty(n.value, np.float32)
+    _check(lib().aidax_ir_load_wav(os.fsencode(path), taps.ctypes.data_as(_fp), n.value, C.byref(n), C.byref(sr)))
+    return taps, sr.value
 
 
 def device_count() -> int:
@@ -306,6 +319,7 @@ class Pool:
         live_handles.add(self)
         self.n_streams = n_streams
         self.max_frames = max_frames
+        self.samplerate = samplerate
 
     def set_model(self, m: Optional[Model], start_mode: int = START_WARMUP):
         _check(lib().aidax_pool_set_model(self.h, m.h if m is not None else None, start_mode))
@@ -323,6 +337,24 @@ class Pool:
     @staticmethod
     def staged_free(staged: C.c_void_p):
         lib().aidax_staged_free(staged)
+
+    def set_ir(self, taps: Optional[np.ndarray], samplerate: Optional[float] = None):
+        """aidax_pool_set_ir: attach a cabinet IR (taps None: remove it); samplerate defaults to the pool's"""
+        t = None if taps is None else _f32(taps)
+        _check(lib().aidax_pool_set_ir(self.h, None if t is None else t.ctypes.data_as(_fp), 0 if t is None else t.size,
+                                       self.samplerate if samplerate is None else samplerate))
+
+    def prepare_ir(self, taps: Optional[np.ndarray], samplerate: Optional[float] = None) -> C.c_void_p:
+        """worker half of an IR swap: returns the staged handle for commit_ir / staged_free"""
+        t = None if taps is None else _f32(taps)
+        sg = C.c_void_p()
+        _check(lib().aidax_pool_prepare_ir(self.h, None if t is None else t.ctypes.data_as(_fp), 0 if t is None else t.size,
+                                           self.samplerate if samplerate is None else samplerate, C.byref(sg)))
+        return sg
+
+    def commit_ir(self, staged: C.c_void_p):
+        """audio half: swaps the staged IR in; `staged` then holds the retired one (free it with staged_free)"""
+        _check(lib().aidax_pool_commit_ir(self.h, staged))
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

@@ -82,5 +82,7 @@ int  conv_ms_tap(int ksize, int pos);
 bool conv_ms_shape_ok(const ConvDesc& d);
 int conv_st_shape(const ConvDesc& d);          // 1 + the index of the stack's k_conv_st geometry (aidax_layout.h), 0 = none
 uint32_t conv_ms_period(const ConvDesc& d);
+// cabinet IR (aidax_ir.cpp): the A fragments k_ir_conv reads, [n_diag][3 terms][64 lanes][4 words]
+std::vector<uint32_t> pack_ir_fragments(const float* h, uint32_t n_taps, uint32_t* n_diag);
 
 }  // namespace aidax

@@ -14,6 +14,7 @@
 #include <mutex>
 #include <thread>
 #include <sstream>
+#include <string>
 
 #include "aidax_internal.h"
 #include "aidax_kernels.h"
@@ -307,6 +308,26 @@ struct ModelSlot {
     float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
 };
 
+// A pool's cabinet IR (aidax_pool_prepare_ir / aidax_pool_commit_ir): its A fragments for k_ir_conv, swapped in and out like a model.
+struct IrSlot {
+    uint32_t* d_frag = nullptr;      // nullptr: no IR
+    uint32_t n_taps = 0, n_diag = 0;
+};
+// ... and the stage's history, allocated by the first aidax_pool_prepare_ir and fed by every pass from then on (k_ir_append): per stream
+// a ring of the last R >= 8192 + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial sums (aidax_ir_mfma.hip)
+struct IrHistory {
+    float* ring = nullptr;
+    float* part = nullptr;
+    uint32_t ring_row = 0, mask = 0, split_cap = 1;
+};
+void free_ir_history(IrHistory* h)
+{
+    if (!h) return;
+    if (h->ring) (void)hipFree(h->ring);
+    if (h->part) (void)hipFree(h->part);
+    delete h;
+}
+
 constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
 constexpr size_t kStagingLimit = size_t(64) << 20;      // pinned staging per direction for aidax_pool_process
 constexpr size_t kZeroCopyLimit = size_t(64) << 10;     // blocks up to this size are read / written by the kernels in place in pinned host memory
@@ -323,6 +344,8 @@ struct aidax_staged {
     StreamState* d_pst = nullptr;    // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
     hipEvent_t fence = nullptr;      // recorded by the commit: everything that may still touch the retired buffers precedes it
     bool fenced = false;
+    bool is_ir = false;              // an IR on its way (aidax_pool_prepare_ir): `ir` instead of `slot`
+    aidax::IrSlot ir;
 };
 
 struct aidax_pool {
@@ -372,7 +395,25 @@ struct aidax_pool {
         if (__atomic_exchange_n(h_lp_fault, 0u, __ATOMIC_ACQ_REL) == 0) return false;
         lp_off.store(true, std::memory_order_relaxed);
         lp_faults.fetch_add(1, std::memory_order_relaxed);
+        // the wrong block is in the IR history: clear it, so that it does not sound through the IR's tail (behind every pass issued so far)
+        if (IrHistory* h = ir_history()) {
+            if (last_stream && last_stream != q && hipEventRecord(ev_x, last_stream) == hipSuccess) (void)hipStreamWaitEvent(q, ev_x, 0);
+            last_stream = q;
+            (void)hipMemsetAsync(h->ring, 0, sizeof(float) * n_streams * static_cast<size_t>(h->ring_row), q);
+        }
         return true;
+    }
+
+    // The cabinet IR stage: the live IR (d_frag == nullptr: none) and the history, which the worker side publishes once (the first
+    // aidax_pool_prepare_ir) and the audio side picks up at its next call; the ring slot of the next pass's first frame.
+    IrSlot ir;
+    std::atomic<IrHistory*> ir_hist_pub{nullptr};
+    IrHistory* ir_hist = nullptr;
+    uint32_t ir_pos = 0;
+    IrHistory* ir_history()
+    {
+        if (!ir_hist) ir_hist = ir_hist_pub.load(std::memory_order_acquire);
+        return ir_hist;
     }
 
     // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
@@ -678,6 +719,10 @@ struct aidax_pool {
     }
     void release()
     {
+        if (ir.d_frag) (void)hipFree(ir.d_frag);
+        ir = IrSlot{};
+        free_ir_history(ir_hist_pub.exchange(nullptr));
+        ir_hist = nullptr;
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);
         if (cur.d_nn) (void)hipFree(cur.d_nn);
@@ -741,6 +786,7 @@ void staged_release(aidax_staged* s)
     if (s->slot.d_counters) (void)hipFree(s->slot.d_counters);
     if (s->slot.lp_owner) lp_gate().release(s->device, s->slot.lp_owner);
     if (s->d_pst) (void)hipFree(s->d_pst);
+    if (s->ir.d_frag) (void)hipFree(s->ir.d_frag);
     if (s->fence) (void)hipEventDestroy(s->fence);
     delete s;
 }
@@ -953,7 +999,25 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (p->h_lp_fault && *static_cast<volatile uint32_t*>(p->h_lp_fault) != 0) p->lp_off.store(true, std::memory_order_relaxed);
         LaunchArgs a = p->args(p->cur, p->d_st, d_in, d_out, n_frames, MODE_CHAIN);
         a.n_streams = n_active;
+        // with an IR history the pass ends behind the IR stage: its end marker (the submit path's event, the blocking path's completion
+        // word) is not handed to the model's launch but issued after the stage by the caller
+        IrHistory* ih = n_frames != 0 ? p->ir_history() : nullptr;
+        if (ih) { p->pass_done = nullptr; p->pass_word = nullptr; }
         HIP_TRY(p->launch(p->cur, a, s));
+        if (ih) {
+            // the IR stage (aidax_ir_mfma.hip): the block's dry samples into the history (also while no IR is live), then the convolution
+            // over the history, in place on d_out
+            HIP_TRY(launch_ir_append(ih->ring, ih->ring_row, ih->mask, p->ir_pos, d_out, n_active, n_frames, s));
+            if (p->ir.d_frag) {
+                IrArgs ia{};
+                ia.frag = p->ir.d_frag; ia.ring = ih->ring; ia.out = d_out; ia.part = ih->part;
+                ia.n_diag = p->ir.n_diag; ia.ring_row = ih->ring_row; ia.mask = ih->mask; ia.pos = p->ir_pos;
+                ia.n_streams = n_active; ia.n_frames = n_frames;
+                ia.n_splits = ir_k_splits(n_active, n_frames, p->ir.n_diag, p->cus, ih->split_cap);
+                HIP_TRY(launch_ir_conv(ia, s));
+            }
+            p->ir_pos = (p->ir_pos + n_frames) & ih->mask;
+        }
         return AIDAX_OK;
     });
 }
@@ -1105,6 +1169,7 @@ AIDAX_API int aidax_pool_prepare_model(aidax_pool* p, const aidax_model* m, int 
 AIDAX_API int aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged)
 {
     if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
+    if (staged->is_ir) return fail(AIDAX_ERR_ARG, "staged object holds an IR: commit it with aidax_pool_commit_ir");
     if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged model was committed already");
     if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged model belongs to another pool");
     return guarded([&]() { return commit_impl(*p, staged); });
@@ -1119,6 +1184,82 @@ AIDAX_API int aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int star
     if (rc != AIDAX_OK) return rc;
     rc = aidax_pool_commit_model(p, sg);
     aidax_staged_free(sg);                                  // what the swap retired (or, on failure, the unused model)
+    return rc;
+}
+
+// The cabinet IR, split between the threads like a model swap. Worker: the history on first use (allocated, zeroed, published), the IR's
+// fragments packed and uploaded on the worker stream. Audio thread: a swap of two host records behind an event — no allocation, no free, no wait.
+AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (taps) {
+        if (n_taps == 0 || n_taps > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR length must be 1 .. 8192 taps");
+        for (uint32_t k = 0; k < n_taps; ++k)
+            if (!std::isfinite(taps[k])) return fail(AIDAX_ERR_ARG, "IR tap " + std::to_string(k) + " is not finite");
+        if (samplerate != p->host_sr)
+            return fail(AIDAX_ERR_ARG, "IR sample rate " + std::to_string(samplerate) + " differs from the pool's " + std::to_string(p->host_sr) + " (no resampling)");
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        std::unique_ptr<aidax_staged, void (*)(aidax_staged*)> sg(new aidax_staged(), staged_release);
+        sg->device = p->device;
+        sg->n_streams = p->n_streams;
+        sg->is_ir = true;
+        HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+        if (!p->ir_hist_pub.load(std::memory_order_acquire)) {
+            std::unique_ptr<IrHistory, void (*)(IrHistory*)> h(new IrHistory(), free_ir_history);
+            uint32_t R = 1;
+            while (R < kIrMaxTaps + p->max_frames) R <<= 1;
+            h->mask = R - 1;
+            h->ring_row = R + kIrMirror;
+            const size_t block = static_cast<size_t>(p->n_streams) * p->max_frames;
+            const size_t budget = size_t(16) << 20;              // floats of partial sums (64 MiB)
+            h->split_cap = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(64, budget / block)));
+            const size_t ring_bytes = sizeof(float) * p->n_streams * static_cast<size_t>(h->ring_row);
+            HIP_TRY(hipMalloc(&h->ring, ring_bytes));
+            if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
+            HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, p->wq));
+            HIP_TRY(hipStreamSynchronize(p->wq));
+            p->ir_hist_pub.store(h.release(), std::memory_order_release);
+        }
+        if (taps) {
+            aidax::IrSlot& ir = sg->ir;
+            const std::vector<uint32_t> frag = pack_ir_fragments(taps, n_taps, &ir.n_diag);
+            ir.n_taps = n_taps;
+            HIP_TRY(hipMalloc(&ir.d_frag, frag.size() * sizeof(uint32_t)));
+            HIP_TRY(hipMemcpyAsync(ir.d_frag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->wq));
+            HIP_TRY(hipStreamSynchronize(p->wq));               // `frag` is pageable; the audio side must find the IR complete
+        }
+        *out = sg.release();
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
+{
+    if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
+    if (!staged->is_ir) return fail(AIDAX_ERR_ARG, "staged object holds a model: commit it with aidax_pool_commit_model");
+    if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged IR was committed already");
+    if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged IR belongs to another pool");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        p->enter_stream(p->q);
+        HIP_TRY(hipEventRecord(staged->fence, p->q));          // the retired fragments are free once the passes before this point have run
+        staged->fenced = true;
+        std::swap(p->ir, staged->ir);
+        (void)p->ir_history();
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate)
+{
+    aidax_staged* sg = nullptr;
+    int rc = aidax_pool_prepare_ir(p, taps, n_taps, samplerate, &sg);
+    if (rc != AIDAX_OK) return rc;
+    rc = aidax_pool_commit_ir(p, sg);
+    aidax_staged_free(sg);
     return rc;
 }
 
@@ -1143,6 +1284,8 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
         p->enter_stream(p->q);
         const ModelSlot& m = p->cur;
         HIP_TRY(launch_init_streams(p->d_st + stream, 1, p->q));      // instantiate(), :283-321
+        if (IrHistory* h = p->ir_history())                            // a fresh instance has no past for the IR to sound
+            HIP_TRY(hipMemsetAsync(h->ring + static_cast<size_t>(stream) * h->ring_row, 0, sizeof(float) * h->ring_row, p->q));
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st + stream, p_targets[0], p_targets[1], p->q));
         if (m.has_model) {
             // a fresh DynamicModel for this stream only: the launch arguments view the pool as one stream

@@ -203,9 +203,37 @@ AIDAX_API int  aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged);
 AIDAX_API void aidax_staged_free(aidax_staged* staged);
 AIDAX_API int  aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode);
 
+/* Cabinet impulse response (IR): an optional last stage of every stream's run(), after the master gain ramp (rt-neural-generic.cpp:654-655).
+ * A pool holds at most one IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models); while
+ * it does, every stream's output block is the causal convolution of the block the pool would have returned without it (`dry`) with h:
+ *     y[s][t] = sum_{k < L} h[k] * dry[s][t - k]
+ * whatever the stream's `enabled` control says (the cabinet sits after the plugin). No latency, any block length the pool takes; n_frames == 0
+ * touches nothing. The IR is applied by the matrix cores (k_ir_conv) to fp32 accuracy, and an IR of a single tap that is a power of two
+ * (a delay, a gain of 2^-k) reproduces the dry signal exactly. Output is deterministic (the same inputs give the same bits).
+ * History: the first aidax_pool_prepare_ir allocates, per stream, a ring of the latest dry samples in device memory; from then on every
+ * pass feeds it, also while no IR is attached, so an IR committed later starts on the true past. Samples from before that first prepare,
+ * or from before a stream's aidax_pool_reset_stream, count as 0. A pool that was never given an IR allocates and launches nothing for it.
+ * The IR swap is split between the threads like a model swap:
+ * aidax_ir_load_wav      host only: RIFF/WAVE, PCM 16 / 24 / 32-bit, IEEE float 32-bit, WAVE_FORMAT_EXTENSIBLE of either; channel 0 of
+ *                        a multi-channel file; integers scaled to [-1, 1) by 2^(bits-1); unknown chunks skipped. Copies min(cap, frames)
+ *                        samples to `taps` (cap == 0: only *n_frames and *samplerate; taps may then be NULL) and reports the file's frame
+ *                        count and rate. AIDAX_ERR_IO when the file cannot be read, AIDAX_ERR_ARG (with the reason in aidax_last_error)
+ *                        for a malformed or unsupported file: truncated chunks, a data size past the end of the file, no frames, other tags.
+ * aidax_pool_prepare_ir  WORKER thread: the history on first use, the IR packed into the kernel's operand form and uploaded on the worker
+ *                        stream; blocks until done. taps == NULL prepares the removal of the IR. AIDAX_ERR_ARG for L == 0 or L > 8192,
+ *                        a tap that is not finite, or a samplerate other than the pool's host rate (no resampling).
+ * aidax_pool_commit_ir   AUDIO thread, between passes: swaps the prepared IR in (no allocation, no free, no wait); `staged` then holds
+ *                        the retired IR for aidax_staged_free on the worker.
+ * aidax_pool_set_ir      prepare + commit + free in one blocking call.
+ * aidax_pool_process with an IR: the pass's completion word is written behind the IR stage, never by the model's kernel. */
+AIDAX_API int  aidax_ir_load_wav(const char* path, float* taps, uint32_t cap, uint32_t* n_frames, double* samplerate);
+AIDAX_API int  aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out);
+AIDAX_API int  aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged);
+AIDAX_API int  aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
- * staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
+ * reset_stream, commit_model, commit_ir, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
+ * prepare_ir, staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync wait for the GPU (for the stream that carries the pass, never for the
  * device). */
 

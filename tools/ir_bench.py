@@ -1,0 +1,101 @@
+"""Cost of the cabinet IR stage (aidax_pool_set_ir, k_ir_conv) on the shipped library: one JSON line.
+
+  cfg2          1024 streams of the LSTM-32 amp model x 256-frame blocks, device-resident, aidax_pool_process_device back to back on one
+                torch stream, timed with torch events over --steps blocks: us per block without an IR and with an 8192-tap IR
+  one_stream    the LV2 instance's pool (one stream, the bundled LSTM-12 model): aidax_pool_process round trip (host in, host out),
+                median and p99 of --calls calls, without and with the IR, at 64 and 256 frames
+
+The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs). Under rocprofv3 --kernel-trace
+--stats the k_ir_conv / k_ir_reduce / k_ir_append rows are the stage's kernels alone.
+
+    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400]
+"""
+import argparse
+import importlib
+import json
+import os
+import sys
+import tempfile
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+FLOOR_US = 10.5          # cfg2 at 8192 taps: 2.15e9 MACs as six bf16 products on 16x16x32 MFMAs at 16 cycles per SIMD, 2.4 GHz
+
+
+def cabinet_ir(L=8192, seed=8192):
+    rng = np.random.default_rng(seed)
+    t = np.arange(L)
+    return (rng.standard_normal(L) * np.exp(-t / (L / 6.0)) * 0.05).astype(np.float32)
+
+
+def cfg2_us(ax, W, torch, path, with_ir, steps, warmup):
+    S, n = 1024, 256
+    pool = ax.Pool(S, n)
+    pool.set_model(ax.Model(path))
+    if with_ir:
+        pool.set_ir(cabinet_ir())
+    x = torch.from_numpy(W.signal(S, n, seed=5)).cuda()
+    y = torch.empty_like(x)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            pool.process_device(x.data_ptr(), y.data_ptr(), n, s.cuda_stream)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record(s)
+        for _ in range(steps):
+            pool.process_device(x.data_ptr(), y.data_ptr(), n, s.cuda_stream)
+        e1.record(s)
+    s.synchronize()
+    us = e0.elapsed_time(e1) * 1000.0 / steps
+    pool.close()
+    return us
+
+
+def one_stream(ax, W, path, with_ir, frames, calls):
+    pool = ax.Pool(1, frames)
+    pool.set_model(ax.Model(path))
+    if with_ir:
+        pool.set_ir(cabinet_ir())
+    x = np.ascontiguousarray(W.signal(1, frames, seed=6))
+    for _ in range(50):
+        pool.process(x)
+    t = np.empty(calls)
+    for i in range(calls):
+        t0 = time.perf_counter()
+        pool.process(x)
+        t[i] = time.perf_counter() - t0
+    pool.close()
+    return {"p50_us": round(float(np.percentile(t, 50)) * 1e6, 2), "p99_us": round(float(np.percentile(t, 99)) * 1e6, 2)}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--steps", type=int, default=400)
+    ap.add_argument("--warmup", type=int, default=50)
+    ap.add_argument("--calls", type=int, default=400)
+    a = ap.parse_args()
+    import torch
+    ax = importlib.import_module("aidadsp-lv2_amd")
+    W = ax.workloads
+    d = tempfile.mkdtemp(prefix="ir_bench_")
+    cfg2 = W.write_model(W.make_model("lstm", 32, 1, seed=32), os.path.join(d, "lstm32.json"))
+    lv2 = os.path.join(ROOT, "tests", "golden", "models", "tw40_california_clean_deerinkstudios.json")
+    out = {"lib": os.path.relpath(ax.lib_path(), ROOT), "ir_taps": 8192, "steps": a.steps}
+    dry = cfg2_us(ax, W, torch, cfg2, False, a.steps, a.warmup)
+    wet = cfg2_us(ax, W, torch, cfg2, True, a.steps, a.warmup)
+    out["cfg2"] = {"us_per_block_no_ir": round(dry, 2), "us_per_block_ir": round(wet, 2), "ir_stage_us": round(wet - dry, 2),
+                   "ir_stage_over_floor": round((wet - dry) / FLOOR_US, 2), "floor_us": FLOOR_US}
+    out["one_stream"] = {}
+    for frames in (64, 256):
+        out["one_stream"][str(frames)] = {"no_ir": one_stream(ax, W, lv2, False, frames, a.calls),
+                                          "ir": one_stream(ax, W, lv2, True, frames, a.calls)}
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()
