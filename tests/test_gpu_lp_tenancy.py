@@ -205,6 +205,36 @@ def test_a_reported_give_up_is_silence_for_that_block_and_the_pool_falls_back(tm
     pool.close()
 
 
+def test_a_reported_give_up_with_an_ir_is_silence_and_the_history_starts_after_it(tmp_path, monkeypatch):
+    """The same hook on a pool with a cabinet IR: the block that gave up is silence as without one, and take_lp_fault clears the IR
+    history, so every later block is the convolution of the dry signal from the block after the give-up on (the wrong block never
+    sounds through the IR's tail). Dry reference: the oracle's output with the failed block zeroed; bound: the model's 2e-6 through
+    ||h||_1, plus the IR stage's own per-sample bound (tests/test_gpu_ir.py)."""
+    from tests.test_gpu_ir import _ir, _tau
+    monkeypatch.setenv("AIDAX_TUNE", "16")
+    path, spec = _model_file(tmp_path, "l32x2i", kind="lstm", hidden=32, input_size=1, seed=324, n_rnn=2)
+    m = ax.Model(path)
+    S, n, nblk = 40, 128, 8
+    x = modelgen.signal(S, n * nblk, seed=10)
+    dry = O.run_streams(spec, O.default_controls(), x, n)
+    dry[:, :n] = 0.0
+    h = _ir(300, 325)
+    pool = ax.Pool(S, n)
+    pool.set_model(m)
+    pool.set_ir(h)
+    assert pool.kernel_name == "k_mfma_ls"
+    blk = np.ascontiguousarray(x[:, :n])
+    out = np.full_like(blk, 7.0)
+    rc = ax.lib().aidax_pool_process(pool.h, blk.ctypes.data_as(_fp), out.ctypes.data_as(_fp), n)
+    assert rc == ERR_DEVICE and "hand-over" in _last_error()
+    assert not out.any()                                                     # silence, never garbage
+    assert pool.kernel_name == "k_chain+k_mfma"
+    got = np.concatenate([out] + [pool.process(np.ascontiguousarray(x[:, b * n:(b + 1) * n])) for b in range(1, nblk)], axis=1)
+    pool.sync()
+    pool.close()
+    _tau("lp_give_up", got, dry, h, slack=2e-6 * float(np.abs(h.astype(np.float64)).sum()))
+
+
 def test_hub_delivers_silence_for_a_pass_that_gave_up_and_recovers(tmp_path, monkeypatch):
     """The same hook under the hub: the instance that reads the row of a faulted pass gets AIDAX_ERR_DEVICE and silence
     (never the row), later passes run on k_mfma and the audio is the oracle's again, one period late."""

@@ -31,6 +31,17 @@ NOT_REPRODUCIBLE = (
     "test_deadline_",                                        # the hub's deadline tests: which pass a block joins depends on the wall clock
 )
 
+# tests whose assertion is a wall-clock bound: on a busy box such a test may miss its bar once, on either leg. A failure of one of these
+# (and of nothing else) gets ONE more run on the shipped library, alone; any other failure fails the leg
+WALL_CLOCK = (
+    ("test_deadline_one_stalled_instance_does_not_hold_the_others", "run() must return within half a period (two on this leg) and the "
+     "deadline must close at least one pass: a descheduled host or launcher thread misses that"),
+    ("test_deadline_that_splits_a_period_loses_nothing", "the launcher thread must close at least one pass by the 1.2 ms deadline inside "
+     "a 5 ms pause: a launcher descheduled for longer does not"),
+    ("test_hub_under_real_time_pacing_with_threads", "at most 5 % silent blocks: how many periods three paced host threads miss "
+     "depends on how busy the box is"),
+)
+
 
 @pytest.mark.gpu
 def test_hook_free_suite_on_the_shipped_library(tmp_path):
@@ -46,12 +57,13 @@ def test_hook_free_suite_on_the_shipped_library(tmp_path):
         with open(os.path.join(gp, "ship_leg_pytest.txt"), "w") as f:
             f.write(r.stdout + r.stderr)
     tail = r.stdout[-6000:] + r.stderr[-2000:]
-    # a test with a wall-clock bar (the hub's deadline tests, the latency audits) may miss it once on a busy box, on either leg: what
-    # failed gets ONE more run on the shipped library, alone, and the report says so
+    # a test with a wall-clock bar (WALL_CLOCK) may miss it once on a busy box: what failed gets ONE more run on the shipped library,
+    # alone, and the report says so. Any other failure, or an error, fails the leg as it stands
     second_attempt = []
     if r.returncode != 0:
         failed = re.findall(r"^FAILED (\S+)", r.stdout, flags=re.M)
-        assert failed and len(failed) <= 3, tail
+        others = [k for k in failed if not any(name in k for name, _ in WALL_CLOCK)]
+        assert failed and not others, (others, tail)
         env2 = dict(env, AIDAX_DIGEST_OUT=str(tmp_path / "ship_retry.json"))
         r2 = subprocess.run(base + failed, cwd=ROOT, env=env2, capture_output=True, text=True, timeout=900)
         assert r2.returncode == 0, (failed, r2.stdout[-4000:])
@@ -62,11 +74,18 @@ def test_hook_free_suite_on_the_shipped_library(tmp_path):
     skipped = int(m.group(1)) if m else 0
     ship = json.loads(out.read_text())
     assert os.path.samefile(ship["lib"], conftest.SHIP_LIB)
+    if second_attempt:                                                 # a retried test is compared on what its second run drew
+        retry = json.loads((tmp_path / "ship_retry.json").read_text())
+        assert os.path.samefile(retry["lib"], conftest.SHIP_LIB)
+        for k in second_attempt:
+            ship["digests"].pop(k, None)
+            if k in retry["digests"]:
+                ship["digests"][k] = retry["digests"][k]
     assert passed >= 120, (passed, skipped, tail)                      # the hook-free part is most of the suite
 
     # bit identity of the two builds on everything both legs ran
     mine = {k: [hex(v[0]), v[1]] for k, v in conftest.DIGESTS.items()}
-    common = sorted(k for k in ship["digests"] if k in mine and k not in second_attempt and not any(t in k for t in NOT_REPRODUCIBLE))
+    common = sorted(k for k in ship["digests"] if k in mine and not any(t in k for t in NOT_REPRODUCIBLE))
     differ = [k for k in common if ship["digests"][k] != mine[k]]
     report = {"ship_passed": passed, "ship_skipped_need_a_hook": skipped, "tests_compared": len(common),
               "arrays_compared": sum(mine[k][1] for k in common), "differ": differ, "passed_on_second_attempt": second_attempt}
