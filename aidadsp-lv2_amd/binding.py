@@ -15,6 +15,8 @@ _HEADER = os.path.join(_ROOT, "include", "aidax.h")
 
 ALL_STREAMS = -1
 START_WARMUP, START_RESET = 0, 1
+IR_SLOTS = 64                     # AIDAX_IR_SLOTS: bank slots per pool, besides the pool IR
+IR_POOL, IR_NONE = -1, -2         # a stream's IR: the pool IR (default), none, or a bank slot 0 .. IR_SLOTS - 1
 _fp = C.POINTER(C.c_float)
 
 
@@ -159,6 +161,10 @@ def lib() -> C.CDLL:
     L.aidax_pool_prepare_ir.argtypes = [vp, _fp, u32, C.c_double, C.POINTER(vp)]
     L.aidax_pool_commit_ir.argtypes = [vp, vp]
     L.aidax_pool_set_ir.argtypes = [vp, _fp, u32, C.c_double]
+    L.aidax_pool_prepare_ir_slot.argtypes = [vp, u32, _fp, u32, C.c_double, C.POINTER(vp)]
+    L.aidax_pool_set_ir_slot.argtypes = [vp, u32, _fp, u32, C.c_double]
+    L.aidax_pool_assign_ir.argtypes = [vp, i32, i32]
+    L.aidax_pool_stream_ir.argtypes = [vp, u32, C.POINTER(i32)]
     _lib = L
     return L
 
@@ -355,6 +361,30 @@ class Pool:
     def commit_ir(self, staged: C.c_void_p):
         """audio half: swaps the staged IR in; `staged` then holds the retired one (free it with staged_free)"""
         _check(lib().aidax_pool_commit_ir(self.h, staged))
+
+    def set_ir_slot(self, slot: int, taps: Optional[np.ndarray], samplerate: Optional[float] = None):
+        """aidax_pool_set_ir_slot: load bank slot `slot` (taps None: empty it); samplerate defaults to the pool's"""
+        t = None if taps is None else _f32(taps)
+        _check(lib().aidax_pool_set_ir_slot(self.h, slot, None if t is None else t.ctypes.data_as(_fp), 0 if t is None else t.size,
+                                            self.samplerate if samplerate is None else samplerate))
+
+    def prepare_ir_slot(self, slot: int, taps: Optional[np.ndarray], samplerate: Optional[float] = None) -> C.c_void_p:
+        """worker half of a bank slot's swap: returns the staged handle for commit_ir / staged_free"""
+        t = None if taps is None else _f32(taps)
+        sg = C.c_void_p()
+        _check(lib().aidax_pool_prepare_ir_slot(self.h, slot, None if t is None else t.ctypes.data_as(_fp), 0 if t is None else t.size,
+                                                self.samplerate if samplerate is None else samplerate, C.byref(sg)))
+        return sg
+
+    def assign_ir(self, stream: int, slot: int):
+        """aidax_pool_assign_ir: the IR `stream` (ALL_STREAMS: every stream) goes through from the next pass on (IR_POOL, IR_NONE or a
+        bank slot)"""
+        _check(lib().aidax_pool_assign_ir(self.h, stream, slot))
+
+    def stream_ir(self, stream: int) -> int:
+        v = C.c_int32(0)
+        _check(lib().aidax_pool_stream_ir(self.h, stream, C.byref(v)))
+        return v.value
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

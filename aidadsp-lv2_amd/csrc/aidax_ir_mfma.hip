@@ -1,5 +1,5 @@
-// aidax_ir_mfma.hip — the cabinet impulse-response stage: every stream's block convolved with the pool's IR, causally and without
-// latency, as a time-domain Toeplitz GEMM on the matrix cores (k_ir_conv), behind the whole run() of the pass.
+// aidax_ir_mfma.hip — the cabinet impulse-response stage: every stream's block convolved with its IR (the pool IR or a bank slot),
+// causally and without latency, as a time-domain Toeplitz GEMM on the matrix cores (k_ir_conv), behind the whole run() of the pass.
 //
 //   y[s][t] = sum_{k < L} h[k] * x[s][t - k]        x = the dry signal (what the pool returns without an IR), L <= 8192
 //
@@ -81,16 +81,19 @@ __global__ __launch_bounds__(256) void k_ir_append(float* __restrict__ ring, uin
     if (k < kIrMirror) r[k + mask + 1] = v;
 }
 
-// grid: (wave tiles along the block) x (groups of 64 streams) x S; one wave per workgroup
+// grid: (wave tiles along the block) x (work items of the plan) x S; one wave per workgroup. A work item is one IR and up to 64 streams
+// that use it (aidax_pool.cpp: the plan): its fragments, diagonals and stream count are wave-uniform, and a lane finds its stream in each
+// of the four groups through the item's stream list. With every stream on one IR the plan is the identity (item i: streams 64 i ..), the
+// grid of a one-IR pool.
 __global__ __launch_bounds__(64) void k_ir_conv(IrArgs a)
 {
     const int lane = threadIdx.x;
     const int nl = lane & 15, g = lane >> 4;
     const int T = 64 * static_cast<int>(blockIdx.x);                  // the wave's first output frame
-    const uint32_t s0 = 64u * blockIdx.y;                              // its first stream
+    const IrItem item = a.items[blockIdx.y];
     const int split = static_cast<int>(blockIdx.z);
     const int n = static_cast<int>(a.n_frames);
-    const int Q = static_cast<int>(a.n_diag);
+    const int Q = static_cast<int>(item.n_diag);
     const int nb = (Q + 1) / 2 + 1;                                    // windows b = 0 .. nb-1 meet a diagonal q in [0, Q)
     const int per = (nb + static_cast<int>(a.n_splits) - 1) / static_cast<int>(a.n_splits);
     const int b_lo = split * per, b_hi = b_lo + per < nb ? b_lo + per : nb;
@@ -98,16 +101,20 @@ __global__ __launch_bounds__(64) void k_ir_conv(IrArgs a)
     bool tile_on[kIrTiles], grp_on[kIrGroups];
 #pragma unroll
     for (int i = 0; i < kIrTiles; ++i) tile_on[i] = T + 16 * i < n;
+    // a group with streams of the pass: its first one is (an item's list is in stream order, so a group that starts at or beyond a
+    // prefix pass's n_streams has no lane on, and skips its MFMAs as the one-IR kernel skipped the groups past the prefix)
 #pragma unroll
-    for (int i = 0; i < kIrGroups; ++i) grp_on[i] = s0 + 16u * i < a.n_streams;
-    // this lane's stream in each group, and its ring row (a lane past the pool's end reads zeros)
+    for (int i = 0; i < kIrGroups; ++i) grp_on[i] = 16u * i < item.count && a.streams[item.first + 16u * i] < a.n_streams;
+    // this lane's stream in each group, and its ring row (a lane past the item's end, or on a stream past the pass's prefix, reads zeros)
     const float* rows[kIrGroups];
+    uint32_t strm[kIrGroups];
     bool lane_on[kIrGroups];
 #pragma unroll
     for (int i = 0; i < kIrGroups; ++i) {
-        const uint32_t s = s0 + 16u * i + static_cast<uint32_t>(nl);
-        lane_on[i] = s < a.n_streams;
-        rows[i] = a.ring + static_cast<size_t>(lane_on[i] ? s : 0u) * a.ring_row;
+        const uint32_t k = 16u * i + static_cast<uint32_t>(nl);
+        strm[i] = k < item.count ? a.streams[item.first + k] : 0u;
+        lane_on[i] = k < item.count && strm[i] < a.n_streams;
+        rows[i] = a.ring + static_cast<size_t>(lane_on[i] ? strm[i] : 0u) * a.ring_row;
     }
     const bool aligned = (a.pos & 3u) == 0u;                           // the lanes' 8-frame windows start on 16-byte boundaries
 
@@ -117,7 +124,7 @@ __global__ __launch_bounds__(64) void k_ir_conv(IrArgs a)
 #pragma unroll
         for (int j = 0; j < kIrGroups; ++j) acc[i][j] = f32x4{ 0.f, 0.f, 0.f, 0.f };
 
-    const ir_u32x4* frag = reinterpret_cast<const ir_u32x4*>(a.frag) + lane;
+    const ir_u32x4* frag = reinterpret_cast<const ir_u32x4*>(item.frag) + lane;
     auto load_a = [&](int q, ir_u32x4 (&f)[3]) {
         if (q >= 0 && q < Q) {
 #pragma unroll
@@ -179,12 +186,12 @@ __global__ __launch_bounds__(64) void k_ir_conv(IrArgs a)
             for (int term = 0; term < 3; ++term) alo[k][term] = ahi[k][term];
     }
 
-    // a lane holds frames t0 + 4 g .. + 3 of stream (group base + nl): the output row, or this split's partial row
+    // a lane holds frames t0 + 4 g .. + 3 of its stream in group i: the output row, or this split's partial row
     float* dst = a.n_splits > 1 ? a.part + static_cast<size_t>(split) * a.n_streams * a.n_frames : a.out;
 #pragma unroll
     for (int i = 0; i < kIrGroups; ++i) {
         if (!grp_on[i] || !lane_on[i]) continue;
-        float* r = dst + static_cast<size_t>(s0 + 16u * i + static_cast<uint32_t>(nl)) * a.n_frames;
+        float* r = dst + static_cast<size_t>(strm[i]) * a.n_frames;
 #pragma unroll
         for (int t = 0; t < kIrTiles; ++t) {
             const int f = T + 16 * t + 4 * g;
@@ -196,23 +203,30 @@ __global__ __launch_bounds__(64) void k_ir_conv(IrArgs a)
     }
 }
 
-// the K split's partial sums, added in split order (the same bits on every run)
-__global__ __launch_bounds__(256) void k_ir_reduce(const float* __restrict__ part, float* __restrict__ out, uint32_t count, uint32_t n_splits)
+// the K split's partial sums, added in split order (the same bits on every run), for the streams of the plan only: a stream on no IR
+// keeps its dry row. Thread i: entry i / n_frames of the stream lists, frame i % n_frames
+__global__ __launch_bounds__(256) void k_ir_reduce(const float* __restrict__ part, float* __restrict__ out, const uint32_t* __restrict__ streams,
+                                                   uint32_t n_listed, uint32_t n_streams, uint32_t n_frames, uint32_t n_splits)
 {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= count) return;
+    if (i >= n_listed * n_frames) return;
+    const uint32_t j = i / n_frames;
+    const uint32_t s = streams[j];
+    if (s >= n_streams) return;
+    const uint32_t e = s * n_frames + (i - j * n_frames);
+    const size_t count = static_cast<size_t>(n_streams) * n_frames;
     // (eight loads in flight at a time, added in split order: a small pool's 64 partials cost 8 round trips, not 64)
-    float v = part[i];
+    float v = part[e];
     uint32_t k = 1;
     for (; k + 8 <= n_splits; k += 8) {
         float t[8];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) t[j] = part[static_cast<size_t>(k + j) * count + i];
+        for (int j8 = 0; j8 < 8; ++j8) t[j8] = part[static_cast<size_t>(k + j8) * count + e];
 #pragma unroll
-        for (int j = 0; j < 8; ++j) v += t[j];
+        for (int j8 = 0; j8 < 8; ++j8) v += t[j8];
     }
-    for (; k < n_splits; ++k) v += part[static_cast<size_t>(k) * count + i];
-    out[i] = v;
+    for (; k < n_splits; ++k) v += part[static_cast<size_t>(k) * count + e];
+    out[e] = v;
 }
 
 }  // namespace
@@ -220,10 +234,10 @@ __global__ __launch_bounds__(256) void k_ir_reduce(const float* __restrict__ par
 uint32_t ir_diagonals(uint32_t n_taps) { return (n_taps + 30u) / 16u + 1u; }
 uint32_t ir_windows(uint32_t n_diag) { return (n_diag + 1u) / 2u + 1u; }
 
-uint32_t ir_k_splits(uint32_t n_streams, uint32_t n_frames, uint32_t n_diag, int cus, uint32_t cap)
+uint32_t ir_k_splits(uint32_t n_items, uint32_t n_frames, uint32_t n_diag, int cus, uint32_t cap)
 {
-    if (n_frames == 0 || n_streams == 0) return 1;
-    const uint32_t waves = ((n_frames + 63u) / 64u) * ((n_streams + 63u) / 64u);
+    if (n_frames == 0 || n_items == 0) return 1;
+    const uint32_t waves = ((n_frames + 63u) / 64u) * n_items;
     const uint32_t target = 4u * static_cast<uint32_t>(cus > 0 ? cus : 256);         // a wave per SIMD
     uint32_t s = (target + waves - 1u) / waves;
     const uint32_t nb = ir_windows(n_diag);
@@ -243,12 +257,12 @@ hipError_t launch_ir_append(float* ring, uint32_t ring_row, uint32_t mask, uint3
 
 hipError_t launch_ir_conv(const IrArgs& a, hipStream_t q)
 {
-    if (a.n_frames == 0 || a.n_streams == 0) return hipSuccess;
-    hipLaunchKernelGGL(k_ir_conv, dim3((a.n_frames + 63u) / 64u, (a.n_streams + 63u) / 64u, a.n_splits), dim3(64), 0, q, a);
+    if (a.n_frames == 0 || a.n_items == 0 || a.n_listed == 0) return hipSuccess;
+    hipLaunchKernelGGL(k_ir_conv, dim3((a.n_frames + 63u) / 64u, a.n_items, a.n_splits), dim3(64), 0, q, a);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess || a.n_splits <= 1) return e;
-    const uint32_t count = a.n_streams * a.n_frames;
-    hipLaunchKernelGGL(k_ir_reduce, dim3((count + 255u) / 256u), dim3(256), 0, q, a.part, a.out, count, a.n_splits);
+    const uint32_t count = a.n_listed * a.n_frames;
+    hipLaunchKernelGGL(k_ir_reduce, dim3((count + 255u) / 256u), dim3(256), 0, q, a.part, a.out, a.streams, a.n_listed, a.n_streams, a.n_frames, a.n_splits);
     return hipGetLastError();
 }
 

@@ -96,20 +96,30 @@ hipError_t launch_reset_for_model(StreamState* st, float* nn, uint32_t n_streams
 // mask = R - 1) whose first kIrMirror slots are repeated behind slot R - 1; `pos` is the ring slot of the block's first frame.
 constexpr uint32_t kIrMaxTaps = 8192;
 constexpr uint32_t kIrMirror = 32;
-struct IrArgs {
+constexpr uint32_t kIrItemStreams = 64;        // streams of one work item: the 4 x 16 MFMA columns of a k_ir_conv wave
+// One work item of k_ir_conv's plan: an IR and up to 64 streams that use it, streams[first .. first + count - 1] in stream order
+struct IrItem {
     const uint32_t* frag;        // the IR's A fragments: [n_diag][3 terms][64 lanes][4 words] (pack_ir_fragments)
+    uint32_t n_diag, count, first, pad;
+};
+struct IrArgs {
+    const IrItem* items;         // the plan: one item per blockIdx.y
+    const uint32_t* streams;     // the items' stream lists, one after the other
     const float* ring;
     float* out;                  // [n_streams][n_frames]
     float* part;                 // n_splits > 1: [n_splits][n_streams][n_frames] partial sums
-    uint32_t n_diag, ring_row, mask, pos, n_streams, n_frames, n_splits;
+    uint32_t n_items, n_listed, ring_row, mask, pos, n_streams, n_frames, n_splits;      // n_listed: entries of `streams` the items use;
+                                                                                         // n_streams: the pass's (prefix), an entry at or beyond it is skipped
 };
 uint32_t ir_diagonals(uint32_t n_taps);        // diagonals of 16 frames an IR of n_taps reaches: (n_taps + 30) / 16 + 1
 uint32_t ir_windows(uint32_t n_diag);          // 32-frame input windows a wave walks
-// workgroups the windows are split over (a wave per SIMD of a device with `cus` CUs, at least four windows each, at most `cap`)
-uint32_t ir_k_splits(uint32_t n_streams, uint32_t n_frames, uint32_t n_diag, int cus, uint32_t cap);
+// workgroups the windows are split over (a wave per SIMD of a device with `cus` CUs, at least four windows each, at most `cap`), for a
+// grid of `n_items` work items of up to 64 streams; n_diag: the longest IR's
+uint32_t ir_k_splits(uint32_t n_items, uint32_t n_frames, uint32_t n_diag, int cus, uint32_t cap);
 hipError_t launch_ir_append(float* ring, uint32_t ring_row, uint32_t mask, uint32_t pos, const float* dry, uint32_t n_streams, uint32_t n_frames,
                             hipStream_t q);
-hipError_t launch_ir_conv(const IrArgs& a, hipStream_t q);     // k_ir_conv (+ k_ir_reduce when n_splits > 1): out = the IR over the ring
+// k_ir_conv (+ k_ir_reduce when n_splits > 1): the rows of the plan's streams = each one's IR over its ring; other rows are not touched
+hipError_t launch_ir_conv(const IrArgs& a, hipStream_t q);
 
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 

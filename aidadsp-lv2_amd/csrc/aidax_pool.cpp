@@ -19,6 +19,49 @@
 #include "aidax_internal.h"
 #include "aidax_kernels.h"
 
+#ifdef AIDAX_TEST_HOOKS
+// Test build only: per thread, how often this file calls each HIP runtime entry point it uses (every call site, checked with HIP_TRY or
+// not) and each IR stage launcher, read and cleared by aidax_test_hip_calls below. A fixed table per thread: counting allocates nothing.
+// (tests/test_gpu_ir_bank_rt.py: the audio-thread calls allocate, free and wait for nothing.)
+namespace aidax {
+namespace {
+struct HipCallTable { const char* name[48]; uint64_t n[48]; int used; };
+thread_local HipCallTable hip_calls{};
+void note_hip_call(const char* name)
+{
+    for (int i = 0; i < hip_calls.used; ++i)
+        if (std::strcmp(hip_calls.name[i], name) == 0) { ++hip_calls.n[i]; return; }
+    if (hip_calls.used < 48) { hip_calls.name[hip_calls.used] = name; hip_calls.n[hip_calls.used++] = 1; }
+}
+}  // namespace
+}  // namespace aidax
+#define AIDAX_COUNTED(fn, ...) (aidax::note_hip_call(#fn), ::fn(__VA_ARGS__))
+#define hipSetDevice(...) AIDAX_COUNTED(hipSetDevice, __VA_ARGS__)
+#define hipMalloc(...) AIDAX_COUNTED(hipMalloc, __VA_ARGS__)
+#define hipHostMalloc(...) AIDAX_COUNTED(hipHostMalloc, __VA_ARGS__)
+#define hipHostRegister(...) AIDAX_COUNTED(hipHostRegister, __VA_ARGS__)
+#define hipEventCreateWithFlags(...) AIDAX_COUNTED(hipEventCreateWithFlags, __VA_ARGS__)
+#define hipStreamCreateWithFlags(...) AIDAX_COUNTED(hipStreamCreateWithFlags, __VA_ARGS__)
+#define hipStreamCreateWithPriority(...) AIDAX_COUNTED(hipStreamCreateWithPriority, __VA_ARGS__)
+#define hipFree(...) AIDAX_COUNTED(hipFree, __VA_ARGS__)
+#define hipHostFree(...) AIDAX_COUNTED(hipHostFree, __VA_ARGS__)
+#define hipHostUnregister(...) AIDAX_COUNTED(hipHostUnregister, __VA_ARGS__)
+#define hipEventDestroy(...) AIDAX_COUNTED(hipEventDestroy, __VA_ARGS__)
+#define hipStreamDestroy(...) AIDAX_COUNTED(hipStreamDestroy, __VA_ARGS__)
+#define hipStreamSynchronize(...) AIDAX_COUNTED(hipStreamSynchronize, __VA_ARGS__)
+#define hipEventSynchronize(...) AIDAX_COUNTED(hipEventSynchronize, __VA_ARGS__)
+#define hipDeviceSynchronize(...) AIDAX_COUNTED(hipDeviceSynchronize, __VA_ARGS__)
+#define hipMemcpy(...) AIDAX_COUNTED(hipMemcpy, __VA_ARGS__)
+#define hipMemcpyAsync(...) AIDAX_COUNTED(hipMemcpyAsync, __VA_ARGS__)
+#define hipMemsetAsync(...) AIDAX_COUNTED(hipMemsetAsync, __VA_ARGS__)
+#define hipEventRecord(...) AIDAX_COUNTED(hipEventRecord, __VA_ARGS__)
+#define hipEventQuery(...) AIDAX_COUNTED(hipEventQuery, __VA_ARGS__)
+#define hipStreamWaitEvent(...) AIDAX_COUNTED(hipStreamWaitEvent, __VA_ARGS__)
+#define hipStreamWriteValue32(...) AIDAX_COUNTED(hipStreamWriteValue32, __VA_ARGS__)
+#define launch_ir_append(...) (aidax::note_hip_call("launch_ir_append"), aidax::launch_ir_append(__VA_ARGS__))
+#define launch_ir_conv(...) (aidax::note_hip_call("launch_ir_conv"), aidax::launch_ir_conv(__VA_ARGS__))
+#endif
+
 using namespace aidax;
 
 namespace aidax {
@@ -313,22 +356,34 @@ struct IrSlot {
     uint32_t* d_frag = nullptr;      // nullptr: no IR
     uint32_t n_taps = 0, n_diag = 0;
 };
-// ... and the stage's history, allocated by the first aidax_pool_prepare_ir and fed by every pass from then on (k_ir_append): per stream
-// a ring of the last R >= 8192 + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial sums (aidax_ir_mfma.hip)
+constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
+
+// ... and the stage's history, allocated by the first aidax_pool_prepare_ir / aidax_pool_prepare_ir_slot and fed by every pass from then
+// on (k_ir_append): per stream a ring of the last R >= 8192 + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial
+// sums (aidax_ir_mfma.hip). With it, the device copy of the plan (the IR items k_ir_conv runs: [plan_items_cap] IrItem, then the stream
+// lists) and the pinned snapshots it is uploaded from, stream-ordered with the passes like the control records (flush_ctl).
 struct IrHistory {
     float* ring = nullptr;
     float* part = nullptr;
     uint32_t ring_row = 0, mask = 0, split_cap = 1;
+    uint8_t* d_plan = nullptr;
+    uint8_t* h_plan[kCtlRing] = {};
+    hipEvent_t plan_ev[kCtlRing] = {};
+    bool plan_used[kCtlRing] = {};
+    int plan_next = 0;                   // (audio side)
 };
 void free_ir_history(IrHistory* h)
 {
     if (!h) return;
     if (h->ring) (void)hipFree(h->ring);
     if (h->part) (void)hipFree(h->part);
+    if (h->d_plan) (void)hipFree(h->d_plan);
+    for (int k = 0; k < kCtlRing; ++k) {
+        if (h->h_plan[k]) (void)hipHostFree(h->h_plan[k]);
+        if (h->plan_ev[k]) (void)hipEventDestroy(h->plan_ev[k]);
+    }
     delete h;
 }
-
-constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
 constexpr size_t kStagingLimit = size_t(64) << 20;      // pinned staging per direction for aidax_pool_process
 constexpr size_t kZeroCopyLimit = size_t(64) << 10;     // blocks up to this size are read / written by the kernels in place in pinned host memory
 
@@ -344,7 +399,8 @@ struct aidax_staged {
     StreamState* d_pst = nullptr;    // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
     hipEvent_t fence = nullptr;      // recorded by the commit: everything that may still touch the retired buffers precedes it
     bool fenced = false;
-    bool is_ir = false;              // an IR on its way (aidax_pool_prepare_ir): `ir` instead of `slot`
+    bool is_ir = false;              // an IR on its way (aidax_pool_prepare_ir / _slot): `ir` instead of `slot`
+    int32_t ir_slot = AIDAX_IR_POOL; // ... for the pool IR or for this bank slot
     aidax::IrSlot ir;
 };
 
@@ -404,9 +460,10 @@ struct aidax_pool {
         return true;
     }
 
-    // The cabinet IR stage: the live IR (d_frag == nullptr: none) and the history, which the worker side publishes once (the first
-    // aidax_pool_prepare_ir) and the audio side picks up at its next call; the ring slot of the next pass's first frame.
+    // The cabinet IR stage: the pool IR and the bank (d_frag == nullptr: empty), and the history, which the worker side publishes once
+    // (the first prepare of either kind) and the audio side picks up at its next call; the ring slot of the next pass's first frame.
     IrSlot ir;
+    IrSlot bank[AIDAX_IR_SLOTS];
     std::atomic<IrHistory*> ir_hist_pub{nullptr};
     IrHistory* ir_hist = nullptr;
     uint32_t ir_pos = 0;
@@ -414,6 +471,63 @@ struct aidax_pool {
     {
         if (!ir_hist) ir_hist = ir_hist_pub.load(std::memory_order_acquire);
         return ir_hist;
+    }
+    // Which IR each stream's output goes through (AIDAX_IR_POOL, AIDAX_IR_NONE or a bank slot), and the plan built from it on the audio
+    // side whenever an assignment or a commit has changed it: the streams grouped by IR into items of up to 64, the IRs in order (pool IR,
+    // slot 0, 1, ...), each IR's streams in stream order. One IR for every stream gives the identity plan (item i: streams 64 i ..).
+    // Host memory sized at creation; the device copy lives in the history (IrHistory::d_plan).
+    std::vector<int32_t> ir_assign;
+    std::vector<IrItem> plan_items;          // [ceil(n_streams / 64) + 65]
+    std::vector<uint32_t> plan_streams;      // [n_streams]
+    uint32_t plan_n_items = 0, plan_n_listed = 0, plan_max_diag = 0;
+    bool plan_identity = false, plan_dirty = true;
+    size_t plan_items_bytes() const { return plan_items.size() * sizeof(IrItem); }
+    int ir_key(uint32_t s) const                 // 0: the pool IR, 1 + j: bank slot j, -1: none (also an empty slot)
+    {
+        const int32_t a = ir_assign[s];
+        if (a == AIDAX_IR_POOL) return ir.d_frag ? 0 : -1;
+        return a >= 0 && bank[a].d_frag ? 1 + a : -1;
+    }
+    void build_ir_plan()
+    {
+        uint32_t count[AIDAX_IR_SLOTS + 1] = {}, at[AIDAX_IR_SLOTS + 1];
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            const int k = ir_key(s);
+            if (k >= 0) ++count[k];
+        }
+        uint32_t first = 0;
+        for (int k = 0; k <= AIDAX_IR_SLOTS; ++k) { at[k] = first; first += count[k]; }
+        plan_n_listed = first;
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            const int k = ir_key(s);
+            if (k >= 0) plan_streams[at[k]++] = s;
+        }
+        plan_n_items = 0; plan_max_diag = 0; plan_identity = false;
+        first = 0;
+        for (int k = 0; k <= AIDAX_IR_SLOTS; ++k) {
+            const IrSlot& sl = k == 0 ? ir : bank[k - 1];
+            for (uint32_t c = 0; c < count[k]; c += kIrItemStreams)
+                plan_items[plan_n_items++] = IrItem{ sl.d_frag, sl.n_diag, std::min(kIrItemStreams, count[k] - c), first + c, 0u };
+            if (count[k]) plan_max_diag = std::max(plan_max_diag, sl.n_diag);
+            if (count[k] == n_streams) plan_identity = true;
+            first += count[k];
+        }
+        plan_dirty = false;
+    }
+    // a dirty plan rebuilt and uploaded, stream-ordered with the passes that follow: the passes already issued keep the plan they were
+    // issued with (the device copy is overwritten behind them, from a pinned snapshot that no later rebuild touches while it is in flight)
+    void flush_ir_plan(IrHistory* h, hipStream_t s)
+    {
+        if (!plan_dirty) return;
+        build_ir_plan();
+        const int k = h->plan_next;
+        if (h->plan_used[k] && hipEventQuery(h->plan_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(h->plan_ev[k]));   // four rebuilds behind
+        std::memcpy(h->h_plan[k], plan_items.data(), plan_n_items * sizeof(IrItem));
+        std::memcpy(h->h_plan[k] + plan_items_bytes(), plan_streams.data(), plan_n_listed * sizeof(uint32_t));
+        HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], plan_items_bytes() + plan_n_listed * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(h->plan_ev[k], s));
+        h->plan_used[k] = true;
+        h->plan_next = (k + 1) % kCtlRing;
     }
 
     // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
@@ -721,6 +835,10 @@ struct aidax_pool {
     {
         if (ir.d_frag) (void)hipFree(ir.d_frag);
         ir = IrSlot{};
+        for (IrSlot& b : bank) {
+            if (b.d_frag) (void)hipFree(b.d_frag);
+            b = IrSlot{};
+        }
         free_ir_history(ir_hist_pub.exchange(nullptr));
         ir_hist = nullptr;
         if (d_ctl) (void)hipFree(d_ctl);
@@ -1003,17 +1121,23 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         // word) is not handed to the model's launch but issued after the stage by the caller
         IrHistory* ih = n_frames != 0 ? p->ir_history() : nullptr;
         if (ih) { p->pass_done = nullptr; p->pass_word = nullptr; }
+        if (ih) p->flush_ir_plan(ih, s);                               // the plan this pass is issued with, ahead of it
         HIP_TRY(p->launch(p->cur, a, s));
         if (ih) {
             // the IR stage (aidax_ir_mfma.hip): the block's dry samples into the history (also while no IR is live), then the convolution
-            // over the history, in place on d_out
+            // over the history, in place on d_out, of the streams the plan holds (one launch whatever the number of IRs)
             HIP_TRY(launch_ir_append(ih->ring, ih->ring_row, ih->mask, p->ir_pos, d_out, n_active, n_frames, s));
-            if (p->ir.d_frag) {
+            if (p->plan_n_items) {
                 IrArgs ia{};
-                ia.frag = p->ir.d_frag; ia.ring = ih->ring; ia.out = d_out; ia.part = ih->part;
-                ia.n_diag = p->ir.n_diag; ia.ring_row = ih->ring_row; ia.mask = ih->mask; ia.pos = p->ir_pos;
+                ia.items = reinterpret_cast<const IrItem*>(ih->d_plan);
+                ia.streams = reinterpret_cast<const uint32_t*>(ih->d_plan + p->plan_items_bytes());
+                // the identity plan over the prefix only: the grid of a one-IR pool (entries at or beyond n_active are skipped anyway)
+                ia.n_items = p->plan_identity ? std::min(p->plan_n_items, (n_active + kIrItemStreams - 1) / kIrItemStreams) : p->plan_n_items;
+                ia.n_listed = p->plan_identity ? n_active : p->plan_n_listed;
+                ia.ring = ih->ring; ia.out = d_out; ia.part = ih->part;
+                ia.ring_row = ih->ring_row; ia.mask = ih->mask; ia.pos = p->ir_pos;
                 ia.n_streams = n_active; ia.n_frames = n_frames;
-                ia.n_splits = ir_k_splits(n_active, n_frames, p->ir.n_diag, p->cus, ih->split_cap);
+                ia.n_splits = ir_k_splits(ia.n_items, n_frames, p->plan_max_diag, p->cus, ih->split_cap);
                 HIP_TRY(launch_ir_conv(ia, s));
             }
             p->ir_pos = (p->ir_pos + n_frames) & ih->mask;
@@ -1122,6 +1246,9 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
                 HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->ctl_ring[k]), sizeof(StreamCtl) * n_streams, hipHostMallocDefault));
                 HIP_TRY(hipEventCreateWithFlags(&p->ctl_ev[k], hipEventDisableTiming));
             }
+            p->ir_assign.assign(n_streams, AIDAX_IR_POOL);
+            p->plan_items.resize((n_streams + kIrItemStreams - 1) / kIrItemStreams + AIDAX_IR_SLOTS + 1);
+            p->plan_streams.resize(n_streams);
             p->controls.resize(n_streams);
             for (auto& c : p->controls) aidax_controls_default(&c);
             p->loading.assign(n_streams, 1);
@@ -1189,10 +1316,11 @@ AIDAX_API int aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int star
 
 // The cabinet IR, split between the threads like a model swap. Worker: the history on first use (allocated, zeroed, published), the IR's
 // fragments packed and uploaded on the worker stream. Audio thread: a swap of two host records behind an event — no allocation, no free, no wait.
-AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
 {
     if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
     *out = nullptr;
+    if (slot != AIDAX_IR_POOL && (slot < 0 || slot >= AIDAX_IR_SLOTS)) return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
     if (taps) {
         if (n_taps == 0 || n_taps > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR length must be 1 .. 8192 taps");
         for (uint32_t k = 0; k < n_taps; ++k)
@@ -1206,6 +1334,7 @@ AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n
         sg->device = p->device;
         sg->n_streams = p->n_streams;
         sg->is_ir = true;
+        sg->ir_slot = slot;
         HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
         if (!p->ir_hist_pub.load(std::memory_order_acquire)) {
             std::unique_ptr<IrHistory, void (*)(IrHistory*)> h(new IrHistory(), free_ir_history);
@@ -1219,6 +1348,12 @@ AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n
             const size_t ring_bytes = sizeof(float) * p->n_streams * static_cast<size_t>(h->ring_row);
             HIP_TRY(hipMalloc(&h->ring, ring_bytes));
             if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
+            const size_t plan_bytes = p->plan_items_bytes() + sizeof(uint32_t) * p->n_streams;
+            HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
+            for (int k = 0; k < kCtlRing; ++k) {
+                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_plan[k]), plan_bytes, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&h->plan_ev[k], hipEventDisableTiming));
+            }
             HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, p->wq));
             HIP_TRY(hipStreamSynchronize(p->wq));
             p->ir_hist_pub.store(h.release(), std::memory_order_release);
@@ -1236,6 +1371,20 @@ AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n
     });
 }
 
+AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+{
+    return prepare_ir_impl(p, AIDAX_IR_POOL, taps, n_taps, samplerate, out);
+}
+
+AIDAX_API int aidax_pool_prepare_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+{
+    if (slot >= static_cast<uint32_t>(AIDAX_IR_SLOTS)) {
+        if (out) *out = nullptr;
+        return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
+    }
+    return prepare_ir_impl(p, static_cast<int32_t>(slot), taps, n_taps, samplerate, out);
+}
+
 AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
 {
     if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
@@ -1247,7 +1396,8 @@ AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
         p->enter_stream(p->q);
         HIP_TRY(hipEventRecord(staged->fence, p->q));          // the retired fragments are free once the passes before this point have run
         staged->fenced = true;
-        std::swap(p->ir, staged->ir);
+        std::swap(staged->ir_slot == AIDAX_IR_POOL ? p->ir : p->bank[staged->ir_slot], staged->ir);
+        p->plan_dirty = true;                                  // every stream of that IR switches at this block boundary
         (void)p->ir_history();
         return AIDAX_OK;
     });
@@ -1263,10 +1413,60 @@ AIDAX_API int aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_tap
     return rc;
 }
 
+AIDAX_API int aidax_pool_set_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate)
+{
+    aidax_staged* sg = nullptr;
+    int rc = aidax_pool_prepare_ir_slot(p, slot, taps, n_taps, samplerate, &sg);
+    if (rc != AIDAX_OK) return rc;
+    rc = aidax_pool_commit_ir(p, sg);
+    aidax_staged_free(sg);
+    return rc;
+}
+
+// Audio thread: host assignments only (the plan is rebuilt by the next pass).
+AIDAX_API int aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    if (slot != AIDAX_IR_POOL && slot != AIDAX_IR_NONE && (slot < 0 || slot >= AIDAX_IR_SLOTS))
+        return fail(AIDAX_ERR_ARG, "IR slot must be the pool IR (-1), none (-2) or 0 .. 63");
+    if (stream == AIDAX_ALL_STREAMS) std::fill(p->ir_assign.begin(), p->ir_assign.end(), slot);
+    else p->ir_assign[stream] = slot;
+    p->plan_dirty = true;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
+{
+    if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    *slot = p->ir_assign[stream];
+    return AIDAX_OK;
+}
+
 AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode)
 {
     return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr);
 }
+
+#ifdef AIDAX_TEST_HOOKS
+// Test build only (not in include/aidax.h): the calling thread's counted calls since the last read, one "name count" line each, into
+// `buf` (NUL-terminated, cut at `cap` bytes); returns the number of entry points listed and starts the count afresh.
+AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap)
+{
+    size_t at = 0;
+    if (buf && cap) buf[0] = '\0';
+    for (int i = 0; i < hip_calls.used; ++i)
+        if (buf && at < cap) {
+            const int w = std::snprintf(buf + at, cap - at, "%s %llu\n", hip_calls.name[i], static_cast<unsigned long long>(hip_calls.n[i]));
+            if (w > 0) at += static_cast<size_t>(w);
+        }
+    const int n = hip_calls.used;
+    hip_calls.used = 0;
+    return n;
+}
+#endif
 
 }  // extern "C"
 

@@ -204,8 +204,9 @@ AIDAX_API void aidax_staged_free(aidax_staged* staged);
 AIDAX_API int  aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode);
 
 /* Cabinet impulse response (IR): an optional last stage of every stream's run(), after the master gain ramp (rt-neural-generic.cpp:654-655).
- * A pool holds at most one IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models); while
- * it does, every stream's output block is the causal convolution of the block the pool would have returned without it (`dry`) with h:
+ * A pool holds one pool IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models) and a bank
+ * of per-stream IRs (below); while it does, the output block of every stream that follows it (by default, all of them) is the causal
+ * convolution of the block the pool would have returned without it (`dry`) with h:
  *     y[s][t] = sum_{k < L} h[k] * dry[s][t - k]
  * whatever the stream's `enabled` control says (the cabinet sits after the plugin). No latency, any block length the pool takes; n_frames == 0
  * touches nothing. The IR is applied by the matrix cores (k_ir_conv) to fp32 accuracy, and an IR of a single tap that is a power of two
@@ -231,11 +232,37 @@ AIDAX_API int  aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t 
 AIDAX_API int  aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged);
 AIDAX_API int  aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate);
 
+/* Per-stream IRs: a bank of AIDAX_IR_SLOTS slots per pool beside the pool IR above, and per stream the IR its output goes through:
+ * AIDAX_IR_POOL (the default: the pool IR, whatever aidax_pool_set_ir / commit_ir put there), AIDAX_IR_NONE, or a bank slot 0 .. 63.
+ * A stream on AIDAX_IR_NONE, on an empty slot or on the pool IR while the pool has none returns its dry block. The history above is per
+ * stream and does not depend on the assignment: a stream moved to another IR at a block boundary hears the new IR applied to its whole
+ * past, and a commit into a slot switches all of that slot's streams at the same block boundary. aidax_pool_reset_stream clears the
+ * stream's history and keeps its assignment; a pool that never prepared an IR of either kind allocates and launches nothing for the stage,
+ * assignments or not. Each pass runs with the assignments and slots in force when it was issued (also the blocks in flight through
+ * aidax_pool_submit, and passes on a caller's stream). One k_ir_conv launch per pass, whatever the number of distinct IRs; with every stream
+ * on one IR (the pool IR or any one slot) the output is bit-identical to that IR as the pool IR.
+ * aidax_pool_prepare_ir_slot  WORKER thread: as aidax_pool_prepare_ir, into bank slot `slot` (taps == NULL: prepares emptying it); the
+ *                             first prepare of either kind allocates the history. AIDAX_ERR_ARG also for slot >= AIDAX_IR_SLOTS. Commit
+ *                             with aidax_pool_commit_ir: the staged object knows its slot, and holds the retired fragments afterwards.
+ * aidax_pool_set_ir_slot      prepare_ir_slot + commit + free in one blocking call.
+ * aidax_pool_assign_ir        AUDIO thread: stream (AIDAX_ALL_STREAMS: every stream) goes through `slot` from the next pass on. No
+ *                             allocation, no free, no wait. AIDAX_ERR_ARG for a stream or slot out of range.
+ * aidax_pool_stream_ir        the assignment of one stream (AIDAX_ERR_ARG for a stream out of range). */
+#define AIDAX_IR_SLOTS 64
+enum { AIDAX_IR_POOL = -1, AIDAX_IR_NONE = -2 };
+AIDAX_API int  aidax_pool_prepare_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out);
+AIDAX_API int  aidax_pool_set_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate);
+AIDAX_API int  aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot);
+AIDAX_API int  aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
- * prepare_ir, staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
+ * reset_stream, commit_model, commit_ir, assign_ir, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
+ * prepare_ir, prepare_ir_slot, staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync wait for the GPU (for the stream that carries the pass, never for the
- * device). */
+ * device) — with one exception in every pass: changed control records, and a changed IR plan (after an assign_ir or a commit_ir), go
+ * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
+ * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
+ * each of five passes in a row. */
 
 /* One stream becomes a fresh plugin instance with the pool's model: instantiate() state for its DSP
  * members (:283-321; gain smoothers pre = 1 / master = 0 cleared, biquad states 0) and a fresh DynamicModel

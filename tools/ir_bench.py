@@ -5,10 +5,14 @@
   one_stream    the LV2 instance's pool (one stream, the bundled LSTM-12 model): aidax_pool_process round trip (host in, host out),
                 median and p99 of --calls calls, without and with the IR, at 64 and 256 frames
 
+  --irs K,...   per-stream IRs (aidax_pool_set_ir_slot / aidax_pool_assign_ir): cfg2 with K distinct IRs in bank slots, assigned once
+                in contiguous runs of streams and once round-robin ("cfg2_bank": us per block and the stage's cost against the pool IR's),
+                and the one-stream round trip with the IR in a bank slot ("one_stream_bank")
+
 The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs). Under rocprofv3 --kernel-trace
 --stats the k_ir_conv / k_ir_reduce / k_ir_append rows are the stage's kernels alone.
 
-    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400]
+    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64]
 """
 import argparse
 import importlib
@@ -32,12 +36,22 @@ def cabinet_ir(L=8192, seed=8192):
     return (rng.standard_normal(L) * np.exp(-t / (L / 6.0)) * 0.05).astype(np.float32)
 
 
-def cfg2_us(ax, W, torch, path, with_ir, steps, warmup):
+def load_bank(pool, S, K, pattern):
+    """K distinct IRs in bank slots 0 .. K-1, stream s on slot s * K // S (runs) or s % K (round_robin)"""
+    for k in range(K):
+        pool.set_ir_slot(k, cabinet_ir(seed=8192 + k))
+    for s in range(S):
+        pool.assign_ir(s, s * K // S if pattern == "runs" else s % K)
+
+
+def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None):
     S, n = 1024, 256
     pool = ax.Pool(S, n)
     pool.set_model(ax.Model(path))
     if with_ir:
         pool.set_ir(cabinet_ir())
+    if bank:
+        load_bank(pool, S, *bank)
     x = torch.from_numpy(W.signal(S, n, seed=5)).cuda()
     y = torch.empty_like(x)
     s = torch.cuda.Stream()
@@ -56,11 +70,13 @@ def cfg2_us(ax, W, torch, path, with_ir, steps, warmup):
     return us
 
 
-def one_stream(ax, W, path, with_ir, frames, calls):
+def one_stream(ax, W, path, with_ir, frames, calls, bank=False):
     pool = ax.Pool(1, frames)
     pool.set_model(ax.Model(path))
     if with_ir:
         pool.set_ir(cabinet_ir())
+    if bank:
+        load_bank(pool, 1, 1, "runs")
     x = np.ascontiguousarray(W.signal(1, frames, seed=6))
     for _ in range(50):
         pool.process(x)
@@ -78,6 +94,7 @@ def main():
     ap.add_argument("--steps", type=int, default=400)
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--calls", type=int, default=400)
+    ap.add_argument("--irs", default="", help="comma-separated K: cfg2 with K distinct IRs in bank slots (e.g. 1,4,16,64)")
     a = ap.parse_args()
     import torch
     ax = importlib.import_module("aidadsp-lv2_amd")
@@ -94,6 +111,14 @@ def main():
     for frames in (64, 256):
         out["one_stream"][str(frames)] = {"no_ir": one_stream(ax, W, lv2, False, frames, a.calls),
                                           "ir": one_stream(ax, W, lv2, True, frames, a.calls)}
+    if a.irs:
+        out["cfg2_bank"] = {}
+        for K in (int(k) for k in a.irs.split(",")):
+            for pattern in ("runs", "round_robin"):
+                us = cfg2_us(ax, W, torch, cfg2, False, a.steps, a.warmup, bank=(K, pattern))
+                out["cfg2_bank"][f"K{K}_{pattern}"] = {"us_per_block": round(us, 2), "ir_stage_us": round(us - dry, 2),
+                                                        "over_pool_ir_stage": round((us - dry) / (wet - dry), 3)}
+        out["one_stream_bank"] = {str(f): one_stream(ax, W, lv2, False, f, a.calls, bank=True) for f in (64, 256)}
     print(json.dumps(out))
 
 
