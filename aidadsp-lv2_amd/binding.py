@@ -165,6 +165,9 @@ def lib() -> C.CDLL:
     L.aidax_pool_set_ir_slot.argtypes = [vp, u32, _fp, u32, C.c_double]
     L.aidax_pool_assign_ir.argtypes = [vp, i32, i32]
     L.aidax_pool_stream_ir.argtypes = [vp, u32, C.POINTER(i32)]
+    L.aidax_pool_set_ir_fade.argtypes = [vp, u32]
+    L.aidax_pool_ir_fade.argtypes = [vp]
+    L.aidax_pool_ir_fade.restype = u32
     _lib = L
     return L
 
@@ -385,6 +388,14 @@ class Pool:
         v = C.c_int32(0)
         _check(lib().aidax_pool_stream_ir(self.h, stream, C.byref(v)))
         return v.value
+
+    def set_ir_fade(self, frames: int):
+        """aidax_pool_set_ir_fade: crossfade old and new IR over the first min(frames, n_frames) frames of the pass behind an IR change
+        (0: off, the default)"""
+        _check(lib().aidax_pool_set_ir_fade(self.h, frames))
+
+    def ir_fade(self) -> int:
+        return int(lib().aidax_pool_ir_fade(self.h))
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

@@ -229,6 +229,25 @@ __global__ __launch_bounds__(256) void k_ir_reduce(const float* __restrict__ par
     out[e] = v;
 }
 
+// The crossfade of an IR change, in place on the first lf frames of the fading streams' output rows (which hold the new side: the
+// main section's convolution, or the dry block of a stream that goes to no IR). The old side is the fade-out section's row of the side
+// buffer, or, for a stream that came from no IR, its dry samples out of the history ring. Thread i: entry i / lf of `mix`, frame i % lf.
+// Both weights are quotients of small integers, rounded once each; at the last frame they are 1 and 0, and the new side comes out as it is.
+__global__ __launch_bounds__(256) void k_ir_fade(IrFadeArgs a)
+{
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_mix * a.lf) return;
+    const uint32_t j = i / a.lf, t = i - j * a.lf;
+    const uint32_t e = a.mix[j];
+    const uint32_t s = e & ~kIrFadeDry;
+    if (s >= a.n_streams) return;
+    const size_t at = static_cast<size_t>(s) * a.n_frames + t;
+    const float was = (e & kIrFadeDry) ? a.ring[static_cast<size_t>(s) * a.ring_row + ((a.pos + t) & a.mask)] : a.side[at];
+    const float lf = static_cast<float>(a.lf);
+    const float w = static_cast<float>(t + 1u) / lf, u = static_cast<float>(a.lf - 1u - t) / lf;
+    a.out[at] = __builtin_fmaf(w, a.out[at], u * was);
+}
+
 }  // namespace
 
 uint32_t ir_diagonals(uint32_t n_taps) { return (n_taps + 30u) / 16u + 1u; }
@@ -263,6 +282,14 @@ hipError_t launch_ir_conv(const IrArgs& a, hipStream_t q)
     if (e != hipSuccess || a.n_splits <= 1) return e;
     const uint32_t count = a.n_listed * a.n_frames;
     hipLaunchKernelGGL(k_ir_reduce, dim3((count + 255u) / 256u), dim3(256), 0, q, a.part, a.out, a.streams, a.n_listed, a.n_streams, a.n_frames, a.n_splits);
+    return hipGetLastError();
+}
+
+hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q)
+{
+    if (a.n_mix == 0 || a.lf == 0 || a.n_frames == 0) return hipSuccess;
+    const uint32_t count = a.n_mix * a.lf;
+    hipLaunchKernelGGL(k_ir_fade, dim3((count + 255u) / 256u), dim3(256), 0, q, a);
     return hipGetLastError();
 }
 

@@ -120,6 +120,19 @@ hipError_t launch_ir_append(float* ring, uint32_t ring_row, uint32_t mask, uint3
                             hipStream_t q);
 // k_ir_conv (+ k_ir_reduce when n_splits > 1): the rows of the plan's streams = each one's IR over its ring; other rows are not touched
 hipError_t launch_ir_conv(const IrArgs& a, hipStream_t q);
+// The crossfade of an IR change (k_ir_fade), behind launch_ir_conv of the pass and of its fade-out section: for every entry of `mix`
+// (a stream index; kIrFadeDry set: the stream's old side is its dry block, read from the ring at pos + t, else its row of `side`,
+// [n_streams][n_frames]) the first `lf` frames of the stream's row of `out` become u[t] old + w[t] new, w[t] = (t + 1) / lf,
+// u[t] = (lf - 1 - t) / lf (frame lf - 1 is the new side exactly). 1 <= lf <= n_frames; an entry at or beyond n_streams is skipped.
+constexpr uint32_t kIrFadeDry = 0x80000000u;
+struct IrFadeArgs {
+    const uint32_t* mix;
+    const float* side;
+    const float* ring;
+    float* out;
+    uint32_t n_mix, ring_row, mask, pos, n_streams, n_frames, lf;
+};
+hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q);
 
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 

@@ -60,6 +60,7 @@ void note_hip_call(const char* name)
 #define hipStreamWriteValue32(...) AIDAX_COUNTED(hipStreamWriteValue32, __VA_ARGS__)
 #define launch_ir_append(...) (aidax::note_hip_call("launch_ir_append"), aidax::launch_ir_append(__VA_ARGS__))
 #define launch_ir_conv(...) (aidax::note_hip_call("launch_ir_conv"), aidax::launch_ir_conv(__VA_ARGS__))
+#define launch_ir_fade(...) (aidax::note_hip_call("launch_ir_fade"), aidax::launch_ir_fade(__VA_ARGS__))
 #endif
 
 using namespace aidax;
@@ -355,6 +356,7 @@ struct ModelSlot {
 struct IrSlot {
     uint32_t* d_frag = nullptr;      // nullptr: no IR
     uint32_t n_taps = 0, n_diag = 0;
+    uint64_t gen = 0;                // which committed content this is (a number per commit, given by the commit; 0: none): the IR fade's identity of an IR
 };
 constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
 
@@ -371,6 +373,7 @@ struct IrHistory {
     hipEvent_t plan_ev[kCtlRing] = {};
     bool plan_used[kCtlRing] = {};
     int plan_next = 0;                   // (audio side)
+    float* side = nullptr;               // the IR fade's side buffer, [n_streams][max_frames]: what the fade-out section of a fade pass convolves into
 };
 void free_ir_history(IrHistory* h)
 {
@@ -378,6 +381,7 @@ void free_ir_history(IrHistory* h)
     if (h->ring) (void)hipFree(h->ring);
     if (h->part) (void)hipFree(h->part);
     if (h->d_plan) (void)hipFree(h->d_plan);
+    if (h->side) (void)hipFree(h->side);
     for (int k = 0; k < kCtlRing; ++k) {
         if (h->h_plan[k]) (void)hipHostFree(h->h_plan[k]);
         if (h->plan_ev[k]) (void)hipEventDestroy(h->plan_ev[k]);
@@ -482,6 +486,68 @@ struct aidax_pool {
     uint32_t plan_n_items = 0, plan_n_listed = 0, plan_max_diag = 0;
     bool plan_identity = false, plan_dirty = true;
     size_t plan_items_bytes() const { return plan_items.size() * sizeof(IrItem); }
+    // The IR fade (aidax_pool_set_ir_fade; 0: off). Every commit gives its content a generation number, and a stream records the
+    // (key, generation) of the IR it went through in the last pass issued (key as ir_key; -1 / 0: none). A rebuild of the plan that finds
+    // another one in force for a stream adds the stream to the plan's second section, the fade-out items: the old IRs (still in the bank,
+    // or parked, see aidax_pool_commit_ir) with the streams fading from them, grouped like the main section, and to the mix list
+    // (k_ir_fade: stream index, kIrFadeDry set where the old side is the dry block). That section serves the one pass it was built for.
+    // Device and snapshot layout behind the main section: fade items at fade_items_off(), their stream lists, the mix list.
+    uint32_t ir_fade = 0;
+    IrSlot ir_parked[AIDAX_IR_SLOTS + 1];        // per key: the content retired last, kept for the streams that still fade from it
+    uint64_t ir_gen_next = 1;
+    uint64_t ir_pass_seq = 0;                    // passes issued through the IR stage
+    bool any_pass = false;                       // the pool has issued a pass of n_frames > 0 (its first one has nothing to fade from)
+    uint64_t ir_commit_seq[AIDAX_IR_SLOTS + 1] = {};   // ... when the key's content was committed: smaller than ir_pass_seq = it has been played
+    std::vector<int8_t> played_key;              // [n_streams]
+    std::vector<uint64_t> played_gen;            // [n_streams]
+    std::vector<IrItem> fade_items;              // [ceil(n_streams / 64) + 2 * 65]
+    std::vector<uint32_t> fade_streams, fade_mix;    // [n_streams] each
+    std::vector<int16_t> fade_src;               // [n_streams]: scratch of build_ir_fade
+    uint32_t fade_n_items = 0, fade_n_listed = 0, fade_n_mix = 0, fade_max_diag = 0;
+    size_t fade_items_off() const { return (plan_items_bytes() + sizeof(uint32_t) * n_streams + 7u) & ~size_t(7); }
+    size_t fade_streams_off() const { return fade_items_off() + fade_items.size() * sizeof(IrItem); }
+    size_t fade_mix_off() const { return fade_streams_off() + sizeof(uint32_t) * n_streams; }
+    size_t plan_bytes() const { return fade_mix_off() + sizeof(uint32_t) * n_streams; }
+    const IrSlot& ir_slot_of(int k) const { return k == 0 ? ir : bank[k - 1]; }
+    // the fade-out section for the pass about to be issued (behind build_ir_plan, same rebuild), and every stream's record brought up to
+    // that pass. `fade`: a fade length is set (and this is not the pool's first pass); without, the streams switch as they always did.
+    // A stream whose old IR is held nowhere any more (neither in the bank nor parked: it was retired under a fade length of 0) switches
+    // without a fade too.
+    void build_ir_fade(bool fade)
+    {
+        constexpr int kSources = 2 * (AIDAX_IR_SLOTS + 1);              // 0 .. 64: the bank's content, 65 .. 129: the parked one
+        uint32_t count[kSources] = {}, at[kSources];
+        fade_n_items = fade_n_listed = fade_n_mix = fade_max_diag = 0;
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            const int nk = ir_key(s);
+            const uint64_t ng = nk >= 0 ? ir_slot_of(nk).gen : 0;
+            const int ok = played_key[s];
+            const uint64_t og = played_gen[s];
+            fade_src[s] = -2;                                          // no fade
+            played_key[s] = static_cast<int8_t>(nk);
+            played_gen[s] = ng;
+            if (!fade || (nk == ok && ng == og)) continue;
+            if (ok < 0) fade_src[s] = -1;                              // from the dry block
+            else if (ir_slot_of(ok).d_frag && ir_slot_of(ok).gen == og) fade_src[s] = static_cast<int16_t>(ok);
+            else if (ir_parked[ok].d_frag && ir_parked[ok].gen == og) fade_src[s] = static_cast<int16_t>(AIDAX_IR_SLOTS + 1 + ok);
+            if (fade_src[s] >= 0) ++count[fade_src[s]];
+            if (fade_src[s] >= -1) fade_mix[fade_n_mix++] = s | (fade_src[s] < 0 ? kIrFadeDry : 0u);
+        }
+        if (fade_n_mix == 0) return;
+        uint32_t first = 0;
+        for (int k = 0; k < kSources; ++k) { at[k] = first; first += count[k]; }
+        fade_n_listed = first;
+        for (uint32_t s = 0; s < n_streams; ++s)
+            if (fade_src[s] >= 0) fade_streams[at[fade_src[s]]++] = s;
+        first = 0;
+        for (int k = 0; k < kSources; ++k) {
+            const IrSlot& sl = k <= AIDAX_IR_SLOTS ? ir_slot_of(k) : ir_parked[k - AIDAX_IR_SLOTS - 1];
+            for (uint32_t c = 0; c < count[k]; c += kIrItemStreams)
+                fade_items[fade_n_items++] = IrItem{ sl.d_frag, sl.n_diag, std::min(kIrItemStreams, count[k] - c), first + c, 0u };
+            if (count[k]) fade_max_diag = std::max(fade_max_diag, sl.n_diag);
+            first += count[k];
+        }
+    }
     int ir_key(uint32_t s) const                 // 0: the pool IR, 1 + j: bank slot j, -1: none (also an empty slot)
     {
         const int32_t a = ir_assign[s];
@@ -520,11 +586,21 @@ struct aidax_pool {
     {
         if (!plan_dirty) return;
         build_ir_plan();
+        build_ir_fade(any_pass && ir_fade != 0);
         const int k = h->plan_next;
         if (h->plan_used[k] && hipEventQuery(h->plan_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(h->plan_ev[k]));   // four rebuilds behind
         std::memcpy(h->h_plan[k], plan_items.data(), plan_n_items * sizeof(IrItem));
         std::memcpy(h->h_plan[k] + plan_items_bytes(), plan_streams.data(), plan_n_listed * sizeof(uint32_t));
-        HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], plan_items_bytes() + plan_n_listed * sizeof(uint32_t), hipMemcpyHostToDevice, s));
+        size_t bytes = plan_items_bytes() + plan_n_listed * sizeof(uint32_t);
+        if (fade_n_mix) {
+            // the fade-out section rides in the same upload: one copy up to the end of the mix list. It also carries the snapshot's gaps
+            // (stream-list entries past plan_n_listed, items past fade_n_items), which no kernel reads: the counts travel as arguments
+            std::memcpy(h->h_plan[k] + fade_items_off(), fade_items.data(), fade_n_items * sizeof(IrItem));
+            std::memcpy(h->h_plan[k] + fade_streams_off(), fade_streams.data(), fade_n_listed * sizeof(uint32_t));
+            std::memcpy(h->h_plan[k] + fade_mix_off(), fade_mix.data(), fade_n_mix * sizeof(uint32_t));
+            bytes = fade_mix_off() + fade_n_mix * sizeof(uint32_t);
+        }
+        HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], bytes, hipMemcpyHostToDevice, s));
         HIP_TRY(hipEventRecord(h->plan_ev[k], s));
         h->plan_used[k] = true;
         h->plan_next = (k + 1) % kCtlRing;
@@ -839,6 +915,10 @@ struct aidax_pool {
             if (b.d_frag) (void)hipFree(b.d_frag);
             b = IrSlot{};
         }
+        for (IrSlot& b : ir_parked) {
+            if (b.d_frag) (void)hipFree(b.d_frag);
+            b = IrSlot{};
+        }
         free_ir_history(ir_hist_pub.exchange(nullptr));
         ir_hist = nullptr;
         if (d_ctl) (void)hipFree(d_ctl);
@@ -1121,6 +1201,12 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         // word) is not handed to the model's launch but issued after the stage by the caller
         IrHistory* ih = n_frames != 0 ? p->ir_history() : nullptr;
         if (ih) { p->pass_done = nullptr; p->pass_word = nullptr; }
+        // a fade-out section serves this pass alone: spent when the pass has been issued, and dropped when issuing it fails (the streams
+        // then switch; a later pass, with another n_frames and ring position, must not run it)
+        struct FadeSpent {
+            aidax_pool* p;
+            ~FadeSpent() { if (p) p->fade_n_items = p->fade_n_listed = p->fade_n_mix = 0; }
+        } fade_spent{ ih ? p : nullptr };
         if (ih) p->flush_ir_plan(ih, s);                               // the plan this pass is issued with, ahead of it
         HIP_TRY(p->launch(p->cur, a, s));
         if (ih) {
@@ -1140,8 +1226,33 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
                 ia.n_splits = ir_k_splits(ia.n_items, n_frames, p->plan_max_diag, p->cus, ih->split_cap);
                 HIP_TRY(launch_ir_conv(ia, s));
             }
+            if (p->fade_n_mix) {
+                // an IR change since the last pass: the old IRs over the same history into the side buffer (the fade-out section: the
+                // same kernel, K split and fixed-order reduce, `part` reused behind the main section's reduce), then the crossfade of the
+                // first min(F, n_frames) frames in place on d_out. This pass only (fade_spent).
+                if (p->fade_n_items) {
+                    IrArgs fa{};
+                    fa.items = reinterpret_cast<const IrItem*>(ih->d_plan + p->fade_items_off());
+                    fa.streams = reinterpret_cast<const uint32_t*>(ih->d_plan + p->fade_streams_off());
+                    fa.n_items = p->fade_n_items; fa.n_listed = p->fade_n_listed;
+                    fa.ring = ih->ring; fa.out = ih->side; fa.part = ih->part;
+                    fa.ring_row = ih->ring_row; fa.mask = ih->mask; fa.pos = p->ir_pos;
+                    fa.n_streams = n_active; fa.n_frames = n_frames;
+                    fa.n_splits = ir_k_splits(fa.n_items, n_frames, p->fade_max_diag, p->cus, ih->split_cap);
+                    HIP_TRY(launch_ir_conv(fa, s));
+                }
+                IrFadeArgs fm{};
+                fm.mix = reinterpret_cast<const uint32_t*>(ih->d_plan + p->fade_mix_off());
+                fm.side = ih->side; fm.ring = ih->ring; fm.out = d_out;
+                fm.n_mix = p->fade_n_mix; fm.ring_row = ih->ring_row; fm.mask = ih->mask; fm.pos = p->ir_pos;
+                fm.n_streams = n_active; fm.n_frames = n_frames;
+                fm.lf = std::min(p->ir_fade, n_frames);
+                HIP_TRY(launch_ir_fade(fm, s));
+            }
+            ++p->ir_pass_seq;
             p->ir_pos = (p->ir_pos + n_frames) & ih->mask;
         }
+        if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
 }
@@ -1249,6 +1360,12 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
             p->ir_assign.assign(n_streams, AIDAX_IR_POOL);
             p->plan_items.resize((n_streams + kIrItemStreams - 1) / kIrItemStreams + AIDAX_IR_SLOTS + 1);
             p->plan_streams.resize(n_streams);
+            p->played_key.assign(n_streams, -1);
+            p->played_gen.assign(n_streams, 0);
+            p->fade_items.resize((n_streams + kIrItemStreams - 1) / kIrItemStreams + 2 * (AIDAX_IR_SLOTS + 1));
+            p->fade_streams.resize(n_streams);
+            p->fade_mix.resize(n_streams);
+            p->fade_src.resize(n_streams);
             p->controls.resize(n_streams);
             for (auto& c : p->controls) aidax_controls_default(&c);
             p->loading.assign(n_streams, 1);
@@ -1348,7 +1465,8 @@ static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint3
             const size_t ring_bytes = sizeof(float) * p->n_streams * static_cast<size_t>(h->ring_row);
             HIP_TRY(hipMalloc(&h->ring, ring_bytes));
             if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
-            const size_t plan_bytes = p->plan_items_bytes() + sizeof(uint32_t) * p->n_streams;
+            HIP_TRY(hipMalloc(&h->side, sizeof(float) * block));
+            const size_t plan_bytes = p->plan_bytes();           // both sections, whether a fade length is set or not
             HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
             for (int k = 0; k < kCtlRing; ++k) {
                 HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_plan[k]), plan_bytes, hipHostMallocDefault));
@@ -1396,7 +1514,15 @@ AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
         p->enter_stream(p->q);
         HIP_TRY(hipEventRecord(staged->fence, p->q));          // the retired fragments are free once the passes before this point have run
         staged->fenced = true;
-        std::swap(staged->ir_slot == AIDAX_IR_POOL ? p->ir : p->bank[staged->ir_slot], staged->ir);
+        const int key = staged->ir_slot == AIDAX_IR_POOL ? 0 : 1 + staged->ir_slot;
+        staged->ir.gen = staged->ir.d_frag ? p->ir_gen_next++ : 0;
+        std::swap(key == 0 ? p->ir : p->bank[key - 1], staged->ir);
+        // With a fade length set, content that has been played (a pass was issued since its commit) is parked for the streams that will
+        // fade from it in the next pass, and `staged` gets what was parked before: an IR retired one commit earlier, whose last possible
+        // use, a fade pass, precedes the fence above. Content that was never played has no stream to fade from it: it goes to `staged`
+        // as ever, and what is parked (which streams may still have played) stays.
+        if (p->ir_fade != 0 && p->ir_commit_seq[key] != p->ir_pass_seq) std::swap(p->ir_parked[key], staged->ir);
+        p->ir_commit_seq[key] = p->ir_pass_seq;
         p->plan_dirty = true;                                  // every stream of that IR switches at this block boundary
         (void)p->ir_history();
         return AIDAX_OK;
@@ -1436,6 +1562,17 @@ AIDAX_API int aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot)
     p->plan_dirty = true;
     return AIDAX_OK;
 }
+
+// Audio thread: a host record (the plan is rebuilt by the next pass that finds a change).
+AIDAX_API int aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames)
+{
+    if (frames > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR fade length must be 0 .. 8192 frames");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    p->ir_fade = frames;
+    return AIDAX_OK;
+}
+
+AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir_fade : 0; }
 
 AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
 {

@@ -255,8 +255,35 @@ AIDAX_API int  aidax_pool_set_ir_slot(aidax_pool* p, uint32_t slot, const float*
 AIDAX_API int  aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot);
 AIDAX_API int  aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot);
 
+/* IR fade: a change of IR without a click. A pool has an IR fade length F in frames (0, the default: off, and everything above holds
+ * bit for bit). With F > 0, call the IR a stream's output actually goes through its effective IR: the pool IR, a bank slot's content, or
+ * nothing (AIDAX_IR_NONE, an empty slot, the pool IR while the pool has none). When a stream's effective IR in the pass being issued
+ * differs from the one in the last pass issued (after aidax_pool_assign_ir, a commit into its slot, a commit or removal of the pool IR,
+ * or any combination: the changes between two passes collapse into one, and A -> B -> A is no change), that one pass returns
+ *     y[t] = (1 - w[t]) (h_old * x)[t] + w[t] (h_new * x)[t],   w[t] = min(1, (t + 1) / Lf),   Lf = min(F, n_frames)
+ * for that stream, x being its dry history including this block and "nothing" the unit impulse (that side is the dry block). The fade
+ * ends inside the pass: its frames t >= Lf, and every later pass, are bit-identical to a pool that had the new IR all along, and so is
+ * every stream whose effective IR did not change. A pass of n_frames == 0 leaves a pending fade pending. Each pass runs with the fade,
+ * plan and assignments in force when it was issued (blocks in flight through aidax_pool_submit and passes on a caller's stream too).
+ * A fade pass costs a second k_ir_conv launch (the old IRs, over the fading streams only) and k_ir_fade; a pass without a pending fade
+ * issues exactly the launches of a pool without a fade length. Deterministic like the stage itself.
+ * Lifetime: with F > 0 a commit does not hand the fragments it retires to `staged` if they have been played; it parks them in the pool,
+ * one parked IR per slot and one for the pool IR, for the fade pass to read, and `staged` receives what was parked there before (an IR
+ * retired one commit earlier, whose last use precedes the commit's fence). Content that is retired before any pass was issued with it
+ * goes to `staged` at once and the parked IR stays. So aidax_staged_free may run at any time after the commit, as ever, also before
+ * the fade pass is issued; parked fragments are freed by a later retirement's aidax_staged_free or by aidax_pool_destroy. With this
+ * scheme a slot committed twice (or more) between two passes still fades, from the content last played to the content last committed.
+ * What does not fade: a pool's very first pass (there is no earlier pass to differ from), and a stream whose old IR was retired while
+ * F was 0: it switches at the block boundary as with F == 0. The crossfade's side buffer (n_streams x max_frames floats) is allocated
+ * with the history, by the first prepare of either kind, so the fade length may be set and changed at any time between passes.
+ * Prefix passes of the hub fade the streams of the prefix; the others switch.
+ * aidax_pool_set_ir_fade   AUDIO thread, between passes: host records only. AIDAX_ERR_ARG for a null pool or frames > 8192.
+ * aidax_pool_ir_fade       the fade length (0 for a null pool). */
+AIDAX_API int      aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames);
+AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
+ * reset_stream, commit_model, commit_ir, assign_ir, set_ir_fade, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_ir, prepare_ir_slot, staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync wait for the GPU (for the stream that carries the pass, never for the
  * device) — with one exception in every pass: changed control records, and a changed IR plan (after an assign_ir or a commit_ir), go

@@ -9,10 +9,15 @@
                 in contiguous runs of streams and once round-robin ("cfg2_bank": us per block and the stage's cost against the pool IR's),
                 and the one-stream round trip with the IR in a bank slot ("one_stream_bank")
 
+  --fade F      the IR fade (aidax_pool_set_ir_fade): cfg2's steady state with the fade length set against without ("cfg2_fade_steady":
+                the launches are the same), the cost of ONE fade pass against a plain pass timed the same way (events around a single
+                pass) with all 1024 streams fading (a pool-IR commit), with 16 of 1024 fading (assign_ir), and the round trip of a
+                one-stream pool whose every pass is a fade pass, at 64 and 256 frames
+
 The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs). Under rocprofv3 --kernel-trace
 --stats the k_ir_conv / k_ir_reduce / k_ir_append rows are the stage's kernels alone.
 
-    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64]
+    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64] [--fade 256]
 """
 import argparse
 import importlib
@@ -44,10 +49,12 @@ def load_bank(pool, S, K, pattern):
         pool.assign_ir(s, s * K // S if pattern == "runs" else s % K)
 
 
-def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None):
+def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None, fade=0):
     S, n = 1024, 256
     pool = ax.Pool(S, n)
     pool.set_model(ax.Model(path))
+    if fade:
+        pool.set_ir_fade(fade)
     if with_ir:
         pool.set_ir(cabinet_ir())
     if bank:
@@ -68,6 +75,68 @@ def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None):
     us = e0.elapsed_time(e1) * 1000.0 / steps
     pool.close()
     return us
+
+
+def cfg2_fade_pass(ax, W, torch, path, fade, reps, warmup, which):
+    """us of single passes, each between two events: (plain passes, fade passes). which: "commit" (a pool-IR commit before every fade
+    pass: all 1024 streams fade, 8192 taps on both sides) or "assign" (16 streams moved between the pool IR and a slot)"""
+    S, n = 1024, 256
+    pool = ax.Pool(S, n)
+    pool.set_model(ax.Model(path))
+    pool.set_ir_fade(fade)
+    pool.set_ir(cabinet_ir())
+    pool.set_ir_slot(0, cabinet_ir(seed=1))
+    staged = [pool.prepare_ir(cabinet_ir(seed=100 + i)) for i in range(reps)] if which == "commit" else []
+    x = torch.from_numpy(W.signal(S, n, seed=5)).cuda()
+    y = torch.empty_like(x)
+    s = torch.cuda.Stream()
+    torch.cuda.synchronize()
+    times = {"plain": [], "fade": []}
+    with torch.cuda.stream(s):
+        for _ in range(warmup):
+            pool.process_device(x.data_ptr(), y.data_ptr(), n, s.cuda_stream)
+        s.synchronize()
+        for i in range(reps):
+            for kind in ("plain", "fade"):
+                if kind == "fade" and which == "commit":
+                    pool.commit_ir(staged[i])
+                elif kind == "fade":
+                    for k in range(16):
+                        pool.assign_ir(64 * k, 0 if i % 2 == 0 else ax.IR_POOL)
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record(s)
+                pool.process_device(x.data_ptr(), y.data_ptr(), n, s.cuda_stream)
+                e1.record(s)
+                s.synchronize()
+                times[kind].append(e0.elapsed_time(e1) * 1000.0)
+    for sg in staged:
+        pool.staged_free(sg)
+    pool.close()
+    return {k: round(float(np.median(v)), 2) for k, v in times.items()}
+
+
+def one_stream_fade(ax, W, path, frames, calls, fade):
+    """aidax_pool_process round trip of a one-stream pool: plain passes, then passes that each follow an assign_ir (every one a fade pass)"""
+    pool = ax.Pool(1, frames)
+    pool.set_model(ax.Model(path))
+    pool.set_ir_fade(fade)
+    pool.set_ir(cabinet_ir())
+    pool.set_ir_slot(0, cabinet_ir(seed=1))
+    x = np.ascontiguousarray(W.signal(1, frames, seed=6))
+    for _ in range(50):
+        pool.process(x)
+    out = {}
+    for kind in ("plain", "fade"):
+        t = np.empty(calls)
+        for i in range(calls):
+            if kind == "fade":
+                pool.assign_ir(0, 0 if i % 2 == 0 else ax.IR_POOL)
+            t0 = time.perf_counter()
+            pool.process(x)
+            t[i] = time.perf_counter() - t0
+        out[kind] = {"p50_us": round(float(np.percentile(t, 50)) * 1e6, 2), "p99_us": round(float(np.percentile(t, 99)) * 1e6, 2)}
+    pool.close()
+    return out
 
 
 def one_stream(ax, W, path, with_ir, frames, calls, bank=False):
@@ -95,6 +164,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=50)
     ap.add_argument("--calls", type=int, default=400)
     ap.add_argument("--irs", default="", help="comma-separated K: cfg2 with K distinct IRs in bank slots (e.g. 1,4,16,64)")
+    ap.add_argument("--fade", type=int, default=0, help="fade length in frames: the IR fade's steady state and the cost of one fade pass")
     a = ap.parse_args()
     import torch
     ax = importlib.import_module("aidadsp-lv2_amd")
@@ -119,6 +189,17 @@ def main():
                 out["cfg2_bank"][f"K{K}_{pattern}"] = {"us_per_block": round(us, 2), "ir_stage_us": round(us - dry, 2),
                                                         "over_pool_ir_stage": round((us - dry) / (wet - dry), 3)}
         out["one_stream_bank"] = {str(f): one_stream(ax, W, lv2, False, f, a.calls, bank=True) for f in (64, 256)}
+    if a.fade:
+        steady = cfg2_us(ax, W, torch, cfg2, True, a.steps, a.warmup, fade=a.fade)
+        again = cfg2_us(ax, W, torch, cfg2, True, a.steps, a.warmup)
+        out["cfg2_fade_steady"] = {"fade_frames": a.fade, "us_per_block_fade_set": round(steady, 2), "us_per_block_fade_0": round(wet, 2),
+                                   "us_per_block_fade_0_again": round(again, 2), "ir_stage_us_fade_set": round(steady - dry, 2)}
+        out["cfg2_fade_pass"] = {}
+        for which, name in (("commit", "all_1024_fading"), ("assign", "16_of_1024_fading")):
+            t = cfg2_fade_pass(ax, W, torch, cfg2, a.fade, 40, a.warmup, which)
+            out["cfg2_fade_pass"][name] = {"plain_pass_us": t["plain"], "fade_pass_us": t["fade"], "extra_us": round(t["fade"] - t["plain"], 2),
+                                           "extra_over_ir_stage": round((t["fade"] - t["plain"]) / (wet - dry), 3)}
+        out["one_stream_fade"] = {str(f): one_stream_fade(ax, W, lv2, f, a.calls, min(a.fade, f)) for f in (64, 256)}
     print(json.dumps(out))
 
 
