@@ -84,6 +84,14 @@ build/asan/asan_harness: $(ASAN_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude $(ASAN_SRCS) -o $@
 asan: build/asan/asan_harness
 
+# ... and the IR stage's host side (aidax_ir_resample, the fragment packer) the same way: tests/asan_ir_harness.cpp, tests/test_asan_ir.py
+ASAN_IR_SRCS := tests/asan_ir_harness.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
+build/asan/asan_ir_harness: $(ASAN_IR_SRCS) $(HDRS) $(SRC)/json_min.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_IR_SRCS) -o $@
+asan_ir: build/asan/asan_ir_harness
+
 oracle:
 	$(MAKE) -s -C oracle all
 	$(MAKE) -s -C oracle _ref
@@ -92,4 +100,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan
+.PHONY: all hooks oracle bundle clean asan asan_ir

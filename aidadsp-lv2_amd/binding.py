@@ -168,6 +168,10 @@ def lib() -> C.CDLL:
     L.aidax_pool_set_ir_fade.argtypes = [vp, u32]
     L.aidax_pool_ir_fade.argtypes = [vp]
     L.aidax_pool_ir_fade.restype = u32
+    L.aidax_ir_resample.argtypes = [_fp, u32, C.c_double, C.c_double, u32, _fp, u32, C.POINTER(u32)]
+    L.aidax_pool_set_ir_capacity.argtypes = [vp, u32]
+    L.aidax_pool_ir_capacity.argtypes = [vp]
+    L.aidax_pool_ir_capacity.restype = u32
     _lib = L
     return L
 
@@ -212,6 +216,25 @@ def load_ir_wav(path: str):
     taps = np.empty(n.value, np.float32)
     _check(lib().aidax_ir_load_wav(os.fsencode(path), taps.ctypes.data_as(_fp), n.value, C.byref(n), C.byref(sr)))
     return taps, sr.value
+
+
+def resample_ir(taps, rate_in: float, rate_out: float, lead: int = 0, cap: Optional[int] = None):
+    """aidax_ir_resample: (taps at rate_out as float32, n_full). `lead` frames of the pre-ringing are kept (the caller's latency);
+    cap cuts the result (no tail fade), None keeps all n_full frames."""
+    t = _f32(taps).reshape(-1)
+    n = C.c_uint32(0)
+    _check(lib().aidax_ir_resample(t.ctypes.data_as(_fp), t.size, rate_in, rate_out, lead, None, 0, C.byref(n)))
+    out = np.empty(n.value if cap is None else min(int(cap), n.value), np.float32)
+    if out.size:
+        _check(lib().aidax_ir_resample(t.ctypes.data_as(_fp), t.size, rate_in, rate_out, lead, out.ctypes.data_as(_fp), out.size, C.byref(n)))
+    return out, n.value
+
+
+def load_ir_wav_for(pool: "Pool", path: str, lead: int = 0) -> np.ndarray:
+    """A WAV file's IR ready for `pool`: read (aidax_ir_load_wav), converted to the pool's host rate (aidax_ir_resample; a file at that
+    rate is taken as it is, behind `lead` zeros) and cut to the pool's IR capacity."""
+    taps, sr = load_ir_wav(path)
+    return resample_ir(taps, sr, pool.samplerate, lead, pool.ir_capacity())[0]
 
 
 def device_count() -> int:
@@ -396,6 +419,13 @@ class Pool:
 
     def ir_fade(self) -> int:
         return int(lib().aidax_pool_ir_fade(self.h))
+
+    def set_ir_capacity(self, max_taps: int):
+        """aidax_pool_set_ir_capacity: the longest IR the pool takes (8192 .. 65536 taps), before its first prepare_ir / set_ir of any kind"""
+        _check(lib().aidax_pool_set_ir_capacity(self.h, max_taps))
+
+    def ir_capacity(self) -> int:
+        return int(lib().aidax_pool_ir_capacity(self.h))
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

@@ -44,6 +44,44 @@ const uint8_t kSubtypeTail[12] = { 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xa
 
 int wav_error(const std::string& path, const std::string& what) { return fail(AIDAX_ERR_ARG, path + ": " + what); }
 
+// aidax_ir_resample's filter: a sinc of kRsZeros zero crossings a side under a Kaiser window of shape kRsBeta (include/aidax.h)
+constexpr int64_t kRsZeros = 32;
+constexpr double kRsBeta = 12.0;
+constexpr double kRsPi = 3.14159265358979323846;
+constexpr uint32_t kRsMaxLead = 1024;
+
+// I0 by its power series, sum ((x / 2)^k / k!)^2: every term positive, 40 of them at x = 12
+double bessel_i0(double x)
+{
+    const double q = 0.25 * x * x;
+    double term = 1.0, sum = 1.0;
+    for (int k = 1; k < 200; ++k) {
+        term *= q / (static_cast<double>(k) * static_cast<double>(k));
+        sum += term;
+        if (term < 1e-20 * sum) break;
+    }
+    return sum;
+}
+
+uint64_t gcd_u64(uint64_t a, uint64_t b)
+{
+    while (b) { const uint64_t t = a % b; a = b; b = t; }
+    return a;
+}
+
+// sin(pi n / D) from the residue of n mod 2 D folded into [0, D / 2]: exactly 0 where n / D is an integer
+double sin_pi_ratio(int64_t n, int64_t D)
+{
+    int64_t r = n % (2 * D);
+    if (r < 0) r += 2 * D;
+    double sign = 1.0;
+    if (r >= D) { r -= D; sign = -1.0; }
+    if (2 * r > D) r = D - r;
+    return r == 0 ? 0.0 : sign * std::sin(kRsPi * static_cast<double>(r) / static_cast<double>(D));
+}
+
+bool integer_rate(double r) { return r >= 1.0 && r <= 16777216.0 && r == std::floor(r); }
+
 }  // namespace
 
 }  // namespace aidax
@@ -133,6 +171,65 @@ AIDAX_API int aidax_ir_load_wav(const char* path, float* taps, uint32_t cap, uin
     }
     *n_frames = static_cast<uint32_t>(frames);
     *samplerate = static_cast<double>(rate);
+    return AIDAX_OK;
+}
+
+// Band-limited rate conversion of an IR (include/aidax.h). With L / M the reduced ratio rate_out / rate_in, D = max(L, M) and
+// n = (i - lead) M - k L (exact, 64-bit), input tap k reaches output frame i through c sinc(n / D) K(n / (D Z)), c = min(1, L / M):
+// the sinc's sine from n mod 2 D, every sum in fp64 in tap order, one rounding to fp32. No table: any ratio costs the same per tap.
+AIDAX_API int aidax_ir_resample(const float* in, uint32_t n_in, double rate_in, double rate_out, uint32_t lead, float* out, uint32_t cap,
+                                uint32_t* n_full)
+{
+    if (n_full) *n_full = 0;
+    if (!in || !n_full || (cap != 0 && !out)) return fail(AIDAX_ERR_ARG, "null argument");
+    if (n_in == 0) return fail(AIDAX_ERR_ARG, "IR resample: no input taps");
+    if (!integer_rate(rate_in) || !integer_rate(rate_out))
+        return fail(AIDAX_ERR_ARG, "IR resample: sample rates must be positive integers up to 16777216 (got " + std::to_string(rate_in) + " and " + std::to_string(rate_out) + ")");
+    if (lead > kRsMaxLead) return fail(AIDAX_ERR_ARG, "IR resample: lead must be 0 .. 1024 frames");
+    for (uint32_t k = 0; k < n_in; ++k)
+        if (!std::isfinite(in[k])) return fail(AIDAX_ERR_ARG, "IR resample: tap " + std::to_string(k) + " is not finite");
+    const uint64_t ri = static_cast<uint64_t>(rate_in), ro = static_cast<uint64_t>(rate_out), g = gcd_u64(ri, ro);
+    const int64_t L = static_cast<int64_t>(ro / g), M = static_cast<int64_t>(ri / g), D = L > M ? L : M;
+    const int64_t reach = kRsZeros * D;                                      // |n| < reach: the kernel's support
+    // lead + floor((n_in - 1 + Z / c) L / M) + 1, in integers (at most 2^32 2^24 + 2^29)
+    const uint64_t full = static_cast<uint64_t>(lead) + static_cast<uint64_t>((static_cast<int64_t>(n_in - 1) * L + reach) / M) + 1u;
+    if (full >= (uint64_t(1) << 31)) return fail(AIDAX_ERR_ARG, "IR resample: the result would have 2^31 frames or more");
+    *n_full = static_cast<uint32_t>(full);
+    const uint32_t n_out = cap < *n_full ? cap : *n_full;
+    if (L == M) {                                                            // the same rate: the taps as they are, behind the lead
+        for (uint32_t i = 0; i < n_out; ++i) out[i] = i >= lead && i - lead < n_in ? in[i - lead] : 0.f;
+        return AIDAX_OK;
+    }
+    const double scale = L > M ? static_cast<double>(M) / static_cast<double>(L) : 1.0;       // (M / L) c
+    const double inv_i0 = 1.0 / bessel_i0(kRsBeta);
+    auto weight = [&](int64_t n) {
+        if (n == 0) return 1.0;
+        const double x = static_cast<double>(n) / static_cast<double>(D);
+        const double v = x / static_cast<double>(kRsZeros);
+        return sin_pi_ratio(n, D) / (kRsPi * x) * bessel_i0(kRsBeta * std::sqrt(1.0 - v * v)) * inv_i0;
+    };
+    // The weight is a function of n alone, and for the usual ratios (D = 160 between 48 and 44.1 kHz) there are far fewer values of n
+    // than (frame, tap) pairs: a table of all 2 Z D - 1 of them, the same doubles the direct evaluation gives.
+    std::vector<double> table;
+    if (D <= 4096 && static_cast<int64_t>(n_out) > D) {
+        table.resize(static_cast<size_t>(2 * reach - 1));
+        for (int64_t n = 1 - reach; n < reach; ++n) table[static_cast<size_t>(n + reach - 1)] = weight(n);
+    }
+    for (uint32_t i = 0; i < n_out; ++i) {
+        const int64_t a = (static_cast<int64_t>(i) - static_cast<int64_t>(lead)) * M;
+        // the taps k with |a - k L| < reach, floor / ceiling divisions of possibly negative numerators
+        int64_t lo = a - reach, hi = a + reach;
+        int64_t k_lo = (lo >= 0 ? lo / L : -((-lo + L - 1) / L)) + 1;        // floor(lo / L) + 1
+        int64_t k_hi = (hi >= 0 ? (hi + L - 1) / L : -(-hi / L)) - 1;        // ceil(hi / L) - 1
+        if (k_lo < 0) k_lo = 0;
+        if (k_hi > static_cast<int64_t>(n_in) - 1) k_hi = static_cast<int64_t>(n_in) - 1;
+        double acc = 0.0;
+        for (int64_t k = k_lo; k <= k_hi; ++k) {
+            const int64_t n = a - k * L;
+            acc += static_cast<double>(in[k]) * (table.empty() ? weight(n) : table[static_cast<size_t>(n + reach - 1)]);
+        }
+        out[i] = static_cast<float>(scale * acc);
+    }
     return AIDAX_OK;
 }
 

@@ -1,7 +1,7 @@
 // aidax_ir_mfma.hip — the cabinet impulse-response stage: every stream's block convolved with its IR (the pool IR or a bank slot),
 // causally and without latency, as a time-domain Toeplitz GEMM on the matrix cores (k_ir_conv), behind the whole run() of the pass.
 //
-//   y[s][t] = sum_{k < L} h[k] * x[s][t - k]        x = the dry signal (what the pool returns without an IR), L <= 8192
+//   y[s][t] = sum_{k < L} h[k] * x[s][t - k]        x = the dry signal (what the pool returns without an IR), L <= the pool's IR capacity (8192 .. 65536)
 //
 // Per block of n frames and a pool of N streams: M = the block's frames (tiles of 16), N = the streams (16 per MFMA), K = input frames
 // (steps of 32). With the output tile at frame t0 and the input window at frame j0, the A operand is a Toeplitz slice of the IR,
@@ -19,10 +19,15 @@
 // windows are split over S workgroups (the K split, ir_k_splits) whose partial sums a second launch (k_ir_reduce) adds in a fixed order:
 // no atomics, the same bits on every run. S == 1 writes the output directly.
 //
-// The history ring: per stream a row of R + 32 floats, R a power of two >= 8192 + max_frames; frame p of the stream's life sits at
+// The history ring: per stream a row of R + 32 floats, R a power of two >= the pool's IR capacity + max_frames; frame p of the stream's life sits at
 // p mod R, and the first 32 slots are mirrored behind slot R - 1, so that a lane's eight consecutive inputs are contiguous whatever the
 // ring position. k_ir_append writes the block's dry samples into the ring before k_ir_conv reads it (the conv kernel then never reads
 // what it writes: the output may be the same buffer as the dry input). Input frames past the block's end are read as zeros.
+//
+// Nothing here knows the capacity: ring mask and row, and every IR's diagonal count, are run-time arguments. At 65536 taps an IR has 4098
+// diagonals (12.6 MiB of fragments) and a wave walks 2050 windows: frame and window numbers stay below 2^17 in the int arithmetic, ring
+// positions are masked, and stream x row and fragment offsets are formed in size_t. The oldest window may reach up to 31 frames past
+// the IR's last tap; those frames meet zero taps, and their ring slots are in range whatever they hold.
 #include <hip/hip_runtime.h>
 #include <cstdint>
 #include "aidax_kernels.h"

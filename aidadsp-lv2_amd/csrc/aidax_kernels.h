@@ -94,7 +94,7 @@ hipError_t launch_reset_for_model(StreamState* st, float* nn, uint32_t n_streams
 
 // The cabinet IR stage (aidax_ir_mfma.hip). A pool's history ring: per stream a row of ring_row = R + kIrMirror floats (R a power of two,
 // mask = R - 1) whose first kIrMirror slots are repeated behind slot R - 1; `pos` is the ring slot of the block's first frame.
-constexpr uint32_t kIrMaxTaps = 8192;
+constexpr uint32_t kIrMaxTaps = 8192;          // a pool's default IR capacity (aidax_pool_set_ir_capacity raises it), and the longest fade
 constexpr uint32_t kIrMirror = 32;
 constexpr uint32_t kIrItemStreams = 64;        // streams of one work item: the 4 x 16 MFMA columns of a k_ir_conv wave
 // One work item of k_ir_conv's plan: an IR and up to 64 streams that use it, streams[first .. first + count - 1] in stream order

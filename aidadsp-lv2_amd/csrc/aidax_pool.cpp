@@ -361,7 +361,7 @@ struct IrSlot {
 constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
 
 // ... and the stage's history, allocated by the first aidax_pool_prepare_ir / aidax_pool_prepare_ir_slot and fed by every pass from then
-// on (k_ir_append): per stream a ring of the last R >= 8192 + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial
+// on (k_ir_append): per stream a ring of the last R >= capacity + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial
 // sums (aidax_ir_mfma.hip). With it, the device copy of the plan (the IR items k_ir_conv runs: [plan_items_cap] IrItem, then the stream
 // lists) and the pinned snapshots it is uploaded from, stream-ordered with the passes like the control records (flush_ctl).
 struct IrHistory {
@@ -471,6 +471,8 @@ struct aidax_pool {
     std::atomic<IrHistory*> ir_hist_pub{nullptr};
     IrHistory* ir_hist = nullptr;
     uint32_t ir_pos = 0;
+    // the longest IR the pool takes (aidax_pool_set_ir_capacity, set-up side: fixed once the first prepare has sized the history with it)
+    std::atomic<uint32_t> ir_capacity{kIrMaxTaps};
     IrHistory* ir_history()
     {
         if (!ir_hist) ir_hist = ir_hist_pub.load(std::memory_order_acquire);
@@ -1439,7 +1441,9 @@ static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint3
     *out = nullptr;
     if (slot != AIDAX_IR_POOL && (slot < 0 || slot >= AIDAX_IR_SLOTS)) return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
     if (taps) {
-        if (n_taps == 0 || n_taps > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR length must be 1 .. 8192 taps");
+        const uint32_t capacity = p->ir_capacity.load(std::memory_order_relaxed);
+        if (n_taps == 0 || n_taps > capacity)
+            return fail(AIDAX_ERR_ARG, "IR length must be 1 .. " + std::to_string(capacity) + " taps" + (capacity != kIrMaxTaps ? " (the pool's IR capacity)" : ""));
         for (uint32_t k = 0; k < n_taps; ++k)
             if (!std::isfinite(taps[k])) return fail(AIDAX_ERR_ARG, "IR tap " + std::to_string(k) + " is not finite");
         if (samplerate != p->host_sr)
@@ -1456,7 +1460,7 @@ static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint3
         if (!p->ir_hist_pub.load(std::memory_order_acquire)) {
             std::unique_ptr<IrHistory, void (*)(IrHistory*)> h(new IrHistory(), free_ir_history);
             uint32_t R = 1;
-            while (R < kIrMaxTaps + p->max_frames) R <<= 1;
+            while (R < p->ir_capacity.load(std::memory_order_relaxed) + p->max_frames) R <<= 1;
             h->mask = R - 1;
             h->ring_row = R + kIrMirror;
             const size_t block = static_cast<size_t>(p->n_streams) * p->max_frames;
@@ -1573,6 +1577,20 @@ AIDAX_API int aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames)
 }
 
 AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir_fade : 0; }
+
+// Set-up side: a host record that the first prepare reads when it sizes the history ring (R >= capacity + max_frames); the kernels take
+// the ring's mask and row, and every IR's diagonal count, at run time.
+AIDAX_API int aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps)
+{
+    if (max_taps < kIrMaxTaps || max_taps > AIDAX_IR_MAX_CAPACITY) return fail(AIDAX_ERR_ARG, "IR capacity must be 8192 .. 65536 taps");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (p->ir_hist_pub.load(std::memory_order_acquire))
+        return fail(AIDAX_ERR_STATE, "IR capacity is fixed once the first aidax_pool_prepare_ir / _ir_slot has allocated the history");
+    p->ir_capacity.store(max_taps, std::memory_order_relaxed);
+    return AIDAX_OK;
+}
+
+AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p) { return p ? p->ir_capacity.load(std::memory_order_relaxed) : 0; }
 
 AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
 {

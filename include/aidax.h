@@ -204,7 +204,8 @@ AIDAX_API void aidax_staged_free(aidax_staged* staged);
 AIDAX_API int  aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode);
 
 /* Cabinet impulse response (IR): an optional last stage of every stream's run(), after the master gain ramp (rt-neural-generic.cpp:654-655).
- * A pool holds one pool IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models) and a bank
+ * A pool holds one pool IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models; up to 65536
+ * in a pool whose IR capacity was raised, see "IR capacity" below) and a bank
  * of per-stream IRs (below); while it does, the output block of every stream that follows it (by default, all of them) is the causal
  * convolution of the block the pool would have returned without it (`dry`) with h:
  *     y[s][t] = sum_{k < L} h[k] * dry[s][t - k]
@@ -221,8 +222,9 @@ AIDAX_API int  aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int sta
  *                        count and rate. AIDAX_ERR_IO when the file cannot be read, AIDAX_ERR_ARG (with the reason in aidax_last_error)
  *                        for a malformed or unsupported file: truncated chunks, a data size past the end of the file, no frames, other tags.
  * aidax_pool_prepare_ir  WORKER thread: the history on first use, the IR packed into the kernel's operand form and uploaded on the worker
- *                        stream; blocks until done. taps == NULL prepares the removal of the IR. AIDAX_ERR_ARG for L == 0 or L > 8192,
- *                        a tap that is not finite, or a samplerate other than the pool's host rate (no resampling).
+ *                        stream; blocks until done. taps == NULL prepares the removal of the IR. AIDAX_ERR_ARG for L == 0 or L > the pool's
+ *                        IR capacity (8192 unless raised), a tap that is not finite, or a samplerate other than the pool's host rate: this
+ *                        call converts nothing, aidax_ir_resample (below) brings an IR to the pool's rate first.
  * aidax_pool_commit_ir   AUDIO thread, between passes: swaps the prepared IR in (no allocation, no free, no wait); `staged` then holds
  *                        the retired IR for aidax_staged_free on the worker.
  * aidax_pool_set_ir      prepare + commit + free in one blocking call.
@@ -282,9 +284,53 @@ AIDAX_API int  aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_
 AIDAX_API int      aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames);
 AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p);
 
+/* IR rate conversion (host only: no device, no pool, any thread). The IRs the reference ships, like most commercial cabinet IRs, are
+ * 48 kHz files; a pool at another host rate plays them after
+ * aidax_ir_resample   `in` (n_in taps at rate_in) converted to rate_out by a Kaiser-windowed sinc. Both rates are positive integers (as
+ *                     doubles, <= 2^24); with L / M = rate_out / rate_in in lowest terms, c = min(1, L / M), Z = 32 zero crossings a side
+ *                     and beta = 12,
+ *                         out[i] = (M / L) sum_k in[k] c sinc(c u) K(c u / Z),   u = ((i - lead) M - k L) / L,
+ *                         K(v) = I0(beta sqrt(1 - v^2)) / I0(beta) for |v| < 1, else 0,
+ *                     evaluated in fp64 from the exact integer (i - lead) M - k L (the sine from its residue, so an integer u weighs
+ *                     exactly 0, and 1 at u = 0) and rounded once to fp32. The factor M / L keeps the frequency response of the filter
+ *                     that the IR is (sum out ~ sum in): the cabinet sounds as loud at either rate. Equal rates give a bit copy of `in`
+ *                     behind `lead` zeros; a ratio L / M = r of 2 or 4 gives out[lead + r k] == in[k] / r bit for bit. The same inputs
+ *                     give the same bits.
+ *                     lead: output frame i stands for time (i - lead) / rate_out. A band-limited copy of a causal IR rings before
+ *                     t = 0, over ceil(Z max(1, L / M)) frames; `lead` (0 .. 1024) of those frames are kept, frames before the
+ *                     kernel's support are zeros, and the caller reports `lead` frames to its host as latency. lead = 0 cuts the
+ *                     pre-ringing off for a cabinet without latency, at the price of an error in the passband response of about
+ *                     0.1 % from 48 to 44.1 kHz and about 2 % going up (1.1e-3 / 1.9e-2 / 2.3e-2 of max |H| to 44.1 / 96 / 192 kHz
+ *                     on a decaying-noise IR of 8192 taps).
+ *                     Length: *n_full = lead + floor((n_in - 1 + Z / c) L / M) + 1 frames hold the whole support (16447 for 8192 taps
+ *                     from 48 to 96 kHz); min(cap, *n_full) are written to `out`; cap == 0 with out == NULL asks for *n_full alone, as
+ *                     in aidax_ir_load_wav. A result cut short by `cap` ends abruptly: no fade is applied to its tail.
+ *                     AIDAX_ERR_ARG for a null `in` or `n_full` (or `out` with cap > 0), n_in == 0, a tap that is not finite, a rate
+ *                     that is not a positive integer, lead > 1024, or a result of 2^31 frames or more. At most
+ *                     *n_full x 2 Z max(1, M / L) kernel values; about 2 ms on one host core for 8192 taps from 48 to 44.1, 96 or 192 kHz
+ *                     (the weights of a ratio with max(L, M) <= 4096 are tabulated once per call), 40 ms for an odd ratio such as 48000 : 44101. */
+AIDAX_API int      aidax_ir_resample(const float* in, uint32_t n_in, double rate_in, double rate_out, uint32_t lead, float* out, uint32_t cap,
+                                     uint32_t* n_full);
+
+/* IR capacity: the longest IR a pool takes, 8192 taps by default and up to AIDAX_IR_MAX_CAPACITY for a pool that asks. An 8192-frame
+ * 48 kHz cabinet is about 16 450 taps at a 96 kHz host and 32 830 at 192 kHz; 65536 taps are 1.36 s at 48 kHz. The capacity sizes the
+ * history: the first prepare of either kind allocates n_streams x (R + 32) x 4 bytes of ring, R the power of two >= capacity +
+ * max_frames (1024 streams x 256 frames: 67 MB at the default, 537 MB at 65536). The stage's work per block is linear in the taps of
+ * the IRs in use, not in the capacity; a pool that never raises it allocates and launches exactly what it did before this call existed.
+ * The fade length keeps its limit of 8192 frames.
+ * aidax_pool_set_ir_capacity  SET-UP side, before the pool's first aidax_pool_prepare_ir / _ir_slot (and not concurrently with it):
+ *                             a host record. AIDAX_ERR_ARG for a null pool or max_taps outside 8192 .. 65536, AIDAX_ERR_STATE once
+ *                             the history has been allocated.
+ * aidax_pool_ir_capacity      the capacity in taps (0 for a null pool). */
+#define AIDAX_IR_MAX_CAPACITY 65536
+AIDAX_API int      aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps);
+AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
  * reset_stream, commit_model, commit_ir, assign_ir, set_ir_fade, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
- * prepare_ir, prepare_ir_slot, staged_free). None of the audio-side calls allocates or frees device or pinned memory, and only
+ * prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
+ * before the two threads start; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * habit. None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync wait for the GPU (for the stream that carries the pass, never for the
  * device) — with one exception in every pass: changed control records, and a changed IR plan (after an assign_ir or a commit_ir), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has

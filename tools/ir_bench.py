@@ -14,10 +14,16 @@
                 pass) with all 1024 streams fading (a pool-IR commit), with 16 of 1024 fading (assign_ir), and the round trip of a
                 one-stream pool whose every pass is a fade pass, at 64 and 256 frames
 
-The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs). Under rocprofv3 --kernel-trace
+  --taps N      the IR's length (default 8192); above 8192 every pool's IR capacity is raised to N (aidax_pool_set_ir_capacity), and the
+                arithmetic floor scales with N
+
+  --rate R      a pool at host rate R playing a 48 kHz cabinet of 8192 frames brought to R by aidax_ir_resample ("rate": the host time
+                of the conversion, the taps it gives, cfg2 and the one-stream round trip with them; the capacity is raised as needed)
+
+The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs) unless --taps says otherwise. Under rocprofv3 --kernel-trace
 --stats the k_ir_conv / k_ir_reduce / k_ir_append rows are the stage's kernels alone.
 
-    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64] [--fade 256]
+    python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64] [--fade 256] [--taps 65536] [--rate 96000]
 """
 import argparse
 import importlib
@@ -33,12 +39,25 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
 FLOOR_US = 10.5          # cfg2 at 8192 taps: 2.15e9 MACs as six bf16 products on 16x16x32 MFMAs at 16 cycles per SIMD, 2.4 GHz
+TAPS = 8192              # --taps: the length of cabinet_ir(), and above 8192 the capacity every pool here is given
+IR = None                # --rate: the taps every pool here plays instead of cabinet_ir()
+SR = 48000.0             # ... and the pools' host rate
 
 
-def cabinet_ir(L=8192, seed=8192):
+def cabinet_ir(L=None, seed=8192):
+    if IR is not None:
+        return IR
+    L = L or TAPS
     rng = np.random.default_rng(seed)
     t = np.arange(L)
     return (rng.standard_normal(L) * np.exp(-t / (L / 6.0)) * 0.05).astype(np.float32)
+
+
+def new_pool(ax, S, n):
+    pool = ax.Pool(S, n, SR)
+    if TAPS > 8192:
+        pool.set_ir_capacity(TAPS)
+    return pool
 
 
 def load_bank(pool, S, K, pattern):
@@ -51,7 +70,7 @@ def load_bank(pool, S, K, pattern):
 
 def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None, fade=0):
     S, n = 1024, 256
-    pool = ax.Pool(S, n)
+    pool = new_pool(ax, S, n)
     pool.set_model(ax.Model(path))
     if fade:
         pool.set_ir_fade(fade)
@@ -81,7 +100,7 @@ def cfg2_fade_pass(ax, W, torch, path, fade, reps, warmup, which):
     """us of single passes, each between two events: (plain passes, fade passes). which: "commit" (a pool-IR commit before every fade
     pass: all 1024 streams fade, 8192 taps on both sides) or "assign" (16 streams moved between the pool IR and a slot)"""
     S, n = 1024, 256
-    pool = ax.Pool(S, n)
+    pool = new_pool(ax, S, n)
     pool.set_model(ax.Model(path))
     pool.set_ir_fade(fade)
     pool.set_ir(cabinet_ir())
@@ -117,7 +136,7 @@ def cfg2_fade_pass(ax, W, torch, path, fade, reps, warmup, which):
 
 def one_stream_fade(ax, W, path, frames, calls, fade):
     """aidax_pool_process round trip of a one-stream pool: plain passes, then passes that each follow an assign_ir (every one a fade pass)"""
-    pool = ax.Pool(1, frames)
+    pool = new_pool(ax, 1, frames)
     pool.set_model(ax.Model(path))
     pool.set_ir_fade(fade)
     pool.set_ir(cabinet_ir())
@@ -140,7 +159,7 @@ def one_stream_fade(ax, W, path, frames, calls, fade):
 
 
 def one_stream(ax, W, path, with_ir, frames, calls, bank=False):
-    pool = ax.Pool(1, frames)
+    pool = new_pool(ax, 1, frames)
     pool.set_model(ax.Model(path))
     if with_ir:
         pool.set_ir(cabinet_ir())
@@ -165,18 +184,35 @@ def main():
     ap.add_argument("--calls", type=int, default=400)
     ap.add_argument("--irs", default="", help="comma-separated K: cfg2 with K distinct IRs in bank slots (e.g. 1,4,16,64)")
     ap.add_argument("--fade", type=int, default=0, help="fade length in frames: the IR fade's steady state and the cost of one fade pass")
+    ap.add_argument("--taps", type=int, default=8192, help="IR length; above 8192 the pools' IR capacity is raised to it")
+    ap.add_argument("--rate", type=int, default=0, help="host rate of the pools: a 48 kHz cabinet of 8192 frames converted to it")
     a = ap.parse_args()
     import torch
     ax = importlib.import_module("aidadsp-lv2_amd")
+    global TAPS, IR, SR
+    TAPS = a.taps
+    rate = None
+    if a.rate:
+        src = cabinet_ir(8192)
+        t = []
+        for _ in range(5):
+            t0 = time.perf_counter()
+            taps, n_full = ax.resample_ir(src, 48000, a.rate)
+            t.append(time.perf_counter() - t0)
+        IR, SR, TAPS = taps, float(a.rate), max(8192, int(n_full))
+        rate = {"host_rate": a.rate, "taps": int(n_full), "resample_ms_best_of_5": round(min(t) * 1e3, 3)}
     W = ax.workloads
     d = tempfile.mkdtemp(prefix="ir_bench_")
     cfg2 = W.write_model(W.make_model("lstm", 32, 1, seed=32), os.path.join(d, "lstm32.json"))
     lv2 = os.path.join(ROOT, "tests", "golden", "models", "tw40_california_clean_deerinkstudios.json")
-    out = {"lib": os.path.relpath(ax.lib_path(), ROOT), "ir_taps": 8192, "steps": a.steps}
+    out = {"lib": os.path.relpath(ax.lib_path(), ROOT), "ir_taps": int(cabinet_ir().size), "steps": a.steps}
+    if rate:
+        out["rate"] = rate
+    floor_us = FLOOR_US * cabinet_ir().size / 8192
     dry = cfg2_us(ax, W, torch, cfg2, False, a.steps, a.warmup)
     wet = cfg2_us(ax, W, torch, cfg2, True, a.steps, a.warmup)
     out["cfg2"] = {"us_per_block_no_ir": round(dry, 2), "us_per_block_ir": round(wet, 2), "ir_stage_us": round(wet - dry, 2),
-                   "ir_stage_over_floor": round((wet - dry) / FLOOR_US, 2), "floor_us": FLOOR_US}
+                   "ir_stage_over_floor": round((wet - dry) / floor_us, 2), "floor_us": round(floor_us, 2)}
     out["one_stream"] = {}
     for frames in (64, 256):
         out["one_stream"][str(frames)] = {"no_ir": one_stream(ax, W, lv2, False, frames, a.calls),
