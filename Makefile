@@ -21,7 +21,7 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -We
 # GRU-24 pipeline 88.5 -> 84.1 us, cfg3 478 -> 464 us, nothing slower by more than noise)
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS) -fno-slp-vectorize
 
-HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp
+HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_ir_stage.cpp
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
 KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp_p1.o $(OBJDIR)/aidax_mfmalp_p2.o $(OBJDIR)/aidax_mfmalp_p3.o $(OBJDIR)/aidax_mfmalp_p4.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o
 HDRS      := $(wildcard $(SRC)/*.h) include/aidax.h
@@ -84,7 +84,7 @@ build/asan/asan_harness: $(ASAN_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude $(ASAN_SRCS) -o $@
 asan: build/asan/asan_harness
 
-# ... and the IR stage's host side (aidax_ir_resample, the fragment packer) the same way: tests/asan_ir_harness.cpp, tests/test_asan_ir.py
+# ... and the IR stage's host side (aidax_ir_resample, the fragment packer, IrPlan) the same way: tests/asan_ir_harness.cpp, tests/test_asan_ir.py
 ASAN_IR_SRCS := tests/asan_ir_harness.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
 build/asan/asan_ir_harness: $(ASAN_IR_SRCS) $(HDRS) $(SRC)/json_min.h
 	@mkdir -p build/asan

@@ -1,13 +1,14 @@
 // aidax_ir.cpp — host side of the cabinet IR stage: the WAV reader (aidax_ir_load_wav) and the packer that turns an IR into the
-// A fragments k_ir_conv multiplies (aidax_ir_mfma.hip). Host only; the pool's half (prepare / commit) is in aidax_pool.cpp.
+// A fragments k_ir_conv multiplies (aidax_ir_mfma.hip), and IrPlan, the stage's plan builder. Host only, no HIP call; the device half is
+// IrStage (aidax_ir_stage.cpp).
+#include <algorithm>
 #include <cmath>
 #include <cstdio>
 #include <cstring>
 #include <string>
 #include <vector>
 
-#include "aidax_internal.h"
-#include "aidax_kernels.h"
+#include "aidax_ir_stage.h"
 
 namespace aidax {
 
@@ -30,6 +31,98 @@ std::vector<uint32_t> pack_ir_fragments(const float* h, uint32_t n_taps, uint32_
             }
     *n_diag = Q;
     return out;
+}
+
+void IrPlan::init(uint32_t n)
+{
+    const size_t runs = (n + kIrItemStreams - 1) / kIrItemStreams;
+    n_streams = n;
+    assign.assign(n, AIDAX_IR_POOL);
+    played_key.assign(n, -1);
+    played_gen.assign(n, 0);
+    main.items.resize(runs + kKeys);
+    main.streams.resize(n);
+    fade_out.items.resize(runs + 2 * kKeys);
+    fade_out.streams.resize(n);
+    mix.resize(n);
+    src.resize(n);
+}
+
+// A section from src[]: the streams with src[s] >= 0 grouped by source, the sources in index order, each one's streams in stream order,
+// cut into items of up to kIrItemStreams. Returns the largest number of streams one source holds.
+uint32_t IrPlan::group(IrSection& sec, int n_sources)
+{
+    uint32_t count[2 * kKeys] = {}, at[2 * kKeys];
+    for (uint32_t s = 0; s < n_streams; ++s)
+        if (src[s] >= 0) ++count[src[s]];
+    uint32_t first = 0, most = 0;
+    for (int k = 0; k < n_sources; ++k) { at[k] = first; first += count[k]; }
+    sec.n_listed = first;
+    for (uint32_t s = 0; s < n_streams; ++s)
+        if (src[s] >= 0) sec.streams[at[src[s]]++] = s;
+    sec.n_items = sec.max_diag = 0;
+    first = 0;
+    for (int k = 0; k < n_sources; ++k) {
+        if (count[k] == 0) continue;
+        const IrSlot& sl = source(k);
+        for (uint32_t c = 0; c < count[k]; c += kIrItemStreams)
+            sec.items[sec.n_items++] = IrItem{ sl.d_frag, sl.n_diag, std::min(kIrItemStreams, count[k] - c), first + c, 0u };
+        sec.max_diag = std::max(sec.max_diag, sl.n_diag);
+        most = std::max(most, count[k]);
+        first += count[k];
+    }
+    return most;
+}
+
+// `any_pass`: the pool has issued a pass (its first one has nothing to fade from). Without a fade length the streams switch as they
+// always did; a stream whose old IR is held nowhere any more (neither live nor parked: it was retired under a fade length of 0)
+// switches without a fade too.
+void IrPlan::rebuild(bool any_pass)
+{
+    for (uint32_t s = 0; s < n_streams; ++s) src[s] = static_cast<int16_t>(key(s));
+    identity = group(main, kKeys) == n_streams;
+    const bool fading = any_pass && fade != 0;
+    spend_fade();
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        const int nk = src[s], ok = played_key[s];
+        const uint64_t ng = nk >= 0 ? live[nk].gen : 0, og = played_gen[s];
+        src[s] = -2;                                               // no fade
+        played_key[s] = static_cast<int8_t>(nk);
+        played_gen[s] = ng;
+        if (!fading || (nk == ok && ng == og)) continue;
+        if (ok < 0) src[s] = -1;                                   // from the dry block
+        else if (live[ok].d_frag && live[ok].gen == og) src[s] = static_cast<int16_t>(ok);
+        else if (parked[ok].d_frag && parked[ok].gen == og) src[s] = static_cast<int16_t>(kKeys + ok);
+        if (src[s] >= -1) mix[n_mix++] = s | (src[s] < 0 ? kIrFadeDry : 0u);
+    }
+    if (n_mix) group(fade_out, 2 * kKeys);
+    dirty = false;
+}
+
+void IrPlan::commit(int key, IrSlot& staged)
+{
+    staged.gen = staged.d_frag ? gen_next++ : 0;
+    std::swap(live[key], staged);
+    // With a fade length set, content that has been played (a pass was issued since its commit) is parked for the streams that will
+    // fade from it in the next pass, and `staged` gets what was parked before: an IR retired one commit earlier, whose last possible
+    // use, a fade pass, precedes the commit's fence. Content that was never played has no stream to fade from it: it goes to `staged`
+    // as ever, and what is parked (which streams may still have played) stays.
+    if (fade != 0 && commit_seq[key] != pass_seq) std::swap(parked[key], staged);
+    commit_seq[key] = pass_seq;
+    dirty = true;                                                  // every stream of that IR switches at this block boundary
+}
+
+size_t IrPlan::serialise(uint8_t* snapshot) const
+{
+    std::memcpy(snapshot, main.items.data(), main.n_items * sizeof(IrItem));
+    std::memcpy(snapshot + plan_items_bytes(), main.streams.data(), main.n_listed * sizeof(uint32_t));
+    if (n_mix == 0) return plan_items_bytes() + main.n_listed * sizeof(uint32_t);
+    // the fade-out section rides in the same upload: one copy up to the end of the mix list. It also carries the snapshot's gaps
+    // (stream-list entries past n_listed, items past n_items), which no kernel reads: the counts travel as arguments
+    std::memcpy(snapshot + fade_items_off(), fade_out.items.data(), fade_out.n_items * sizeof(IrItem));
+    std::memcpy(snapshot + fade_streams_off(), fade_out.streams.data(), fade_out.n_listed * sizeof(uint32_t));
+    std::memcpy(snapshot + fade_mix_off(), mix.data(), n_mix * sizeof(uint32_t));
+    return fade_mix_off() + n_mix * sizeof(uint32_t);
 }
 
 namespace {

@@ -1,0 +1,171 @@
+// aidax_ir_stage.cpp — the device half of the cabinet IR stage (aidax_ir_stage.h): the history, the IR and plan uploads and the
+// launches of aidax_ir_mfma.hip behind every pass. Host logic only.
+#include <algorithm>
+#include <memory>
+
+#include "aidax_ir_stage.h"
+#include "aidax_hip_host.h"
+
+namespace aidax {
+
+constexpr int kPlanRing = 4;                             // pinned snapshots of the plan in flight
+
+// Per stream a ring of the last R >= capacity + max_frames dry samples (aidax_kernels.h: IrArgs), fed by every pass (k_ir_append), and
+// the K split's partial sums (aidax_ir_mfma.hip). With it, the device copy of the plan (IrPlan's layout) and the pinned snapshots it
+// is uploaded from, stream-ordered with the passes like the pool's control records.
+struct IrHistory {
+    float* ring = nullptr;
+    float* part = nullptr;
+    uint32_t ring_row = 0, mask = 0, split_cap = 1;
+    uint8_t* d_plan = nullptr;
+    uint8_t* h_plan[kPlanRing] = {};
+    hipEvent_t plan_ev[kPlanRing] = {};
+    bool plan_used[kPlanRing] = {};
+    int plan_next = 0;                   // (audio side)
+    float* side = nullptr;               // the IR fade's side buffer, [n_streams][max_frames]: what the fade-out section of a fade pass convolves into
+};
+
+static void free_ir_history(IrHistory* h)
+{
+    if (!h) return;
+    if (h->ring) (void)hipFree(h->ring);
+    if (h->part) (void)hipFree(h->part);
+    if (h->d_plan) (void)hipFree(h->d_plan);
+    if (h->side) (void)hipFree(h->side);
+    for (int k = 0; k < kPlanRing; ++k) {
+        if (h->h_plan[k]) (void)hipHostFree(h->h_plan[k]);
+        if (h->plan_ev[k]) (void)hipEventDestroy(h->plan_ev[k]);
+    }
+    delete h;
+}
+
+void IrStage::release()
+{
+    for (IrSlot* bank : { plan.live, plan.parked })
+        for (int k = 0; k < IrPlan::kKeys; ++k) {
+            if (bank[k].d_frag) (void)hipFree(bank[k].d_frag);
+            bank[k] = IrSlot{};
+        }
+    free_ir_history(pub_.exchange(nullptr));
+    hist_ = nullptr;
+}
+
+void IrStage::prepare(const float* taps, uint32_t n_taps, IrSlot& ir)
+{
+    if (!has_history()) {
+        std::unique_ptr<IrHistory, void (*)(IrHistory*)> h(new IrHistory(), free_ir_history);
+        uint32_t R = 1;
+        while (R < capacity.load(std::memory_order_relaxed) + max_frames_) R <<= 1;
+        h->mask = R - 1;
+        h->ring_row = R + kIrMirror;
+        const size_t block = static_cast<size_t>(plan.n_streams) * max_frames_;
+        const size_t budget = size_t(16) << 20;              // floats of partial sums (64 MiB)
+        h->split_cap = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(64, budget / block)));
+        const size_t ring_bytes = sizeof(float) * plan.n_streams * static_cast<size_t>(h->ring_row);
+        HIP_TRY(hipMalloc(&h->ring, ring_bytes));
+        if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
+        HIP_TRY(hipMalloc(&h->side, sizeof(float) * block));
+        const size_t plan_bytes = plan.plan_bytes();         // both sections, whether a fade length is set or not
+        HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
+        for (int k = 0; k < kPlanRing; ++k) {
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_plan[k]), plan_bytes, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&h->plan_ev[k], hipEventDisableTiming));
+        }
+        HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, wq_));
+        HIP_TRY(hipStreamSynchronize(wq_));
+        pub_.store(h.release(), std::memory_order_release);
+    }
+    if (taps) {
+        const std::vector<uint32_t> frag = pack_ir_fragments(taps, n_taps, &ir.n_diag);
+        ir.n_taps = n_taps;
+        HIP_TRY(hipMalloc(&ir.d_frag, frag.size() * sizeof(uint32_t)));
+        HIP_TRY(hipMemcpyAsync(ir.d_frag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice, wq_));
+        HIP_TRY(hipStreamSynchronize(wq_));                 // `frag` is pageable; the audio side must find the IR complete
+    }
+}
+
+void IrStage::commit(int32_t slot, IrSlot& staged, hipEvent_t fence, hipStream_t q)
+{
+    HIP_TRY(hipEventRecord(fence, q));                       // the retired fragments are free once the passes before this point have run
+    plan.commit(1 + slot, staged);
+    (void)adopt();
+}
+
+// the passes already issued keep the plan they were issued with: the device copy is overwritten behind them, from a pinned snapshot
+// that no later rebuild touches while it is in flight
+void IrStage::flush_plan(hipStream_t s, bool any_pass)
+{
+    IrHistory* h = hist_;
+    plan.rebuild(any_pass);
+    const int k = h->plan_next;
+    if (h->plan_used[k] && hipEventQuery(h->plan_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(h->plan_ev[k]));   // four rebuilds behind
+    const size_t bytes = plan.serialise(h->h_plan[k]);
+    HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], bytes, hipMemcpyHostToDevice, s));
+    HIP_TRY(hipEventRecord(h->plan_ev[k], s));
+    h->plan_used[k] = true;
+    h->plan_next = (k + 1) % kPlanRing;
+}
+
+// k_ir_conv's arguments for one section of the plan, which lies at these offsets of the device copy
+IrArgs IrStage::conv_args(const IrSection& sec, size_t items_off, size_t streams_off, float* out, uint32_t n_active, uint32_t n_frames) const
+{
+    const IrHistory* h = hist_;
+    IrArgs a{};
+    a.items = reinterpret_cast<const IrItem*>(h->d_plan + items_off);
+    a.streams = reinterpret_cast<const uint32_t*>(h->d_plan + streams_off);
+    a.n_items = sec.n_items; a.n_listed = sec.n_listed;
+    a.ring = h->ring; a.out = out; a.part = h->part;
+    a.ring_row = h->ring_row; a.mask = h->mask; a.pos = pos_;
+    a.n_streams = n_active; a.n_frames = n_frames;
+    return a;
+}
+
+void IrStage::issue(hipStream_t s, float* d_out, uint32_t n_active, uint32_t n_frames)
+{
+    IrHistory* h = hist_;
+    // the block's dry samples into the history (also while no IR is live), then the convolution over the history, in place on d_out,
+    // of the streams the plan holds (one launch whatever the number of IRs)
+    HIP_TRY(launch_ir_append(h->ring, h->ring_row, h->mask, pos_, d_out, n_active, n_frames, s));
+    if (plan.main.n_items) {
+        IrArgs ia = conv_args(plan.main, 0, plan.plan_items_bytes(), d_out, n_active, n_frames);
+        if (plan.identity) {
+            // the identity plan over the prefix only: the grid of a one-IR pool (entries at or beyond n_active are skipped anyway)
+            ia.n_items = std::min(ia.n_items, (n_active + kIrItemStreams - 1) / kIrItemStreams);
+            ia.n_listed = n_active;
+        }
+        ia.n_splits = ir_k_splits(ia.n_items, n_frames, plan.main.max_diag, cus_, h->split_cap);
+        HIP_TRY(launch_ir_conv(ia, s));
+    }
+    if (plan.n_mix) {
+        // an IR change since the last pass: the old IRs over the same history into the side buffer (the fade-out section: the
+        // same kernel, K split and fixed-order reduce, `part` reused behind the main section's reduce), then the crossfade of the
+        // first min(F, n_frames) frames in place on d_out
+        if (plan.fade_out.n_items) {
+            IrArgs fa = conv_args(plan.fade_out, plan.fade_items_off(), plan.fade_streams_off(), h->side, n_active, n_frames);
+            fa.n_splits = ir_k_splits(fa.n_items, n_frames, plan.fade_out.max_diag, cus_, h->split_cap);
+            HIP_TRY(launch_ir_conv(fa, s));
+        }
+        IrFadeArgs fm{};
+        fm.mix = reinterpret_cast<const uint32_t*>(h->d_plan + plan.fade_mix_off());
+        fm.side = h->side; fm.ring = h->ring; fm.out = d_out;
+        fm.n_mix = plan.n_mix; fm.ring_row = h->ring_row; fm.mask = h->mask; fm.pos = pos_;
+        fm.n_streams = n_active; fm.n_frames = n_frames;
+        fm.lf = std::min(plan.fade, n_frames);
+        HIP_TRY(launch_ir_fade(fm, s));
+    }
+    plan.pass_issued();
+    pos_ = (pos_ + n_frames) & h->mask;
+}
+
+void IrStage::clear_stream(uint32_t stream, hipStream_t q)
+{
+    if (!adopt()) return;
+    HIP_TRY(hipMemsetAsync(hist_->ring + static_cast<size_t>(stream) * hist_->ring_row, 0, sizeof(float) * hist_->ring_row, q));
+}
+
+void IrStage::clear_all(hipStream_t q)
+{
+    (void)hipMemsetAsync(hist_->ring, 0, sizeof(float) * plan.n_streams * static_cast<size_t>(hist_->ring_row), q);
+}
+
+}  // namespace aidax

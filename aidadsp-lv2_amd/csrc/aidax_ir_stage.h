@@ -1,0 +1,133 @@
+// aidax_ir_stage.h — the cabinet IR stage of a pool: IrPlan, its host-only half (aidax_ir.cpp: which stream goes through which IR, and
+// the work items k_ir_conv runs for that), and IrStage, the device half around it (aidax_ir_stage.cpp: the history, the uploads, the launches).
+#pragma once
+
+#include <atomic>
+#include <cstdint>
+#include <vector>
+
+#include "aidax_internal.h"
+#include "aidax_kernels.h"
+
+namespace aidax {
+
+// One IR's content on the device (aidax_pool_prepare_ir / aidax_pool_commit_ir): its A fragments for k_ir_conv, swapped in and out like a model.
+struct IrSlot {
+    uint32_t* d_frag = nullptr;      // nullptr: no IR
+    uint32_t n_taps = 0, n_diag = 0;
+    uint64_t gen = 0;                // which committed content this is (a number per commit, given by the commit; 0: none): the IR fade's identity of an IR
+};
+
+// One section of the plan: IRs with the streams that go through them, as items of up to kIrItemStreams streams — the IRs in source
+// order, each IR's streams in stream order (items[i] lists streams[first .. first + count - 1]). Host memory sized at creation.
+struct IrSection {
+    std::vector<IrItem> items;
+    std::vector<uint32_t> streams;       // [n_streams]
+    uint32_t n_items = 0, n_listed = 0, max_diag = 0;
+    void clear() { n_items = n_listed = max_diag = 0; }
+};
+
+// Which IR each stream's output goes through (AIDAX_IR_POOL, AIDAX_IR_NONE or a bank slot), and the plan built from it on the audio
+// side whenever an assignment or a commit has changed it. An IR's key: 0 the pool IR, 1 + j bank slot j. One IR for every stream gives
+// the identity plan (item i: streams 64 i ..). No HIP call in here.
+//
+// The IR fade (`fade` frames; 0: off). Every commit gives its content a generation number, and a stream records the (key, generation)
+// of the IR it went through in the last pass issued (-1 / 0: none). A rebuild that finds another one in force for a stream adds the
+// stream to the fade-out section: the old IRs (still live, or parked, see commit) with the streams fading from them, and to the mix list
+// (k_ir_fade: stream index, kIrFadeDry set where the old side is the dry block). That section serves the one pass it was built for:
+// pass_issued() ends it, and so does spend_fade() for a pass that failed on its way.
+struct IrPlan {
+    static constexpr int kKeys = AIDAX_IR_SLOTS + 1;
+    uint32_t n_streams = 0;
+    std::vector<int32_t> assign;             // [n_streams]
+    IrSlot live[kKeys];                      // d_frag == nullptr: empty
+    IrSlot parked[kKeys];                    // per key: the content retired last, kept for the streams that still fade from it
+    uint64_t gen_next = 1;
+    uint64_t pass_seq = 0;                   // passes issued through the stage
+    uint64_t commit_seq[kKeys] = {};         // ... when the key's content was committed: smaller than pass_seq = it has been played
+    std::vector<int8_t> played_key;          // [n_streams]
+    std::vector<uint64_t> played_gen;        // [n_streams]
+    uint32_t fade = 0;
+    IrSection main, fade_out;                // items: [ceil(n_streams / 64) + 65] and [ceil(n_streams / 64) + 2 * 65]
+    std::vector<uint32_t> mix;               // [n_streams]
+    uint32_t n_mix = 0;
+    bool identity = false, dirty = true;
+
+    void init(uint32_t n);
+    int key(uint32_t s) const                // the key of the IR stream s goes through; -1: none (also an empty slot)
+    {
+        static_assert(AIDAX_IR_POOL == -1 && AIDAX_IR_NONE == -2, "an assignment is its key - 1");
+        const int k = 1 + assign[s];
+        return k >= 0 && live[k].d_frag ? k : -1;
+    }
+    // both sections for the pass about to be issued, and every stream's played record brought up to that pass
+    void rebuild(bool any_pass);
+    void pass_issued() { ++pass_seq; spend_fade(); }
+    void spend_fade() { fade_out.clear(); n_mix = 0; }
+    // the host half of aidax_pool_commit_ir: `staged` becomes the content of `key` and gets back what is to be freed
+    void commit(int key, IrSlot& staged);
+
+    // The plan's bytes on the device and in a snapshot: the main section's items and stream list, then (8-byte aligned) the fade-out
+    // section's, then the mix list. serialise() writes what the sections hold and returns the length to upload from the snapshot's start.
+    size_t plan_items_bytes() const { return main.items.size() * sizeof(IrItem); }
+    size_t fade_items_off() const { return (plan_items_bytes() + sizeof(uint32_t) * n_streams + 7u) & ~size_t(7); }
+    size_t fade_streams_off() const { return fade_items_off() + fade_out.items.size() * sizeof(IrItem); }
+    size_t fade_mix_off() const { return fade_streams_off() + sizeof(uint32_t) * n_streams; }
+    size_t plan_bytes() const { return fade_mix_off() + sizeof(uint32_t) * n_streams; }
+    size_t serialise(uint8_t* snapshot) const;
+
+  private:
+    std::vector<int16_t> src;                // [n_streams]: scratch of rebuild, each stream's source in the section being grouped
+    // source k of a section: live[k] for k < kKeys, parked[k - kKeys] behind them
+    const IrSlot& source(int k) const { return k < kKeys ? live[k] : parked[k - kKeys]; }
+    uint32_t group(IrSection& sec, int n_sources);
+};
+
+struct IrHistory;
+
+// The device half. The history (per stream a ring of dry samples, the K split's partial sums, the fade's side buffer, the device copy
+// of the plan and the pinned snapshots it is uploaded from) is allocated by the first prepare and published ONCE by the worker side;
+// the audio side picks it up at its next call (adopt) and owns everything else in here. Every function but prepare, capacity and
+// has_history is the audio side's; HIP failures leave as HipFail.
+struct IrStage {
+    IrPlan plan;
+
+    void init(uint32_t n_streams, uint32_t max_frames, int cus, hipStream_t worker)
+    {
+        max_frames_ = max_frames; cus_ = cus; wq_ = worker;
+        plan.init(n_streams);
+    }
+    void release();
+    // the longest IR the stage takes (aidax_pool_set_ir_capacity, set-up side: fixed once the first prepare has sized the history with it)
+    std::atomic<uint32_t> capacity{kIrMaxTaps};
+    bool has_history() const { return pub_.load(std::memory_order_acquire) != nullptr; }
+    // worker side: the history on first use (allocated, zeroed, published), then the IR's fragments packed and uploaded (taps == nullptr: none)
+    void prepare(const float* taps, uint32_t n_taps, IrSlot& out);
+    // a swap of host records behind `fence`, recorded on q: no allocation, no free, no wait
+    void commit(int32_t slot, IrSlot& staged, hipEvent_t fence, hipStream_t q);
+    // is there a history (from now on every pass of n_frames > 0 goes through begin_pass and issue)?
+    bool adopt() { return hist_ || (hist_ = pub_.load(std::memory_order_acquire)); }
+    // ahead of the pass's model launch: a dirty plan rebuilt and uploaded, stream-ordered with the passes that follow. A fade-out
+    // section that a failed pass left behind is dropped here (a later pass, with another n_frames and ring position, must not run it)
+    void begin_pass(hipStream_t s, bool any_pass)
+    {
+        plan.spend_fade();
+        if (plan.dirty) flush_plan(s, any_pass);
+    }
+    // behind it: the block's dry samples into the history, the convolution in place on d_out, the fade-out section and the mix
+    void issue(hipStream_t s, float* d_out, uint32_t n_active, uint32_t n_frames);
+    void clear_stream(uint32_t stream, hipStream_t q);       // one stream's past, if there is a history
+    void clear_all(hipStream_t q);                           // every stream's (errors ignored: the k_mfma_lp give-up path)
+
+  private:
+    uint32_t max_frames_ = 0;
+    int cus_ = 0;
+    hipStream_t wq_ = nullptr;
+    std::atomic<IrHistory*> pub_{nullptr};
+    IrHistory* hist_ = nullptr;
+    uint32_t pos_ = 0;                       // the ring slot of the next pass's first frame
+    void flush_plan(hipStream_t s, bool any_pass);
+    IrArgs conv_args(const IrSection& sec, size_t items_off, size_t streams_off, float* out, uint32_t n_active, uint32_t n_frames) const;
+};
+
+}  // namespace aidax

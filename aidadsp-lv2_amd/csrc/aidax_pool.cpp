@@ -13,55 +13,11 @@
 #include <memory>
 #include <mutex>
 #include <thread>
-#include <sstream>
 #include <string>
 
-#include "aidax_internal.h"
-#include "aidax_kernels.h"
+#include "aidax_ir_stage.h"
+#include "aidax_hip_host.h"
 
-#ifdef AIDAX_TEST_HOOKS
-// Test build only: per thread, how often this file calls each HIP runtime entry point it uses (every call site, checked with HIP_TRY or
-// not) and each IR stage launcher, read and cleared by aidax_test_hip_calls below. A fixed table per thread: counting allocates nothing.
-// (tests/test_gpu_ir_bank_rt.py: the audio-thread calls allocate, free and wait for nothing.)
-namespace aidax {
-namespace {
-struct HipCallTable { const char* name[48]; uint64_t n[48]; int used; };
-thread_local HipCallTable hip_calls{};
-void note_hip_call(const char* name)
-{
-    for (int i = 0; i < hip_calls.used; ++i)
-        if (std::strcmp(hip_calls.name[i], name) == 0) { ++hip_calls.n[i]; return; }
-    if (hip_calls.used < 48) { hip_calls.name[hip_calls.used] = name; hip_calls.n[hip_calls.used++] = 1; }
-}
-}  // namespace
-}  // namespace aidax
-#define AIDAX_COUNTED(fn, ...) (aidax::note_hip_call(#fn), ::fn(__VA_ARGS__))
-#define hipSetDevice(...) AIDAX_COUNTED(hipSetDevice, __VA_ARGS__)
-#define hipMalloc(...) AIDAX_COUNTED(hipMalloc, __VA_ARGS__)
-#define hipHostMalloc(...) AIDAX_COUNTED(hipHostMalloc, __VA_ARGS__)
-#define hipHostRegister(...) AIDAX_COUNTED(hipHostRegister, __VA_ARGS__)
-#define hipEventCreateWithFlags(...) AIDAX_COUNTED(hipEventCreateWithFlags, __VA_ARGS__)
-#define hipStreamCreateWithFlags(...) AIDAX_COUNTED(hipStreamCreateWithFlags, __VA_ARGS__)
-#define hipStreamCreateWithPriority(...) AIDAX_COUNTED(hipStreamCreateWithPriority, __VA_ARGS__)
-#define hipFree(...) AIDAX_COUNTED(hipFree, __VA_ARGS__)
-#define hipHostFree(...) AIDAX_COUNTED(hipHostFree, __VA_ARGS__)
-#define hipHostUnregister(...) AIDAX_COUNTED(hipHostUnregister, __VA_ARGS__)
-#define hipEventDestroy(...) AIDAX_COUNTED(hipEventDestroy, __VA_ARGS__)
-#define hipStreamDestroy(...) AIDAX_COUNTED(hipStreamDestroy, __VA_ARGS__)
-#define hipStreamSynchronize(...) AIDAX_COUNTED(hipStreamSynchronize, __VA_ARGS__)
-#define hipEventSynchronize(...) AIDAX_COUNTED(hipEventSynchronize, __VA_ARGS__)
-#define hipDeviceSynchronize(...) AIDAX_COUNTED(hipDeviceSynchronize, __VA_ARGS__)
-#define hipMemcpy(...) AIDAX_COUNTED(hipMemcpy, __VA_ARGS__)
-#define hipMemcpyAsync(...) AIDAX_COUNTED(hipMemcpyAsync, __VA_ARGS__)
-#define hipMemsetAsync(...) AIDAX_COUNTED(hipMemsetAsync, __VA_ARGS__)
-#define hipEventRecord(...) AIDAX_COUNTED(hipEventRecord, __VA_ARGS__)
-#define hipEventQuery(...) AIDAX_COUNTED(hipEventQuery, __VA_ARGS__)
-#define hipStreamWaitEvent(...) AIDAX_COUNTED(hipStreamWaitEvent, __VA_ARGS__)
-#define hipStreamWriteValue32(...) AIDAX_COUNTED(hipStreamWriteValue32, __VA_ARGS__)
-#define launch_ir_append(...) (aidax::note_hip_call("launch_ir_append"), aidax::launch_ir_append(__VA_ARGS__))
-#define launch_ir_conv(...) (aidax::note_hip_call("launch_ir_conv"), aidax::launch_ir_conv(__VA_ARGS__))
-#define launch_ir_fade(...) (aidax::note_hip_call("launch_ir_fade"), aidax::launch_ir_fade(__VA_ARGS__))
-#endif
 
 using namespace aidax;
 
@@ -289,32 +245,6 @@ struct KeepWarm {
 };
 KeepWarm& keep_warm() { static KeepWarm k; return k; }
 
-struct HipFail : std::runtime_error { using std::runtime_error::runtime_error; };
-
-inline void hip_check(hipError_t e, const char* what)
-{
-    if (e != hipSuccess) {
-        std::ostringstream os;
-        os << what << ": " << hipGetErrorString(e);
-        throw HipFail(os.str());
-    }
-}
-#define HIP_TRY(x) hip_check((x), #x)
-
-template <class F>
-int guarded(F&& f)
-{
-    try {
-        return f();
-    } catch (const HipFail& e) {
-        return fail(AIDAX_ERR_DEVICE, e.what());
-    } catch (const std::exception& e) {
-        return fail(AIDAX_ERR_STATE, e.what());
-    } catch (...) {
-        return fail(AIDAX_ERR_STATE, "unknown failure");
-    }
-}
-
 // The device side of one loaded model: what the reference keeps in a DynamicModel (rt-neural-generic.h:115-129)
 // minus the per-stream members. A pool plays `cur`; aidax_pool_prepare_model builds the next one on the worker
 // thread and aidax_pool_commit_model swaps the two on the audio thread (plain struct assignment).
@@ -352,42 +282,7 @@ struct ModelSlot {
     float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
 };
 
-// A pool's cabinet IR (aidax_pool_prepare_ir / aidax_pool_commit_ir): its A fragments for k_ir_conv, swapped in and out like a model.
-struct IrSlot {
-    uint32_t* d_frag = nullptr;      // nullptr: no IR
-    uint32_t n_taps = 0, n_diag = 0;
-    uint64_t gen = 0;                // which committed content this is (a number per commit, given by the commit; 0: none): the IR fade's identity of an IR
-};
 constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
-
-// ... and the stage's history, allocated by the first aidax_pool_prepare_ir / aidax_pool_prepare_ir_slot and fed by every pass from then
-// on (k_ir_append): per stream a ring of the last R >= capacity + max_frames dry samples (aidax_kernels.h: IrArgs), and the K split's partial
-// sums (aidax_ir_mfma.hip). With it, the device copy of the plan (the IR items k_ir_conv runs: [plan_items_cap] IrItem, then the stream
-// lists) and the pinned snapshots it is uploaded from, stream-ordered with the passes like the control records (flush_ctl).
-struct IrHistory {
-    float* ring = nullptr;
-    float* part = nullptr;
-    uint32_t ring_row = 0, mask = 0, split_cap = 1;
-    uint8_t* d_plan = nullptr;
-    uint8_t* h_plan[kCtlRing] = {};
-    hipEvent_t plan_ev[kCtlRing] = {};
-    bool plan_used[kCtlRing] = {};
-    int plan_next = 0;                   // (audio side)
-    float* side = nullptr;               // the IR fade's side buffer, [n_streams][max_frames]: what the fade-out section of a fade pass convolves into
-};
-void free_ir_history(IrHistory* h)
-{
-    if (!h) return;
-    if (h->ring) (void)hipFree(h->ring);
-    if (h->part) (void)hipFree(h->part);
-    if (h->d_plan) (void)hipFree(h->d_plan);
-    if (h->side) (void)hipFree(h->side);
-    for (int k = 0; k < kCtlRing; ++k) {
-        if (h->h_plan[k]) (void)hipHostFree(h->h_plan[k]);
-        if (h->plan_ev[k]) (void)hipEventDestroy(h->plan_ev[k]);
-    }
-    delete h;
-}
 constexpr size_t kStagingLimit = size_t(64) << 20;      // pinned staging per direction for aidax_pool_process
 constexpr size_t kZeroCopyLimit = size_t(64) << 10;     // blocks up to this size are read / written by the kernels in place in pinned host memory
 
@@ -456,157 +351,16 @@ struct aidax_pool {
         lp_off.store(true, std::memory_order_relaxed);
         lp_faults.fetch_add(1, std::memory_order_relaxed);
         // the wrong block is in the IR history: clear it, so that it does not sound through the IR's tail (behind every pass issued so far)
-        if (IrHistory* h = ir_history()) {
+        if (ir.adopt()) {
             if (last_stream && last_stream != q && hipEventRecord(ev_x, last_stream) == hipSuccess) (void)hipStreamWaitEvent(q, ev_x, 0);
             last_stream = q;
-            (void)hipMemsetAsync(h->ring, 0, sizeof(float) * n_streams * static_cast<size_t>(h->ring_row), q);
+            ir.clear_all(q);
         }
         return true;
     }
 
-    // The cabinet IR stage: the pool IR and the bank (d_frag == nullptr: empty), and the history, which the worker side publishes once
-    // (the first prepare of either kind) and the audio side picks up at its next call; the ring slot of the next pass's first frame.
-    IrSlot ir;
-    IrSlot bank[AIDAX_IR_SLOTS];
-    std::atomic<IrHistory*> ir_hist_pub{nullptr};
-    IrHistory* ir_hist = nullptr;
-    uint32_t ir_pos = 0;
-    // the longest IR the pool takes (aidax_pool_set_ir_capacity, set-up side: fixed once the first prepare has sized the history with it)
-    std::atomic<uint32_t> ir_capacity{kIrMaxTaps};
-    IrHistory* ir_history()
-    {
-        if (!ir_hist) ir_hist = ir_hist_pub.load(std::memory_order_acquire);
-        return ir_hist;
-    }
-    // Which IR each stream's output goes through (AIDAX_IR_POOL, AIDAX_IR_NONE or a bank slot), and the plan built from it on the audio
-    // side whenever an assignment or a commit has changed it: the streams grouped by IR into items of up to 64, the IRs in order (pool IR,
-    // slot 0, 1, ...), each IR's streams in stream order. One IR for every stream gives the identity plan (item i: streams 64 i ..).
-    // Host memory sized at creation; the device copy lives in the history (IrHistory::d_plan).
-    std::vector<int32_t> ir_assign;
-    std::vector<IrItem> plan_items;          // [ceil(n_streams / 64) + 65]
-    std::vector<uint32_t> plan_streams;      // [n_streams]
-    uint32_t plan_n_items = 0, plan_n_listed = 0, plan_max_diag = 0;
-    bool plan_identity = false, plan_dirty = true;
-    size_t plan_items_bytes() const { return plan_items.size() * sizeof(IrItem); }
-    // The IR fade (aidax_pool_set_ir_fade; 0: off). Every commit gives its content a generation number, and a stream records the
-    // (key, generation) of the IR it went through in the last pass issued (key as ir_key; -1 / 0: none). A rebuild of the plan that finds
-    // another one in force for a stream adds the stream to the plan's second section, the fade-out items: the old IRs (still in the bank,
-    // or parked, see aidax_pool_commit_ir) with the streams fading from them, grouped like the main section, and to the mix list
-    // (k_ir_fade: stream index, kIrFadeDry set where the old side is the dry block). That section serves the one pass it was built for.
-    // Device and snapshot layout behind the main section: fade items at fade_items_off(), their stream lists, the mix list.
-    uint32_t ir_fade = 0;
-    IrSlot ir_parked[AIDAX_IR_SLOTS + 1];        // per key: the content retired last, kept for the streams that still fade from it
-    uint64_t ir_gen_next = 1;
-    uint64_t ir_pass_seq = 0;                    // passes issued through the IR stage
-    bool any_pass = false;                       // the pool has issued a pass of n_frames > 0 (its first one has nothing to fade from)
-    uint64_t ir_commit_seq[AIDAX_IR_SLOTS + 1] = {};   // ... when the key's content was committed: smaller than ir_pass_seq = it has been played
-    std::vector<int8_t> played_key;              // [n_streams]
-    std::vector<uint64_t> played_gen;            // [n_streams]
-    std::vector<IrItem> fade_items;              // [ceil(n_streams / 64) + 2 * 65]
-    std::vector<uint32_t> fade_streams, fade_mix;    // [n_streams] each
-    std::vector<int16_t> fade_src;               // [n_streams]: scratch of build_ir_fade
-    uint32_t fade_n_items = 0, fade_n_listed = 0, fade_n_mix = 0, fade_max_diag = 0;
-    size_t fade_items_off() const { return (plan_items_bytes() + sizeof(uint32_t) * n_streams + 7u) & ~size_t(7); }
-    size_t fade_streams_off() const { return fade_items_off() + fade_items.size() * sizeof(IrItem); }
-    size_t fade_mix_off() const { return fade_streams_off() + sizeof(uint32_t) * n_streams; }
-    size_t plan_bytes() const { return fade_mix_off() + sizeof(uint32_t) * n_streams; }
-    const IrSlot& ir_slot_of(int k) const { return k == 0 ? ir : bank[k - 1]; }
-    // the fade-out section for the pass about to be issued (behind build_ir_plan, same rebuild), and every stream's record brought up to
-    // that pass. `fade`: a fade length is set (and this is not the pool's first pass); without, the streams switch as they always did.
-    // A stream whose old IR is held nowhere any more (neither in the bank nor parked: it was retired under a fade length of 0) switches
-    // without a fade too.
-    void build_ir_fade(bool fade)
-    {
-        constexpr int kSources = 2 * (AIDAX_IR_SLOTS + 1);              // 0 .. 64: the bank's content, 65 .. 129: the parked one
-        uint32_t count[kSources] = {}, at[kSources];
-        fade_n_items = fade_n_listed = fade_n_mix = fade_max_diag = 0;
-        for (uint32_t s = 0; s < n_streams; ++s) {
-            const int nk = ir_key(s);
-            const uint64_t ng = nk >= 0 ? ir_slot_of(nk).gen : 0;
-            const int ok = played_key[s];
-            const uint64_t og = played_gen[s];
-            fade_src[s] = -2;                                          // no fade
-            played_key[s] = static_cast<int8_t>(nk);
-            played_gen[s] = ng;
-            if (!fade || (nk == ok && ng == og)) continue;
-            if (ok < 0) fade_src[s] = -1;                              // from the dry block
-            else if (ir_slot_of(ok).d_frag && ir_slot_of(ok).gen == og) fade_src[s] = static_cast<int16_t>(ok);
-            else if (ir_parked[ok].d_frag && ir_parked[ok].gen == og) fade_src[s] = static_cast<int16_t>(AIDAX_IR_SLOTS + 1 + ok);
-            if (fade_src[s] >= 0) ++count[fade_src[s]];
-            if (fade_src[s] >= -1) fade_mix[fade_n_mix++] = s | (fade_src[s] < 0 ? kIrFadeDry : 0u);
-        }
-        if (fade_n_mix == 0) return;
-        uint32_t first = 0;
-        for (int k = 0; k < kSources; ++k) { at[k] = first; first += count[k]; }
-        fade_n_listed = first;
-        for (uint32_t s = 0; s < n_streams; ++s)
-            if (fade_src[s] >= 0) fade_streams[at[fade_src[s]]++] = s;
-        first = 0;
-        for (int k = 0; k < kSources; ++k) {
-            const IrSlot& sl = k <= AIDAX_IR_SLOTS ? ir_slot_of(k) : ir_parked[k - AIDAX_IR_SLOTS - 1];
-            for (uint32_t c = 0; c < count[k]; c += kIrItemStreams)
-                fade_items[fade_n_items++] = IrItem{ sl.d_frag, sl.n_diag, std::min(kIrItemStreams, count[k] - c), first + c, 0u };
-            if (count[k]) fade_max_diag = std::max(fade_max_diag, sl.n_diag);
-            first += count[k];
-        }
-    }
-    int ir_key(uint32_t s) const                 // 0: the pool IR, 1 + j: bank slot j, -1: none (also an empty slot)
-    {
-        const int32_t a = ir_assign[s];
-        if (a == AIDAX_IR_POOL) return ir.d_frag ? 0 : -1;
-        return a >= 0 && bank[a].d_frag ? 1 + a : -1;
-    }
-    void build_ir_plan()
-    {
-        uint32_t count[AIDAX_IR_SLOTS + 1] = {}, at[AIDAX_IR_SLOTS + 1];
-        for (uint32_t s = 0; s < n_streams; ++s) {
-            const int k = ir_key(s);
-            if (k >= 0) ++count[k];
-        }
-        uint32_t first = 0;
-        for (int k = 0; k <= AIDAX_IR_SLOTS; ++k) { at[k] = first; first += count[k]; }
-        plan_n_listed = first;
-        for (uint32_t s = 0; s < n_streams; ++s) {
-            const int k = ir_key(s);
-            if (k >= 0) plan_streams[at[k]++] = s;
-        }
-        plan_n_items = 0; plan_max_diag = 0; plan_identity = false;
-        first = 0;
-        for (int k = 0; k <= AIDAX_IR_SLOTS; ++k) {
-            const IrSlot& sl = k == 0 ? ir : bank[k - 1];
-            for (uint32_t c = 0; c < count[k]; c += kIrItemStreams)
-                plan_items[plan_n_items++] = IrItem{ sl.d_frag, sl.n_diag, std::min(kIrItemStreams, count[k] - c), first + c, 0u };
-            if (count[k]) plan_max_diag = std::max(plan_max_diag, sl.n_diag);
-            if (count[k] == n_streams) plan_identity = true;
-            first += count[k];
-        }
-        plan_dirty = false;
-    }
-    // a dirty plan rebuilt and uploaded, stream-ordered with the passes that follow: the passes already issued keep the plan they were
-    // issued with (the device copy is overwritten behind them, from a pinned snapshot that no later rebuild touches while it is in flight)
-    void flush_ir_plan(IrHistory* h, hipStream_t s)
-    {
-        if (!plan_dirty) return;
-        build_ir_plan();
-        build_ir_fade(any_pass && ir_fade != 0);
-        const int k = h->plan_next;
-        if (h->plan_used[k] && hipEventQuery(h->plan_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(h->plan_ev[k]));   // four rebuilds behind
-        std::memcpy(h->h_plan[k], plan_items.data(), plan_n_items * sizeof(IrItem));
-        std::memcpy(h->h_plan[k] + plan_items_bytes(), plan_streams.data(), plan_n_listed * sizeof(uint32_t));
-        size_t bytes = plan_items_bytes() + plan_n_listed * sizeof(uint32_t);
-        if (fade_n_mix) {
-            // the fade-out section rides in the same upload: one copy up to the end of the mix list. It also carries the snapshot's gaps
-            // (stream-list entries past plan_n_listed, items past fade_n_items), which no kernel reads: the counts travel as arguments
-            std::memcpy(h->h_plan[k] + fade_items_off(), fade_items.data(), fade_n_items * sizeof(IrItem));
-            std::memcpy(h->h_plan[k] + fade_streams_off(), fade_streams.data(), fade_n_listed * sizeof(uint32_t));
-            std::memcpy(h->h_plan[k] + fade_mix_off(), fade_mix.data(), fade_n_mix * sizeof(uint32_t));
-            bytes = fade_mix_off() + fade_n_mix * sizeof(uint32_t);
-        }
-        HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(h->plan_ev[k], s));
-        h->plan_used[k] = true;
-        h->plan_next = (k + 1) % kCtlRing;
-    }
+    IrStage ir;                      // the cabinet IR stage behind every pass (aidax_ir_stage.h)
+    bool any_pass = false;           // the pool has issued a pass of n_frames > 0 (its first one has nothing for an IR change to fade from)
 
     // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
     // block k and the download of the blocks in front of it run under the pass of block k (allocated by the first submit).
@@ -911,18 +665,7 @@ struct aidax_pool {
     }
     void release()
     {
-        if (ir.d_frag) (void)hipFree(ir.d_frag);
-        ir = IrSlot{};
-        for (IrSlot& b : bank) {
-            if (b.d_frag) (void)hipFree(b.d_frag);
-            b = IrSlot{};
-        }
-        for (IrSlot& b : ir_parked) {
-            if (b.d_frag) (void)hipFree(b.d_frag);
-            b = IrSlot{};
-        }
-        free_ir_history(ir_hist_pub.exchange(nullptr));
-        ir_hist = nullptr;
+        ir.release();
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);
         if (cur.d_nn) (void)hipFree(cur.d_nn);
@@ -1201,59 +944,13 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         a.n_streams = n_active;
         // with an IR history the pass ends behind the IR stage: its end marker (the submit path's event, the blocking path's completion
         // word) is not handed to the model's launch but issued after the stage by the caller
-        IrHistory* ih = n_frames != 0 ? p->ir_history() : nullptr;
-        if (ih) { p->pass_done = nullptr; p->pass_word = nullptr; }
-        // a fade-out section serves this pass alone: spent when the pass has been issued, and dropped when issuing it fails (the streams
-        // then switch; a later pass, with another n_frames and ring position, must not run it)
-        struct FadeSpent {
-            aidax_pool* p;
-            ~FadeSpent() { if (p) p->fade_n_items = p->fade_n_listed = p->fade_n_mix = 0; }
-        } fade_spent{ ih ? p : nullptr };
-        if (ih) p->flush_ir_plan(ih, s);                               // the plan this pass is issued with, ahead of it
-        HIP_TRY(p->launch(p->cur, a, s));
-        if (ih) {
-            // the IR stage (aidax_ir_mfma.hip): the block's dry samples into the history (also while no IR is live), then the convolution
-            // over the history, in place on d_out, of the streams the plan holds (one launch whatever the number of IRs)
-            HIP_TRY(launch_ir_append(ih->ring, ih->ring_row, ih->mask, p->ir_pos, d_out, n_active, n_frames, s));
-            if (p->plan_n_items) {
-                IrArgs ia{};
-                ia.items = reinterpret_cast<const IrItem*>(ih->d_plan);
-                ia.streams = reinterpret_cast<const uint32_t*>(ih->d_plan + p->plan_items_bytes());
-                // the identity plan over the prefix only: the grid of a one-IR pool (entries at or beyond n_active are skipped anyway)
-                ia.n_items = p->plan_identity ? std::min(p->plan_n_items, (n_active + kIrItemStreams - 1) / kIrItemStreams) : p->plan_n_items;
-                ia.n_listed = p->plan_identity ? n_active : p->plan_n_listed;
-                ia.ring = ih->ring; ia.out = d_out; ia.part = ih->part;
-                ia.ring_row = ih->ring_row; ia.mask = ih->mask; ia.pos = p->ir_pos;
-                ia.n_streams = n_active; ia.n_frames = n_frames;
-                ia.n_splits = ir_k_splits(ia.n_items, n_frames, p->plan_max_diag, p->cus, ih->split_cap);
-                HIP_TRY(launch_ir_conv(ia, s));
-            }
-            if (p->fade_n_mix) {
-                // an IR change since the last pass: the old IRs over the same history into the side buffer (the fade-out section: the
-                // same kernel, K split and fixed-order reduce, `part` reused behind the main section's reduce), then the crossfade of the
-                // first min(F, n_frames) frames in place on d_out. This pass only (fade_spent).
-                if (p->fade_n_items) {
-                    IrArgs fa{};
-                    fa.items = reinterpret_cast<const IrItem*>(ih->d_plan + p->fade_items_off());
-                    fa.streams = reinterpret_cast<const uint32_t*>(ih->d_plan + p->fade_streams_off());
-                    fa.n_items = p->fade_n_items; fa.n_listed = p->fade_n_listed;
-                    fa.ring = ih->ring; fa.out = ih->side; fa.part = ih->part;
-                    fa.ring_row = ih->ring_row; fa.mask = ih->mask; fa.pos = p->ir_pos;
-                    fa.n_streams = n_active; fa.n_frames = n_frames;
-                    fa.n_splits = ir_k_splits(fa.n_items, n_frames, p->fade_max_diag, p->cus, ih->split_cap);
-                    HIP_TRY(launch_ir_conv(fa, s));
-                }
-                IrFadeArgs fm{};
-                fm.mix = reinterpret_cast<const uint32_t*>(ih->d_plan + p->fade_mix_off());
-                fm.side = ih->side; fm.ring = ih->ring; fm.out = d_out;
-                fm.n_mix = p->fade_n_mix; fm.ring_row = ih->ring_row; fm.mask = ih->mask; fm.pos = p->ir_pos;
-                fm.n_streams = n_active; fm.n_frames = n_frames;
-                fm.lf = std::min(p->ir_fade, n_frames);
-                HIP_TRY(launch_ir_fade(fm, s));
-            }
-            ++p->ir_pass_seq;
-            p->ir_pos = (p->ir_pos + n_frames) & ih->mask;
+        const bool ir_on = n_frames != 0 && p->ir.adopt();
+        if (ir_on) {
+            p->pass_done = nullptr; p->pass_word = nullptr;
+            p->ir.begin_pass(s, p->any_pass);                          // the plan this pass is issued with, ahead of it
         }
+        HIP_TRY(p->launch(p->cur, a, s));
+        if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
@@ -1359,15 +1056,7 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
                 HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->ctl_ring[k]), sizeof(StreamCtl) * n_streams, hipHostMallocDefault));
                 HIP_TRY(hipEventCreateWithFlags(&p->ctl_ev[k], hipEventDisableTiming));
             }
-            p->ir_assign.assign(n_streams, AIDAX_IR_POOL);
-            p->plan_items.resize((n_streams + kIrItemStreams - 1) / kIrItemStreams + AIDAX_IR_SLOTS + 1);
-            p->plan_streams.resize(n_streams);
-            p->played_key.assign(n_streams, -1);
-            p->played_gen.assign(n_streams, 0);
-            p->fade_items.resize((n_streams + kIrItemStreams - 1) / kIrItemStreams + 2 * (AIDAX_IR_SLOTS + 1));
-            p->fade_streams.resize(n_streams);
-            p->fade_mix.resize(n_streams);
-            p->fade_src.resize(n_streams);
+            p->ir.init(n_streams, max_frames, p->cus, p->wq);
             p->controls.resize(n_streams);
             for (auto& c : p->controls) aidax_controls_default(&c);
             p->loading.assign(n_streams, 1);
@@ -1433,15 +1122,14 @@ AIDAX_API int aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int star
     return rc;
 }
 
-// The cabinet IR, split between the threads like a model swap. Worker: the history on first use (allocated, zeroed, published), the IR's
-// fragments packed and uploaded on the worker stream. Audio thread: a swap of two host records behind an event — no allocation, no free, no wait.
+// The cabinet IR, split between the threads like a model swap (IrStage::prepare on the worker, IrStage::commit on the audio thread).
 static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
 {
     if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
     *out = nullptr;
     if (slot != AIDAX_IR_POOL && (slot < 0 || slot >= AIDAX_IR_SLOTS)) return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
     if (taps) {
-        const uint32_t capacity = p->ir_capacity.load(std::memory_order_relaxed);
+        const uint32_t capacity = p->ir.capacity.load(std::memory_order_relaxed);
         if (n_taps == 0 || n_taps > capacity)
             return fail(AIDAX_ERR_ARG, "IR length must be 1 .. " + std::to_string(capacity) + " taps" + (capacity != kIrMaxTaps ? " (the pool's IR capacity)" : ""));
         for (uint32_t k = 0; k < n_taps; ++k)
@@ -1457,37 +1145,7 @@ static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint3
         sg->is_ir = true;
         sg->ir_slot = slot;
         HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
-        if (!p->ir_hist_pub.load(std::memory_order_acquire)) {
-            std::unique_ptr<IrHistory, void (*)(IrHistory*)> h(new IrHistory(), free_ir_history);
-            uint32_t R = 1;
-            while (R < p->ir_capacity.load(std::memory_order_relaxed) + p->max_frames) R <<= 1;
-            h->mask = R - 1;
-            h->ring_row = R + kIrMirror;
-            const size_t block = static_cast<size_t>(p->n_streams) * p->max_frames;
-            const size_t budget = size_t(16) << 20;              // floats of partial sums (64 MiB)
-            h->split_cap = static_cast<uint32_t>(std::max<size_t>(1, std::min<size_t>(64, budget / block)));
-            const size_t ring_bytes = sizeof(float) * p->n_streams * static_cast<size_t>(h->ring_row);
-            HIP_TRY(hipMalloc(&h->ring, ring_bytes));
-            if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
-            HIP_TRY(hipMalloc(&h->side, sizeof(float) * block));
-            const size_t plan_bytes = p->plan_bytes();           // both sections, whether a fade length is set or not
-            HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
-            for (int k = 0; k < kCtlRing; ++k) {
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_plan[k]), plan_bytes, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&h->plan_ev[k], hipEventDisableTiming));
-            }
-            HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, p->wq));
-            HIP_TRY(hipStreamSynchronize(p->wq));
-            p->ir_hist_pub.store(h.release(), std::memory_order_release);
-        }
-        if (taps) {
-            aidax::IrSlot& ir = sg->ir;
-            const std::vector<uint32_t> frag = pack_ir_fragments(taps, n_taps, &ir.n_diag);
-            ir.n_taps = n_taps;
-            HIP_TRY(hipMalloc(&ir.d_frag, frag.size() * sizeof(uint32_t)));
-            HIP_TRY(hipMemcpyAsync(ir.d_frag, frag.data(), frag.size() * sizeof(uint32_t), hipMemcpyHostToDevice, p->wq));
-            HIP_TRY(hipStreamSynchronize(p->wq));               // `frag` is pageable; the audio side must find the IR complete
-        }
+        p->ir.prepare(taps, n_taps, sg->ir);
         *out = sg.release();
         return AIDAX_OK;
     });
@@ -1516,19 +1174,8 @@ AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
         p->enter_stream(p->q);
-        HIP_TRY(hipEventRecord(staged->fence, p->q));          // the retired fragments are free once the passes before this point have run
+        p->ir.commit(staged->ir_slot, staged->ir, staged->fence, p->q);
         staged->fenced = true;
-        const int key = staged->ir_slot == AIDAX_IR_POOL ? 0 : 1 + staged->ir_slot;
-        staged->ir.gen = staged->ir.d_frag ? p->ir_gen_next++ : 0;
-        std::swap(key == 0 ? p->ir : p->bank[key - 1], staged->ir);
-        // With a fade length set, content that has been played (a pass was issued since its commit) is parked for the streams that will
-        // fade from it in the next pass, and `staged` gets what was parked before: an IR retired one commit earlier, whose last possible
-        // use, a fade pass, precedes the fence above. Content that was never played has no stream to fade from it: it goes to `staged`
-        // as ever, and what is parked (which streams may still have played) stays.
-        if (p->ir_fade != 0 && p->ir_commit_seq[key] != p->ir_pass_seq) std::swap(p->ir_parked[key], staged->ir);
-        p->ir_commit_seq[key] = p->ir_pass_seq;
-        p->plan_dirty = true;                                  // every stream of that IR switches at this block boundary
-        (void)p->ir_history();
         return AIDAX_OK;
     });
 }
@@ -1561,9 +1208,10 @@ AIDAX_API int aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot)
         return fail(AIDAX_ERR_ARG, "stream out of range");
     if (slot != AIDAX_IR_POOL && slot != AIDAX_IR_NONE && (slot < 0 || slot >= AIDAX_IR_SLOTS))
         return fail(AIDAX_ERR_ARG, "IR slot must be the pool IR (-1), none (-2) or 0 .. 63");
-    if (stream == AIDAX_ALL_STREAMS) std::fill(p->ir_assign.begin(), p->ir_assign.end(), slot);
-    else p->ir_assign[stream] = slot;
-    p->plan_dirty = true;
+    IrPlan& plan = p->ir.plan;
+    if (stream == AIDAX_ALL_STREAMS) std::fill(plan.assign.begin(), plan.assign.end(), slot);
+    else plan.assign[stream] = slot;
+    plan.dirty = true;
     return AIDAX_OK;
 }
 
@@ -1572,11 +1220,11 @@ AIDAX_API int aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames)
 {
     if (frames > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR fade length must be 0 .. 8192 frames");
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
-    p->ir_fade = frames;
+    p->ir.plan.fade = frames;
     return AIDAX_OK;
 }
 
-AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir_fade : 0; }
+AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir.plan.fade : 0; }
 
 // Set-up side: a host record that the first prepare reads when it sizes the history ring (R >= capacity + max_frames); the kernels take
 // the ring's mask and row, and every IR's diagonal count, at run time.
@@ -1584,19 +1232,19 @@ AIDAX_API int aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps)
 {
     if (max_taps < kIrMaxTaps || max_taps > AIDAX_IR_MAX_CAPACITY) return fail(AIDAX_ERR_ARG, "IR capacity must be 8192 .. 65536 taps");
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
-    if (p->ir_hist_pub.load(std::memory_order_acquire))
+    if (p->ir.has_history())
         return fail(AIDAX_ERR_STATE, "IR capacity is fixed once the first aidax_pool_prepare_ir / _ir_slot has allocated the history");
-    p->ir_capacity.store(max_taps, std::memory_order_relaxed);
+    p->ir.capacity.store(max_taps, std::memory_order_relaxed);
     return AIDAX_OK;
 }
 
-AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p) { return p ? p->ir_capacity.load(std::memory_order_relaxed) : 0; }
+AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p) { return p ? p->ir.capacity.load(std::memory_order_relaxed) : 0; }
 
 AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
 {
     if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
     if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
-    *slot = p->ir_assign[stream];
+    *slot = p->ir.plan.assign[stream];
     return AIDAX_OK;
 }
 
@@ -1610,6 +1258,7 @@ AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_
 // `buf` (NUL-terminated, cut at `cap` bytes); returns the number of entry points listed and starts the count afresh.
 AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap)
 {
+    HipCallTable& hip_calls = hip_call_table();
     size_t at = 0;
     if (buf && cap) buf[0] = '\0';
     for (int i = 0; i < hip_calls.used; ++i)
@@ -1639,8 +1288,7 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
         p->enter_stream(p->q);
         const ModelSlot& m = p->cur;
         HIP_TRY(launch_init_streams(p->d_st + stream, 1, p->q));      // instantiate(), :283-321
-        if (IrHistory* h = p->ir_history())                            // a fresh instance has no past for the IR to sound
-            HIP_TRY(hipMemsetAsync(h->ring + static_cast<size_t>(stream) * h->ring_row, 0, sizeof(float) * h->ring_row, p->q));
+        p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st + stream, p_targets[0], p_targets[1], p->q));
         if (m.has_model) {
             // a fresh DynamicModel for this stream only: the launch arguments view the pool as one stream

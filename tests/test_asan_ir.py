@@ -1,4 +1,5 @@
-"""The host side of the cabinet IR stage (aidax_ir.cpp: aidax_ir_resample, the fragment packer at 65536 taps) under AddressSanitizer +
+"""The host side of the cabinet IR stage (aidax_ir.cpp: aidax_ir_resample, the fragment packer at 65536 taps, and IrPlan, the stage's plan
+builder, against a restatement of its rules over seeded random assignments, commits and passes) under AddressSanitizer +
 UndefinedBehaviorSanitizer: `make asan_ir` builds tests/asan_ir_harness.cpp with the product's own sources. CPU suite only, like
 tests/test_asan.py."""
 import os
@@ -15,3 +16,4 @@ def test_ir_resample_and_the_packer_under_sanitizers():
     assert "AddressSanitizer" not in r.stderr and "runtime error" not in r.stderr and "LeakSanitizer" not in r.stderr, r.stderr[-6000:]
     assert r.returncode == 0, (r.returncode, r.stdout[-1000:], r.stderr[-3000:])
     assert "0 failures" in r.stdout and int(r.stdout.split("asan_ir_harness:")[1].split("resample")[0]) > 500, r.stdout
+    assert int(r.stdout.split("checksum")[1].split(",")[1].split("plan rebuilds")[0]) > 1000, r.stdout

@@ -1,5 +1,5 @@
 """Per-stream cabinet IRs (GPU, -m gpu): the IR bank of a pool, aidax_pool_assign_ir and the plan that groups the streams by IR into the
-work items of one k_ir_conv launch (aidax_pool.cpp, aidax_ir_mfma.hip).
+work items of one k_ir_conv launch (IrPlan in aidax_ir.cpp, IrStage in aidax_ir_stage.cpp, aidax_ir_mfma.hip).
 
 The exact tests use the families of tests/irdata.py, on which the correct output is the true convolution to the last bit whatever the
 order of the additions, the K split or the reduce; every stream is compared with np.array_equal against the exact convolution of ITS OWN

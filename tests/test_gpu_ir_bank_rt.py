@@ -1,7 +1,7 @@
 """Per-stream IRs in real time (GPU, -m gpu): aidax_pool_assign_ir and the commit of a prepared bank slot, called on the audio thread,
 allocate, free and wait for nothing, and neither do the passes that follow them (include/aidax.h, "Threads"). Counted by the test build's
-per-thread table of the pool's own HIP runtime calls (aidax_test_hip_calls, aidax_pool.cpp: every call site of every entry point the pool
-uses, checked or not, and the IR stage's launchers). The shipped library has no such table: these tests run on the test build only."""
+per-thread table of the pool's own HIP runtime calls (aidax_test_hip_calls, aidax_hip_host.h: every call site of every entry point the pool
+and its IR stage use, checked or not, and the IR stage's launchers). The shipped library has no such table: these tests run on the test build only."""
 import ctypes as C
 import importlib
 
