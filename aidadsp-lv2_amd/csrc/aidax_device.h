@@ -105,10 +105,19 @@ __device__ __forceinline__ float sigmoid_pre(float v_scaled)
     return __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(v_scaled));
 }
 
+// A THIRD sigmoid has no function of its own: 0.5 * tanh_rat(v / 2) + 0.5, written fma(tanh_rat(acc), ka, kb) on a row the packer
+// scaled by 0.5. It serves where the lanes of one instruction hold different gates and the candidate's tanh_rat has to be evaluated
+// anyway — LstmCell's shared lane maps (aidax_kernels.hip: S = 4, up to 16 units, for i, f and o; S = 2, up to 32 units, for o)
+// and k_lstm_q4 (aidax_q4.hip) — with (ka, kb) = (1, 0) on the candidate's lanes and (0.5, 0.5) on a gate's. Absolutely accurate to
+// 1.9e-7 (fp32 emulation of the coefficients below); relatively it is not: below v = -15.8 (tanh_rat's clamp, twice) it is exactly 0
+// where the exp forms still return 1e-7 and reach 0 only from v = -88 on, and just above that it moves in steps of 2^-25 = 3.0e-8.
+// Above v = 15.8 it is exactly 1, like the exp forms from v = 17 on. (Both ends hang on tanh_rat reaching +-1 at its clamp, see there.)
+// (tests/test_gpu_activations.py drives all three forms to both ends, on every kernel that uses them.)
+
 // tanh as an odd rational x*P(x^2)/Q(x^2), P of degree 6 and Q of degree 3 in x^2, fitted for
 // this kernel (scratch: Lawson-weighted least squares on [0,9], relative error 6.6e-9 in fp64).
 // In fp32 with FMAs: <= 3.6e-7 relative everywhere, exact odd symmetry, |y| <= 1 with the
-// clamp. The relative accuracy near 0 is the point: tanh = 2*sigmoid(2x)-1 on v_exp_f32 is
+// clamp, and exactly 1 at it. The relative accuracy near 0 is the point: tanh = 2*sigmoid(2x)-1 on v_exp_f32 is
 // only ABSOLUTELY accurate (1.2e-7), and an LSTM whose forget gate sits near 1 integrates
 // that error in c (measured 5.5e-6 after 2048 samples on tw40_british_lead vs 1.3e-6 with
 // this form; the reference's threshold is 1e-5, rt-neural-generic.h:182).
@@ -120,7 +129,14 @@ __device__ __forceinline__ float sigmoid_pre(float v_scaled)
 constexpr float kTanhP[7] = { 0.9999999933888696f, 0.13084010352004496f, 0.003103956503888039f, 1.1154311501654368e-05f,
                               -2.0225239996482085e-08f, 5.277955823366522e-11f, -8.488730763828322e-14f };      // P, ascending in x^2
 constexpr float kTanhQ[4] = { 1.0f, 0.46417337453820245f, 0.02449517952619233f, 0.00025461456545097517f };     // Q, ascending in x^2
-__device__ __forceinline__ float tanh_rat_clamp(float v) { return __builtin_fminf(__builtin_fmaxf(v, -7.9f), 7.9f); }     // (v_max + v_med3; a bare v_med3 lets a NaN through and is no faster)
+// The clamp is the FIRST float at which the FMA sequence below returns exactly 1 (swept on gfx950 over every float from 0.5 up: below
+// it the value stays under 1, the last one 1 - 2.4e-7; tanh itself is 1 - 2.7e-7 there, so the step is inside the bound above): a
+// saturated tanh is +-1 to the bit, as the reference's is from |x| = 9.01 on. It used to be 7.9, where the sequence ends at
+// 1 - 1.8e-7 — within the bound as well, but a cell with f = i = 1 that integrates a saturated candidate then falls 1.8e-7 short per
+// frame (3.3e-6 on |c| <= 8 after a climb to 40 and back), and the tanh-form sigmoid above sat at 1 - 1.2e-7 instead of 1: a
+// forget gate "at 1" of an LSTM-12 let c decay, 1.8e-4 after 80 frames at |c| ~ 40 (tests/test_gpu_activations.py, clamp family).
+constexpr float kTanhClamp = 0x1.f9b3c2p+2f;      // 7.90159655
+__device__ __forceinline__ float tanh_rat_clamp(float v) { return __builtin_fminf(__builtin_fmaxf(v, -kTanhClamp), kTanhClamp); }     // (v_max + v_med3; a bare v_med3 lets a NaN through and is no faster)
 __device__ __forceinline__ float tanh_rat(float v)
 {
     const float x = tanh_rat_clamp(v);
@@ -156,7 +172,9 @@ __device__ __forceinline__ float tanh_rat(float v)
 }
 
 // tanh for FEED-FORWARD layers (the conv1d stacks): 1 - 2 / (1 + e^(2x)) on v_exp_f32 / v_rcp_f32, five instructions
-// against fifteen for the rational. Absolutely accurate to ~1.2e-7, not relatively near 0 — which only matters where
+// against fifteen for the rational. Absolutely accurate, not relatively near 0: with one ulp each for v_exp_f32 and v_rcp_f32 and half an
+// ulp for the sum and for the last FMA, |error| <= 2^-23 (1.5 (1 - y) + (1 - y^2) / 2) + 2^-24 |y| at the true value y — 2.4e-7 around 0,
+// 6e-8 at +1, 4.2e-7 at -1; typically 1.2e-7 (tests/test_gpu_activations.py holds the GRU kernels to the bound) — which only matters where
 // a state integrates the error (the LSTM cell above); a conv stack has no such state, eight layers measured
 // 1.9e-7 against the oracle (tests/test_gpu_parity.py). Saturates cleanly: e -> inf gives 1, e -> 0 gives -1.
 __device__ __forceinline__ float tanh_exp(float v)
