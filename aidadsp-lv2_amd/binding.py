@@ -172,6 +172,26 @@ def lib() -> C.CDLL:
     L.aidax_pool_set_ir_capacity.argtypes = [vp, u32]
     L.aidax_pool_ir_capacity.argtypes = [vp]
     L.aidax_pool_ir_capacity.restype = u32
+    L.aidax_resampler_create.argtypes = [u32, C.c_double, C.c_double, u32, u32, u32, C.c_int, C.POINTER(vp)]
+    L.aidax_resampler_destroy.argtypes = [vp]
+    L.aidax_resampler_destroy.restype = None
+    L.aidax_resampler_row.argtypes = [C.c_double, C.c_double, u32, _fp, u32, C.POINTER(u32)]
+    L.aidax_resampler_process_device.argtypes = [vp, vp, u32, vp, u32, vp]
+    L.aidax_resampler_process.argtypes = [vp, _fp, u32, _fp, u32]
+    L.aidax_resampler_ready.argtypes = [vp]
+    L.aidax_resampler_ready.restype = u32
+    L.aidax_resampler_reset_stream.argtypes = [vp, u32]
+    L.aidax_pool_samplerate.argtypes = [vp]
+    L.aidax_pool_samplerate.restype = C.c_double
+    L.aidax_rate_create.argtypes = [vp, C.c_double, u32, C.POINTER(vp)]
+    L.aidax_rate_destroy.argtypes = [vp]
+    L.aidax_rate_destroy.restype = None
+    L.aidax_rate_latency_frames.argtypes = [vp]
+    L.aidax_rate_latency_frames.restype = u32
+    L.aidax_rate_latency.argtypes = [C.c_double, C.c_double, C.POINTER(u32)]
+    L.aidax_rate_process.argtypes = [vp, _fp, _fp, u32]
+    L.aidax_rate_process_device.argtypes = [vp, vp, vp, u32, vp]
+    L.aidax_rate_reset_stream.argtypes = [vp, u32]
     _lib = L
     return L
 
@@ -235,6 +255,22 @@ def load_ir_wav_for(pool: "Pool", path: str, lead: int = 0) -> np.ndarray:
     rate is taken as it is, behind `lead` zeros) and cut to the pool's IR capacity."""
     taps, sr = load_ir_wav(path)
     return resample_ir(taps, sr, pool.samplerate, lead, pool.ir_capacity())[0]
+
+
+def resampler_row(rate_in: float, rate_out: float, phase: int) -> np.ndarray:
+    """aidax_resampler_row: the T weights of row `phase` of the streaming resampler's filter (host only)"""
+    n = C.c_uint32(0)
+    _check(lib().aidax_resampler_row(rate_in, rate_out, phase, None, 0, C.byref(n)))
+    w = np.empty(n.value, np.float32)
+    _check(lib().aidax_resampler_row(rate_in, rate_out, phase, w.ctypes.data_as(_fp), n.value, C.byref(n)))
+    return w
+
+
+def rate_latency(host_rate: float, pool_rate: float) -> int:
+    """aidax_rate_latency: host frames of delay of a rate adapter between these rates (host only)"""
+    n = C.c_uint32(0)
+    _check(lib().aidax_rate_latency(host_rate, pool_rate, C.byref(n)))
+    return n.value
 
 
 def device_count() -> int:
@@ -496,6 +532,8 @@ class Pool:
 
     def close(self):
         if self.h:
+            for a in list(getattr(self, "_adapters", ())):      # a rate adapter borrows the pool: it goes first
+                a.close()
             lib().aidax_pool_destroy(self.h)
             self.h = C.c_void_p()
 
@@ -568,6 +606,103 @@ class Hub:
     def close(self):
         if self.h:
             lib().aidax_hub_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class Resampler:
+    """aidax_resampler: the streaming polyphase resampler for n_streams streams (rate_in -> rate_out, delays d_in / d_out in frames)."""
+
+    def __init__(self, n_streams: int, rate_in: float, rate_out: float, d_in: int = 0, d_out: int = 0, max_in_frames: int = 256,
+                 device: int = 0):
+        h = C.c_void_p()
+        _check(lib().aidax_resampler_create(n_streams, rate_in, rate_out, d_in, d_out, max_in_frames, device, C.byref(h)))
+        self.h = h
+        live_handles.add(self)
+        self.n_streams = n_streams
+        self.d_in, self.d_out = d_in, d_out
+
+    @property
+    def ready(self) -> int:
+        return int(lib().aidax_resampler_ready(self.h))
+
+    @property
+    def latency_frames(self):
+        """the delays the stage was created with: (d_in input frames, d_out output frames)"""
+        return self.d_in, self.d_out
+
+    def process(self, x: np.ndarray, n_out: Optional[int] = None) -> np.ndarray:
+        """append x ([n_streams][n_in]) and return the next n_out outputs (None: every output that is ready then)"""
+        x = _f32(x)
+        assert x.ndim == 2 and x.shape[0] == self.n_streams
+        if n_out is None:
+            _check(lib().aidax_resampler_process(self.h, x.ctypes.data_as(_fp), x.shape[1], None, 0))
+            x = x[:, :0]
+            n_out = self.ready
+        out = np.empty((self.n_streams, n_out), np.float32)
+        _check(lib().aidax_resampler_process(self.h, x.ctypes.data_as(_fp), x.shape[1], out.ctypes.data_as(_fp), n_out))
+        return out
+
+    def process_device(self, d_in: int, n_in: int, d_out: int, n_out: int, stream: int = 0):
+        """d_in / d_out: raw device pointers ([n_streams][n_in] resp. [n_streams][n_out] fp32); stream: hipStream_t as int."""
+        _check(lib().aidax_resampler_process_device(self.h, C.c_void_p(d_in) if d_in else None, n_in, C.c_void_p(d_out) if d_out else None, n_out,
+                                                    C.c_void_p(stream) if stream else None))
+
+    def reset_stream(self, stream: int):
+        _check(lib().aidax_resampler_reset_stream(self.h, stream))
+
+    def close(self):
+        if self.h:
+            lib().aidax_resampler_destroy(self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class RateAdapter:
+    """aidax_rate: a pool created at its model's rate, driven in blocks at the host's rate. Close it before the pool."""
+
+    def __init__(self, pool: Pool, host_rate: float, max_frames: int = 256):
+        h = C.c_void_p()
+        _check(lib().aidax_rate_create(pool.h, host_rate, max_frames, C.byref(h)))
+        self.h = h
+        self.pool = pool
+        live_handles.add(self)
+        if not hasattr(pool, "_adapters"):
+            pool._adapters = weakref.WeakSet()
+        pool._adapters.add(self)
+        self.n_streams = pool.n_streams
+
+    @property
+    def latency_frames(self) -> int:
+        return int(lib().aidax_rate_latency_frames(self.h))
+
+    def process(self, x: np.ndarray) -> np.ndarray:
+        x = _f32(x)
+        assert x.ndim == 2 and x.shape[0] == self.n_streams
+        out = np.empty_like(x)
+        _check(lib().aidax_rate_process(self.h, x.ctypes.data_as(_fp), out.ctypes.data_as(_fp), x.shape[1]))
+        return out
+
+    def process_device(self, d_in: int, d_out: int, n_frames: int, stream: int = 0):
+        _check(lib().aidax_rate_process_device(self.h, C.c_void_p(d_in) if d_in else None, C.c_void_p(d_out) if d_out else None, n_frames,
+                                               C.c_void_p(stream) if stream else None))
+
+    def reset_stream(self, stream: int):
+        _check(lib().aidax_rate_reset_stream(self.h, stream))
+
+    def close(self):
+        if self.h:
+            lib().aidax_rate_destroy(self.h)
             self.h = C.c_void_p()
 
     def __del__(self):

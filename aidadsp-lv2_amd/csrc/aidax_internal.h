@@ -61,6 +61,12 @@ int  pool_read_stream_state(aidax_pool* p, uint32_t stream, StreamState* out);
 bool pool_has_model(const aidax_pool* p);
 int  pool_peek_stream_state(aidax_pool* p, uint32_t stream, StreamState* pinned_out, void* done_event);
 
+// what the rate adapter (aidax_rate.cpp) needs of the pool it borrows: its device and block limit, and the pool put back on its own
+// stream behind everything issued so far (the event edge of a stream change, no pass: nothing is latched)
+int      pool_device(const aidax_pool* p);
+uint32_t pool_max_frames(const aidax_pool* p);
+int      pool_enter_own_stream(aidax_pool* p);
+
 // k_mfma_lp fault report of a pool (aidax_pool.cpp): true once per give-up; the pool then serves its model with k_mfma
 bool pool_take_lp_fault(aidax_pool* p);
 bool pool_chained_kernel_in_use(aidax_pool* p);      // the next pass of the playing model goes out on k_mfma_lp / k_mfma_ls (whose hand-over can give up)

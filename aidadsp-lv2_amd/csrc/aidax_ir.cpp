@@ -9,6 +9,7 @@
 #include <vector>
 
 #include "aidax_ir_stage.h"
+#include "aidax_sinc.h"
 
 namespace aidax {
 
@@ -137,43 +138,8 @@ const uint8_t kSubtypeTail[12] = { 0x00, 0x00, 0x10, 0x00, 0x80, 0x00, 0x00, 0xa
 
 int wav_error(const std::string& path, const std::string& what) { return fail(AIDAX_ERR_ARG, path + ": " + what); }
 
-// aidax_ir_resample's filter: a sinc of kRsZeros zero crossings a side under a Kaiser window of shape kRsBeta (include/aidax.h)
-constexpr int64_t kRsZeros = 32;
-constexpr double kRsBeta = 12.0;
-constexpr double kRsPi = 3.14159265358979323846;
+// aidax_ir_resample's filter (aidax_sinc.h: kRsZeros, kRsBeta, kaiser_sinc, shared with the streaming resampler)
 constexpr uint32_t kRsMaxLead = 1024;
-
-// I0 by its power series, sum ((x / 2)^k / k!)^2: every term positive, 40 of them at x = 12
-double bessel_i0(double x)
-{
-    const double q = 0.25 * x * x;
-    double term = 1.0, sum = 1.0;
-    for (int k = 1; k < 200; ++k) {
-        term *= q / (static_cast<double>(k) * static_cast<double>(k));
-        sum += term;
-        if (term < 1e-20 * sum) break;
-    }
-    return sum;
-}
-
-uint64_t gcd_u64(uint64_t a, uint64_t b)
-{
-    while (b) { const uint64_t t = a % b; a = b; b = t; }
-    return a;
-}
-
-// sin(pi n / D) from the residue of n mod 2 D folded into [0, D / 2]: exactly 0 where n / D is an integer
-double sin_pi_ratio(int64_t n, int64_t D)
-{
-    int64_t r = n % (2 * D);
-    if (r < 0) r += 2 * D;
-    double sign = 1.0;
-    if (r >= D) { r -= D; sign = -1.0; }
-    if (2 * r > D) r = D - r;
-    return r == 0 ? 0.0 : sign * std::sin(kRsPi * static_cast<double>(r) / static_cast<double>(D));
-}
-
-bool integer_rate(double r) { return r >= 1.0 && r <= 16777216.0 && r == std::floor(r); }
 
 }  // namespace
 
@@ -295,12 +261,7 @@ AIDAX_API int aidax_ir_resample(const float* in, uint32_t n_in, double rate_in, 
     }
     const double scale = L > M ? static_cast<double>(M) / static_cast<double>(L) : 1.0;       // (M / L) c
     const double inv_i0 = 1.0 / bessel_i0(kRsBeta);
-    auto weight = [&](int64_t n) {
-        if (n == 0) return 1.0;
-        const double x = static_cast<double>(n) / static_cast<double>(D);
-        const double v = x / static_cast<double>(kRsZeros);
-        return sin_pi_ratio(n, D) / (kRsPi * x) * bessel_i0(kRsBeta * std::sqrt(1.0 - v * v)) * inv_i0;
-    };
+    auto weight = [&](int64_t n) { return kaiser_sinc(n, D, inv_i0); };
     // The weight is a function of n alone, and for the usual ratios (D = 160 between 48 and 44.1 kHz) there are far fewer values of n
     // than (frame, tap) pairs: a table of all 2 Z D - 1 of them, the same doubles the direct evaluation gives.
     std::vector<double> table;

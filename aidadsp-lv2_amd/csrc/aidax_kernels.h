@@ -134,6 +134,26 @@ struct IrFadeArgs {
 };
 hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q);
 
+// The streaming resampler (aidax_resample.hip, k_resample): one launch appends the call's n_in new frames per stream to the history ring
+// (per stream a row of mask + 1 floats, frame k in slot k & mask) and writes the call's n_out outputs per stream. Output t of the call has
+// the numerator a0 + t M, a0 = q0 L + phi0 (include/aidax.h, "Rate conversion"), and reads the inputs q - H .. q + H around
+// q = q0 + (phi0 + t M) / L; input frames are named relative to the first new one (frame -1 is the ring's latest), and frames before
+// -n_hist are zeros. Workgroups over (output tile of kRsTile, stream); a call without outputs runs one workgroup per stream for the append.
+constexpr uint32_t kRsTile = 256;
+constexpr uint32_t kRsWindow = 4096;           // floats of LDS a tile's input window may take; a wider window is read from memory in place
+struct ResampleArgs {
+    const float* wt;             // the weight rows, transposed: [T][L]
+    float* ring;
+    const float* in;             // [n_streams][n_in]
+    float* out;                  // [n_streams][n_out]
+    uint32_t L, M, H, mask, pos; // pos: the ring slot of the first new frame
+    uint32_t n_streams, n_in, n_out, n_hist, phi0;
+    int32_t q0;                  // relative to the first new frame
+    uint32_t copy;               // equal rates: out = x[q], a bit copy
+};
+uint32_t resample_window(uint32_t L, uint32_t M, uint32_t H);      // floats of a full tile's input window
+hipError_t launch_resample(const ResampleArgs& a, hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

@@ -977,6 +977,17 @@ bool pool_take_lp_fault(aidax_pool* p) { return p->take_lp_fault(); }
 bool pool_chained_kernel_in_use(aidax_pool* p) { return p->cur.has_model && p->cur.kind == ModelSlot::MFMA && p->cur.mdesc.n_layers >= 2 && p->lp_in_use(p->cur); }
 bool pool_lp_in_use(const aidax_pool* p) { return p->cur.has_model && p->lp_in_use(p->cur); }
 
+int pool_device(const aidax_pool* p) { return p->device; }
+uint32_t pool_max_frames(const aidax_pool* p) { return p->max_frames; }
+int pool_enter_own_stream(aidax_pool* p)
+{
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        p->enter_stream(p->q);
+        return AIDAX_OK;
+    });
+}
+
 }  // namespace aidax
 
 extern "C" {
@@ -1092,6 +1103,7 @@ AIDAX_API void aidax_pool_destroy(aidax_pool* p)
 }
 
 AIDAX_API uint32_t aidax_pool_streams(const aidax_pool* p) { return p ? p->n_streams : 0; }
+AIDAX_API double aidax_pool_samplerate(const aidax_pool* p) { return p ? p->host_sr : 0.0; }
 
 AIDAX_API int aidax_pool_prepare_model(aidax_pool* p, const aidax_model* m, int start_mode, aidax_staged** out)
 {

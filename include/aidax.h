@@ -326,12 +326,92 @@ AIDAX_API int      aidax_ir_resample(const float* in, uint32_t n_in, double rate
 AIDAX_API int      aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps);
 AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p);
 
+/* Rate conversion: a model at its trained rate inside a host at another. An AIDA-X model is a nonlinear filter trained at one rate
+ * (aidax_model_info_t.samplerate, 48 kHz for the bundled files; the reference leaves the mismatch open, rt-neural-generic.cpp:348). The
+ * host creates the pool at the MODEL's rate, so the EQ, the gain smoothers and any IR keep their frequencies and times, and wraps it in a
+ * rate adapter at its own rate: every block is converted on the device, host -> pool rate, the pool's pass, pool -> host rate, with
+ * per-stream history. A pool that is never wrapped allocates and launches exactly what it did before these calls existed.
+ *
+ * aidax_resampler: the streaming polyphase resampler underneath, for n_streams streams. It is the window of aidax_ir_resample applied to
+ * a signal (no M / L factor): Z = 32, beta = 12, L / M = rate_out / rate_in in lowest terms, D = max(L, M), c = min(1, L / M),
+ * H = ceil(Z D / L), T = 2 H + 1. For the output index j >= 0, counted since creation and shared by all streams,
+ *     a = (j - d_out) M - d_in L   (exact integers),   q = floor(a / L),   phi = a - q L
+ *     out[s][j] = sum_{i = -H .. H} w_phi[i + H] x[s][q - i]
+ *     w_phi[i + H] = c sinc(c (phi + i L) / L) K(c (phi + i L) / (L Z)),   rounded once from fp64 to fp32
+ * with K and the exact-integer sine of aidax_ir_resample (an integer argument weighs exactly 0, and exactly 1 at 0). x[k] = 0 for k < 0
+ * and for frames from before the stream's last reset; d_in and d_out are integer delays in input and output frames, fixed at creation
+ * (0 .. 65536). The L rows of T weights are built on the host in fp64 at creation and uploaded once. Both rates are positive integers
+ * <= 2^24 with max(L, M) <= 640: every pair of 44.1 / 48 / 88.2 / 96 / 176.4 / 192 kHz (the longest rows, T = 281, at 192 -> 44.1 kHz);
+ * anything else is AIDAX_ERR_ARG with the reason. Equal rates are legal: the row is a delta, the stage a pure delay and a bit copy.
+ * Sums are fp32, one fixed order per output sample: the same inputs give the same bits, and the bits of an output do not depend on how
+ * the input was cut into calls.
+ * aidax_resampler_create          SET-UP side: the weight table, per stream a history ring (the power of two >= T + 2 max_in_frames +
+ *                                 2 ceil(M / L) + 2 frames) and the staging of aidax_resampler_process on device `device_id`. n_streams 1 .. 65535.
+ * aidax_resampler_row             host only and pure: row `phase` (0 .. L - 1) of the filter, min(cap, T) weights to `w`, T to *n_taps
+ *                                 (cap == 0 with w == NULL asks for T alone).
+ * aidax_resampler_process_device  appends n_in frames per stream, laid out [n_streams][n_in], then writes the next n_out outputs, laid
+ *                                 out [n_streams][n_out] (another buffer than d_in). Either count may be 0. One kernel launch,
+ *                                 asynchronous on `hip_stream` (NULL: the resampler's own stream), no host sync; consecutive calls on
+ *                                 different streams are ordered by an event edge. AIDAX_ERR_STATE, with nothing appended, when an output
+ *                                 is asked for whose row reaches past the inputs received (q + H >= frames received), or when outputs
+ *                                 of earlier calls were left untaken for so long that the new frames would overwrite history they need
+ *                                 (more than about max_in_frames behind). AIDAX_ERR_ARG for n_in > max_in_frames or n_out > 2^20.
+ * aidax_resampler_process         the same with host buffers, blocking (pinned staging allocated at creation; waits for the
+ *                                 resampler's stream only); at most ceil((max_in_frames + T) L / M) + 2 outputs a call.
+ * aidax_resampler_ready           how many outputs may be asked for now.
+ * aidax_resampler_reset_stream    that stream's past counts as zeros from here on (ordered behind the calls issued so far); the output
+ *                                 index goes on.
+ *
+ * aidax_rate: the adapter around a pool. With r = pool_rate / host_rate = La / Ma, stage A converts host -> pool with d_in = H_A,
+ * d_out = 0, stage B pool -> host with d_in = 0, d_out = d_B = ceil((H_B + 1) Ma / La). A call of n host frames that brings the total
+ * received to N gives stage A the n frames and takes m = floor(N r) - floor((N - n) r) pool frames from it, runs the pool's pass over
+ * those m frames (m == 0: the legal pre-run), gives them to stage B and takes exactly n host frames. With these delays every row ends
+ * inside the frames received, for any block size down to 1, and m differs by at most one from call to call. The latency is the integer
+ * H_A + d_B host frames: 66 at 44.1 -> 48 kHz, 130 at 96 -> 48, 260 at 192 -> 48, 71 at 48 -> 44.1; report it to the host. Equal rates:
+ * the adapter forwards to the pool, latency 0, bit-identical to aidax_pool_process.
+ * aidax_pool_samplerate      the rate the pool was created at.
+ * aidax_rate_create          SET-UP side: borrows `pool`, which must outlive the adapter. While the adapter exists blocks go through it,
+ *                            not through the pool's own process calls; every other call (model, controls, IRs, reset) stays on the pool.
+ *                            AIDAX_ERR_ARG for rates the resampler refuses (the pool's included) and when ceil(max_frames r) exceeds the
+ *                            pool's max_frames.
+ * aidax_rate_destroy         SET-UP side: waits for the adapter's passes and puts the pool back on its own stream, without a pass.
+ * aidax_rate_latency_frames  H_A + d_B (0 at equal rates).
+ * aidax_rate_latency         the same, pure and host only, for a host that reports its latency before it builds anything.
+ * aidax_rate_process         AUDIO side, blocking, host buffers laid out [n_streams][n] (in place allowed): the adapter's own pinned
+ *                            staging, waits for its stream only; a pool pass that went wrong is reported as aidax_pool_process
+ *                            reports it (silence and AIDAX_ERR_DEVICE). n == 0 runs the pool's pre-run and moves nothing else.
+ * aidax_rate_process_device  AUDIO side, asynchronous on `hip_stream` (NULL: the adapter's own stream), device buffers, d_out another
+ *                            buffer than d_in; a stream handed in stays valid as for aidax_pool_process_device.
+ * aidax_rate_reset_stream    AUDIO side: both stages' history of that stream; the caller resets the pool's stream itself.
+ * None of the processing calls allocates or frees. */
+typedef struct aidax_resampler aidax_resampler;
+typedef struct aidax_rate aidax_rate;
+AIDAX_API int      aidax_resampler_create(uint32_t n_streams, double rate_in, double rate_out, uint32_t d_in, uint32_t d_out,
+                                          uint32_t max_in_frames, int device_id, aidax_resampler** out);
+AIDAX_API void     aidax_resampler_destroy(aidax_resampler* rs);
+AIDAX_API int      aidax_resampler_row(double rate_in, double rate_out, uint32_t phase, float* w, uint32_t cap, uint32_t* n_taps);
+AIDAX_API int      aidax_resampler_process_device(aidax_resampler* rs, const float* d_in, uint32_t n_in, float* d_out, uint32_t n_out,
+                                                  void* hip_stream);
+AIDAX_API int      aidax_resampler_process(aidax_resampler* rs, const float* in, uint32_t n_in, float* out, uint32_t n_out);
+AIDAX_API uint32_t aidax_resampler_ready(const aidax_resampler* rs);
+AIDAX_API int      aidax_resampler_reset_stream(aidax_resampler* rs, uint32_t stream);
+AIDAX_API double   aidax_pool_samplerate(const aidax_pool* p);
+AIDAX_API int      aidax_rate_create(aidax_pool* pool, double host_rate, uint32_t max_frames, aidax_rate** out);
+AIDAX_API void     aidax_rate_destroy(aidax_rate* r);
+AIDAX_API uint32_t aidax_rate_latency_frames(const aidax_rate* r);
+AIDAX_API int      aidax_rate_latency(double host_rate, double pool_rate, uint32_t* frames);
+AIDAX_API int      aidax_rate_process(aidax_rate* r, const float* in, float* out, uint32_t n_frames);
+AIDAX_API int      aidax_rate_process_device(aidax_rate* r, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream);
+AIDAX_API int      aidax_rate_reset_stream(aidax_rate* r, uint32_t stream);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, set_ir_fade, process*, sync) plus, concurrently, ONE worker-side caller (prepare_model,
+ * reset_stream, commit_model, commit_ir, assign_ir, set_ir_fade, process*, sync; around a wrapped pool also aidax_rate_process,
+ * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
  * before the two threads start; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
- * habit. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_sync wait for the GPU (for the stream that carries the pass, never for the
+ * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
+ * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
+ * aidax_pool_process / aidax_pool_sync / aidax_rate_process wait for the GPU (for the stream that carries the pass, never for the
  * device) — with one exception in every pass: changed control records, and a changed IR plan (after an assign_ir or a commit_ir), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
