@@ -17,6 +17,8 @@ ALL_STREAMS = -1
 START_WARMUP, START_RESET = 0, 1
 IR_SLOTS = 64                     # AIDAX_IR_SLOTS: bank slots per pool, besides the pool IR
 IR_POOL, IR_NONE = -1, -2         # a stream's IR: the pool IR (default), none, or a bank slot 0 .. IR_SLOTS - 1
+MODEL_SLOTS = 64                  # AIDAX_MODEL_SLOTS: model-bank slots per pool, besides the pool model
+MODEL_POOL = -1                   # a stream's model: the pool model (default) or a bank slot 0 .. MODEL_SLOTS - 1
 _fp = C.POINTER(C.c_float)
 
 
@@ -111,6 +113,12 @@ def lib() -> C.CDLL:
     L.aidax_pool_prepare_model.argtypes = [vp, vp, C.c_int, C.POINTER(vp)]
     L.aidax_pool_commit_model.argtypes = [vp, vp]
     L.aidax_staged_free.argtypes = [vp]
+    if hasattr(L, "aidax_pool_assign_model"):      # (AIDAX_LIB may name a build from before the model bank: A/B runs against it)
+        L.aidax_model_bank_compatible.argtypes = [vp, vp]
+        L.aidax_pool_prepare_model_slot.argtypes = [vp, u32, vp, C.POINTER(vp)]
+        L.aidax_pool_set_model_slot.argtypes = [vp, u32, vp]
+        L.aidax_pool_assign_model.argtypes = [vp, i32, i32, C.c_int]
+        L.aidax_pool_stream_model.argtypes = [vp, u32, C.POINTER(i32)]
     L.aidax_staged_free.restype = None
     L.aidax_pool_set_loading.argtypes = [vp, i32, C.c_int]
     L.aidax_pool_set_controls.argtypes = [vp, i32, C.POINTER(Controls)]
@@ -306,6 +314,22 @@ def many_streams_form(cell: int, hidden: int, n_streams: int, compute_units: int
     return int(lib().aidax_many_streams_form_at(cell, hidden, n_streams, compute_units, max_frames))
 
 
+def bank_compatible(pool_model: "Model", m: "Model") -> bool:
+    """aidax_model_bank_compatible (host only): may `m` sit in a bank slot of a pool whose pool model is `pool_model`? The reason of a
+    refusal is in last_error()."""
+    rc = lib().aidax_model_bank_compatible(pool_model.h, m.h)
+    if rc == 0:
+        return True
+    if rc == -4:                  # AIDAX_ERR_ARCH: the answer "no"
+        return False
+    _check(rc)
+    return False
+
+
+def last_error() -> str:
+    return lib().aidax_last_error().decode(errors="replace")
+
+
 def db_to_coeff(db: float) -> float:
     return float(lib().aidax_db_to_coeff(C.c_float(db)))
 
@@ -405,6 +429,25 @@ class Pool:
     @staticmethod
     def staged_free(staged: C.c_void_p):
         lib().aidax_staged_free(staged)
+
+    def prepare_model_slot(self, slot: int, m: Optional[Model]) -> C.c_void_p:
+        """worker half of a model-bank slot's swap (m None: empty it): returns the staged handle for commit_model / staged_free"""
+        sg = C.c_void_p()
+        _check(lib().aidax_pool_prepare_model_slot(self.h, slot, m.h if m is not None else None, C.byref(sg)))
+        return sg
+
+    def set_model_slot(self, slot: int, m: Optional[Model]):
+        """aidax_pool_set_model_slot: load model-bank slot `slot` with a weight variant of the pool model's architecture (m None: empty it)"""
+        _check(lib().aidax_pool_set_model_slot(self.h, slot, m.h if m is not None else None))
+
+    def assign_model(self, stream: int, slot: int, start_mode: int = START_WARMUP):
+        """aidax_pool_assign_model: `stream` plays `slot` (MODEL_POOL or a bank slot) from the next pass on, as a fresh DynamicModel"""
+        _check(lib().aidax_pool_assign_model(self.h, stream, slot, start_mode))
+
+    def stream_model(self, stream: int) -> int:
+        v = C.c_int32(0)
+        _check(lib().aidax_pool_stream_model(self.h, stream, C.byref(v)))
+        return v.value
 
     def set_ir(self, taps: Optional[np.ndarray], samplerate: Optional[float] = None):
         """aidax_pool_set_ir: attach a cabinet IR (taps None: remove it); samplerate defaults to the pool's"""

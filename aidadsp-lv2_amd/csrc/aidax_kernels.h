@@ -19,6 +19,8 @@ struct KernelEntry {
     void (*fn_pipe4)(LaunchArgs);     // four streams per workgroup, one helper wave (k_*_pipe4; nullptr: the cell has none)
     const char* name_pipe4;
     void (*fn_pipe4c)(LaunchArgs);    // the same for a conditioned model (PARAM1 / PARAM2 as inputs): the helper wave also runs the PARAM smoothers
+    void (*fn_pipe_bank)(LaunchArgs); // fn_pipe with every stream on the model of its own record (LaunchArgs::bank): the model bank's pass (nullptr: no fn_pipe)
+    const char* name_pipe_bank;
 };
 
 const KernelEntry* find_kernel(int cell, int hidden);
@@ -27,6 +29,7 @@ hipError_t launch_split_kernels(const KernelEntry* e, const LaunchArgs& a, hipSt
 bool split_form_pays(const KernelEntry* e, uint32_t n_frames);
 size_t pipe_lds_bytes(int hidden, uint32_t n_frames);
 hipError_t launch_pipe_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream, hipEvent_t done = nullptr);
+hipError_t launch_pipe_bank_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream, hipEvent_t done = nullptr);
 int pipe_resident_streams(const KernelEntry* e, uint32_t n_frames, int device);
 // k_*_pipe4: a pass of whole 16-frame tiles, whole workgroups of four streams, (the caller checks)
 size_t pipe4_lds_bytes(int hidden, uint32_t n_frames, int input_size);

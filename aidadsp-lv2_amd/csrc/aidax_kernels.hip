@@ -673,7 +673,10 @@ __device__ __forceinline__ void post_done_word(const LaunchArgs& a, int lane)
     }
 }
 
-template <class Cell>
+// kBank (k_*_pipe_bank, the model bank): the stream's model — weight record, Dense row, the file's two gains and its skip flag — is its
+// own record a.bank[s] instead of the launch arguments' one model. The workgroup index is uniform, so the record arrives by scalar
+// reads ahead of every store of the kernel; nothing else in the body knows about the bank.
+template <class Cell, bool kBank = false>
 __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* smem)
 {
     constexpr int H = Cell::HID;
@@ -682,6 +685,17 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int s = blockIdx.x;
     const int n = (int)a.n_frames;
+    // (the record as the kernel reads it: a pointer read from memory is a generic one to the compiler unless its type says device memory,
+    // as it knows of a.wpack — with it the weight reads stay global loads)
+    struct Rec { const float __attribute__((address_space(1)))* wpack; float in_gain, out_gain; int32_t input_skip; uint32_t pad[3]; };
+    static_assert(sizeof(Rec) == sizeof(ModelRec), "ModelRec layout");
+    Rec rec{};
+    if constexpr (kBank) rec = reinterpret_cast<const Rec*>(a.bank)[s];
+    // the five reads of model data (without a bank they are the launch arguments' reads, where they always were)
+    const auto m_wpack = [&]() -> const float* { if constexpr (kBank) return (const float*)rec.wpack; else return a.wpack; };
+    const auto m_in_gain = [&]() -> float { if constexpr (kBank) return rec.in_gain; else return a.in_gain; };
+    const auto m_out_gain = [&]() -> float { if constexpr (kBank) return rec.out_gain; else return a.out_gain; };
+    const auto m_skip = [&]() -> int32_t { if constexpr (kBank) return rec.input_skip; else return a.input_skip; };
 
 #ifdef AIDAX_PIPE_TRACE
     const unsigned long long tr_w0 = wall_clock64(), tr_c0 = clock64();
@@ -767,7 +781,7 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
         // waves of other streams: it issues first (measured 95 -> 84 us per cfg2 block)
         if (!(AIDAX_TUNE(a) & 1)) __builtin_amdgcn_s_setprio(3);
         if (net_on) {
-            cell.load(a.wpack, nnst, lane);
+            cell.load(m_wpack(), nnst, lane);
             cell.publish_h(hh + (kRing - 1) * HS);       // h(-1): the row "before" frame 0
         }
     } else {                              // ---- Q prologue
@@ -783,7 +797,7 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
         cp.g.arm(master_mem, master_tgt, ctl.master_coef);
         q_z1o = cp.z1; q_z2o = cp.z2;
         if (net_on) {
-            const float* wd_nat = a.wpack + (size_t)Cell::PACK * kWave;     // [H] Dense weights then bias
+            const float* wd_nat = m_wpack() + (size_t)Cell::PACK * kWave;     // [H] Dense weights then bias
             for (int i = lane; i < H + 1; i += kWave) wdl[i] = wd_nat[i];
         }
         __builtin_amdgcn_wave_barrier();
@@ -826,7 +840,7 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
                 // rows of one sub-block are contiguous in the ring (base is a multiple of kSB)
                 const float* hprev = hh + ((base + kRing - 1) & (kRing - 1)) * HS;
                 float* hcur = hh + (base & (kRing - 1)) * HS;
-                const float in_gain = a.in_gain;
+                const float in_gain = m_in_gain();
                 if (I == 1 && cnt == kSB) {
                     // snapshot models, whole stage: the stage's inputs travel into registers with four reads and the
                     // frame loop is unrolled, so a frame's only LDS traffic is h (one write, H/4 broadcast reads issued
@@ -912,9 +926,9 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
                         y = __builtin_fmaf(w.z, hv.z, y);
                         y = __builtin_fmaf(w.w, hv.w, y);
                     }
-                    const float xg = xin * a.in_gain;
-                    o = a.input_skip ? xg + y : y;                          // out[i] (+)= forward
-                    o = o * a.out_gain;                                     // out[i] *= output_gain
+                    const float xg = xin * m_in_gain();
+                    o = m_skip() ? xg + y : y;                              // out[i] (+)= forward
+                    o = o * m_out_gain();                                   // out[i] *= output_gain
                 }
                 if (lane < cnt) qb[lane] = o;
                 __builtin_amdgcn_wave_barrier();
@@ -1018,6 +1032,21 @@ __global__ __launch_bounds__(kPipeWaves * kWave) void k_gru_pipe(LaunchArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     stream_body_pipe<GruCell<H>>(a, smem);
+}
+
+// The model bank's pass: the same workgroup per stream, every stream on the model of its record (a.bank)
+template <int H>
+__global__ __launch_bounds__(kPipeWaves * kWave) void k_lstm_pipe_bank(LaunchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    stream_body_pipe<LstmCell<H>, true>(a, smem);
+}
+
+template <int H>
+__global__ __launch_bounds__(kPipeWaves * kWave) void k_gru_pipe_bank(LaunchArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    stream_body_pipe<GruCell<H>, true>(a, smem);
 }
 
 
@@ -1796,17 +1825,17 @@ __global__ void k_adopt_dsp(StreamState* dst, const StreamState* src)
 }
 
 // ------------------------------------------------------------ host dispatch
-#define AIDAX_LSTM(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr }
+#define AIDAX_LSTM(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
 // ... with the four-streams-per-workgroup pipeline as well (BASELINE cfg2's cell)
-#define AIDAX_LSTM_P4(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", k_lstm_pipe4<H>, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true> }
+#define AIDAX_LSTM_P4(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", k_lstm_pipe4<H>, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true>, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
 // LSTM-64 / LSTM-80: the helper waves' share of the register file (pipe) resp. the Dense ring (split, H = 80) push the
 // 4H-row cell past 512 registers — those forms would spill, so they do not exist; the pool serves these cells
 // with k_quad / k_mfma, or the one-wave kernel when neither fits (pools with long blocks).
-#define AIDAX_LSTM_WIDE(H, NN) { 0, H, k_lstm<H>, nullptr, NN, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "-", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr }
-#define AIDAX_GRU(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "-", nullptr }
-#define AIDAX_LSTM_P4C(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true> }
-#define AIDAX_GRU_P4C(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true> }
-#define AIDAX_GRU_P4(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", k_gru_pipe4<H>, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true> }
+#define AIDAX_LSTM_WIDE(H, NN) { 0, H, k_lstm<H>, nullptr, NN, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "-", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr, nullptr, "-" }
+#define AIDAX_GRU(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "-", nullptr, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
+#define AIDAX_LSTM_P4C(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true>, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
+#define AIDAX_GRU_P4C(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true>, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
+#define AIDAX_GRU_P4(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", k_gru_pipe4<H>, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true>, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
 
 static const KernelEntry kTable[] = {
     // the 18 (cell, hidden) pairs of variant/generate_variant_hpp.py:4-6; input size is a run-time argument
@@ -1900,6 +1929,18 @@ hipError_t launch_pipe_kernel(const KernelEntry* e, const LaunchArgs& a, hipStre
         return hipGetLastError();
     }
     hipLaunchKernelGGL(e->fn_pipe, dim3(a.n_streams), dim3(kPipeWaves * kWave), pipe_lds_bytes(e->hidden, a.n_frames), stream, a);
+    return hipGetLastError();
+}
+
+// The model bank's pass: k_*_pipe's grid and LDS, the kernel that reads a.bank (which the caller has set)
+hipError_t launch_pipe_bank_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream, hipEvent_t done)
+{
+    if (!e->fn_pipe_bank || !a.bank) return hipErrorInvalidDeviceFunction;
+    if (done) {
+        hipExtLaunchKernelGGL(e->fn_pipe_bank, dim3(a.n_streams), dim3(kPipeWaves * kWave), pipe_lds_bytes(e->hidden, a.n_frames), stream, nullptr, done, 0, a);
+        return hipGetLastError();
+    }
+    hipLaunchKernelGGL(e->fn_pipe_bank, dim3(a.n_streams), dim3(kPipeWaves * kWave), pipe_lds_bytes(e->hidden, a.n_frames), stream, a);
     return hipGetLastError();
 }
 

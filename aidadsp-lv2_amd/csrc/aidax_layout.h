@@ -299,6 +299,17 @@ template <class F> constexpr auto st_geo_dispatch(int g, F&& f)     // f(G{}) fo
     }
 }
 
+// The model bank (k_*_pipe_bank): what one stream's workgroup reads of ITS model — the weight record in the pool model's
+// layout (pack_weights: same cell, width and input count) and the three scalars of the model file. One record per stream,
+// resolved on the host (a stream on the pool model holds the pool model's values) and uploaded stream-ordered by dirty range.
+struct alignas(16) ModelRec {
+    const float* wpack;
+    float        in_gain, out_gain;
+    int32_t      input_skip;
+    uint32_t     pad[3];
+};
+static_assert(sizeof(ModelRec) == 32, "ModelRec layout");
+
 struct LaunchArgs {
     const StreamCtl* ctl;
     StreamState*     st;
@@ -323,6 +334,7 @@ struct LaunchArgs {
     uint32_t         done_seq;    // k_*_pipe / k_*_pipe4 of a ONE-stream pool whose `out` is the host's memory: the wave that has stored the block
     uint32_t*        done_word;   // writes done_seq here behind it (host memory; nullptr: nobody waits this way) — the blocking path's completion
                                   // word without a packet behind the pass (aidax_pool_process, profiles/r06_host_pipeline.txt)
+    const ModelRec*  bank;        // k_*_pipe_bank only: [n_streams] per-stream model records (every other kernel: unused, nullptr)
 };
 
 }  // namespace aidax

@@ -283,6 +283,56 @@ struct ModelSlot {
 };
 
 constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
+
+// The model bank (include/aidax.h, "Per-stream amp models"): weight variants of the pool model's architecture, one per slot, and per
+// stream the slot it plays. A slot's content is what a table model's prepare uploads (pack_weights) plus the file's three scalars; the
+// architecture fields are kept for the host-only re-checks at commit time.
+struct BankSlot {
+    bool loaded = false;
+    float* d_wpack = nullptr;
+    int cell = 0, hidden = 0, input_size = 0, input_skip = 0;
+    float in_gain = 1.f, out_gain = 1.f, model_sr = 48000.f;
+};
+// Allocated by the first aidax_pool_prepare_model_slot (worker thread) and published through aidax_pool::bank; everything in it but
+// the allocation itself is the audio side's. The per-stream records (h_rec, d_rec) are valid while a stream is assigned to a slot —
+// the assignment that makes the first one rewrites them all — and reach the device like the control records: by dirty range from a
+// ring of pinned snapshots, on the stream of the pass that follows.
+struct ModelBank {
+    BankSlot slot[AIDAX_MODEL_SLOTS];
+    uint32_t users[AIDAX_MODEL_SLOTS] = {};              // streams assigned to each slot
+    uint32_t n_loaded = 0;
+    std::atomic<uint32_t> n_assigned{0};                 // streams on any slot (read by aidax_pool_kernel_name from other threads)
+    std::vector<int32_t> assign;                         // per stream: AIDAX_MODEL_POOL or a slot
+    std::vector<ModelRec> h_rec;
+    ModelRec* d_rec = nullptr;
+    ModelRec* ring[kCtlRing] = {};
+    hipEvent_t ev[kCtlRing] = {};
+    bool used[kCtlRing] = {};
+    int next = 0;
+    uint32_t dirty_lo = 1, dirty_hi = 0;
+    void mark_dirty(uint32_t lo, uint32_t hi)
+    {
+        if (dirty_lo > dirty_hi) { dirty_lo = lo; dirty_hi = hi; }
+        else { dirty_lo = std::min(dirty_lo, lo); dirty_hi = std::max(dirty_hi, hi); }
+    }
+    void release()
+    {
+        for (BankSlot& b : slot)
+            if (b.d_wpack) (void)hipFree(b.d_wpack);
+        if (d_rec) (void)hipFree(d_rec);
+        for (int k = 0; k < kCtlRing; ++k) {
+            if (ring[k]) (void)hipHostFree(ring[k]);
+            if (ev[k]) (void)hipEventDestroy(ev[k]);
+        }
+    }
+};
+// the fields two models must share to sit in one bank; nullptr: none differs
+struct BankArch { int cell, hidden, input_size; float sr; };
+const char* bank_arch_diff(const BankArch& a, const BankArch& b)
+{
+    return a.cell != b.cell ? "cell" : a.hidden != b.hidden ? "hidden" : a.input_size != b.input_size ? "input_size" : a.sr != b.sr ? "samplerate" : nullptr;
+}
+bool bank_table_model(const aidax_model& m) { return !is_conv_model(m) && !is_stack_model(m) && m.n_rnn == 1 && (m.cell == AIDAX_CELL_LSTM || m.cell == AIDAX_CELL_GRU); }
 constexpr size_t kStagingLimit = size_t(64) << 20;      // pinned staging per direction for aidax_pool_process
 constexpr size_t kZeroCopyLimit = size_t(64) << 10;     // blocks up to this size are read / written by the kernels in place in pinned host memory
 
@@ -301,6 +351,9 @@ struct aidax_staged {
     bool is_ir = false;              // an IR on its way (aidax_pool_prepare_ir / _slot): `ir` instead of `slot`
     int32_t ir_slot = AIDAX_IR_POOL; // ... for the pool IR or for this bank slot
     aidax::IrSlot ir;
+    bool is_bank = false;            // a model-bank slot's content on its way (aidax_pool_prepare_model_slot): `bank` instead of `slot`
+    uint32_t bank_slot = 0;
+    aidax::BankSlot bank;
 };
 
 struct aidax_pool {
@@ -400,6 +453,36 @@ struct aidax_pool {
     int ctl_next = 0;
 
     ModelSlot cur;
+    std::atomic<ModelBank*> bank{nullptr};               // the model bank (nullptr until the first aidax_pool_prepare_model_slot)
+    // is a stream assigned to a bank slot? Then every MODE_CHAIN pass is one launch of k_*_pipe_bank over the per-stream records
+    ModelBank* bank_in_force() const
+    {
+        ModelBank* b = bank.load(std::memory_order_acquire);
+        return b && b->n_assigned.load(std::memory_order_relaxed) != 0 ? b : nullptr;
+    }
+    ModelRec pool_rec() const { ModelRec r{}; r.wpack = cur.d_wpack; r.in_gain = cur.in_gain; r.out_gain = cur.out_gain; r.input_skip = cur.input_skip; return r; }
+    // the model stream `s` plays, into launch arguments built for the pool model (warm-ups of one stream)
+    void apply_stream_model(LaunchArgs& a, uint32_t s) const
+    {
+        const ModelBank* b = bank.load(std::memory_order_acquire);
+        if (!b || b->assign[s] < 0) return;
+        const BankSlot& k = b->slot[b->assign[s]];
+        a.wpack = k.d_wpack; a.in_gain = k.in_gain; a.out_gain = k.out_gain; a.input_skip = k.input_skip;
+    }
+    // upload the changed per-stream model records, stream-ordered with the pass that follows (flush_ctl's scheme)
+    void flush_bank(ModelBank& b, hipStream_t s)
+    {
+        if (b.dirty_lo > b.dirty_hi) return;
+        const int k = b.next;
+        if (b.used[k] && hipEventQuery(b.ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(b.ev[k]));
+        const size_t cnt = static_cast<size_t>(b.dirty_hi - b.dirty_lo) + 1;
+        std::memcpy(b.ring[k] + b.dirty_lo, b.h_rec.data() + b.dirty_lo, cnt * sizeof(ModelRec));
+        HIP_TRY(hipMemcpyAsync(b.d_rec + b.dirty_lo, b.ring[k] + b.dirty_lo, cnt * sizeof(ModelRec), hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(b.ev[k], s));
+        b.used[k] = true;
+        b.next = (k + 1) % kCtlRing;
+        b.dirty_lo = 1; b.dirty_hi = 0;
+    }
     int tune = 0;                    // AIDAX_TUNE (measurement switches, see LaunchArgs)
     int cus = 0;                     // compute units of the device (form selection)
     int force_form = 0;              // AIDAX_KERNEL=wave|pipe|split|valu|mfma|quad overrides the heuristic (A/B testing)
@@ -440,6 +523,7 @@ struct aidax_pool {
     // does a MODE_CHAIN pass of this slot consist of one launch (it may then read and write host memory in place)?
     bool single_launch(const ModelSlot& m) const
     {
+        if (&m == &cur && bank_in_force()) return true;
         if (!m.has_model) return chain_form(m) != 2;
         switch (m.kind) {
         case ModelSlot::TABLE: return chain_form(m) != 2;
@@ -640,6 +724,20 @@ struct aidax_pool {
             return e;
         }
         if (m.has_model && m.kind == ModelSlot::CONV) return launch_conv_kernel(a, m.cdesc, s);
+        if (a.bank) {
+            // the model bank in force (pool_process_prefix set the records): the whole pass is one launch of k_*_pipe_bank, whatever form
+            // the pool model alone would take; the pass's end marker rides on it as on k_*_pipe
+            hipEvent_t done = pass_done;
+            pass_done = nullptr;
+            pass_done_taken = done != nullptr;
+            LaunchArgs b = a;
+            if (pass_word && a.n_streams == 1 && a.n_frames != 0) {
+                b.done_word = pass_word; b.done_seq = pass_seq;
+                pass_word = nullptr;
+                pass_word_taken = true;
+            }
+            return launch_pipe_bank_kernel(m.kernel, b, s, done);
+        }
         const int form = a.mode == MODE_CHAIN ? chain_form(m) : 0;
         if (form == 3) {
             LaunchArgs b = a;
@@ -666,6 +764,7 @@ struct aidax_pool {
     void release()
     {
         ir.release();
+        if (ModelBank* b = bank.exchange(nullptr)) { b->release(); delete b; }
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);
         if (cur.d_nn) (void)hipFree(cur.d_nn);
@@ -730,6 +829,7 @@ void staged_release(aidax_staged* s)
     if (s->slot.lp_owner) lp_gate().release(s->device, s->slot.lp_owner);
     if (s->d_pst) (void)hipFree(s->d_pst);
     if (s->ir.d_frag) (void)hipFree(s->ir.d_frag);
+    if (s->bank.d_wpack) (void)hipFree(s->bank.d_wpack);
     if (s->fence) (void)hipEventDestroy(s->fence);
     delete s;
 }
@@ -942,6 +1042,10 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (p->h_lp_fault && *static_cast<volatile uint32_t*>(p->h_lp_fault) != 0) p->lp_off.store(true, std::memory_order_relaxed);
         LaunchArgs a = p->args(p->cur, p->d_st, d_in, d_out, n_frames, MODE_CHAIN);
         a.n_streams = n_active;
+        if (ModelBank* b = p->bank_in_force()) {                     // the records this pass plays, ahead of it on its stream
+            p->flush_bank(*b, s);
+            a.bank = b->d_rec;
+        }
         // with an IR history the pass ends behind the IR stage: its end marker (the submit path's event, the blocking path's completion
         // word) is not handed to the model's launch but issued after the stage by the caller
         const bool ir_on = n_frames != 0 && p->ir.adopt();
@@ -1119,7 +1223,180 @@ AIDAX_API int aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged)
     if (staged->is_ir) return fail(AIDAX_ERR_ARG, "staged object holds an IR: commit it with aidax_pool_commit_ir");
     if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged model was committed already");
     if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged model belongs to another pool");
+    ModelBank* b = p->bank.load(std::memory_order_acquire);
+    if (staged->is_bank) {
+        // a bank slot's content: host integers, then the swap and the fence behind everything that may still read the retired weights
+        const uint32_t k = staged->bank_slot;
+        if (!b) return fail(AIDAX_ERR_STATE, "the pool has no model bank");
+        if (b->users[k] != 0) return fail(AIDAX_ERR_STATE, "model bank slot " + std::to_string(k) + " has streams assigned: move them first");
+        const ModelSlot& cur = p->cur;
+        if (staged->bank.loaded) {
+            const BankSlot& n = staged->bank;
+            if (!cur.has_model || cur.kind != ModelSlot::TABLE || !cur.kernel || !cur.kernel->fn_pipe_bank ||
+                bank_arch_diff({ cur.cell, cur.hidden, cur.input_size, cur.model_sr }, { n.cell, n.hidden, n.input_size, n.model_sr }))
+                return fail(AIDAX_ERR_STATE, "the pool's model changed since aidax_pool_prepare_model_slot: prepare the slot again");
+        }
+        return guarded([&]() -> int {
+            HIP_TRY(hipSetDevice(p->device));
+            p->enter_stream(p->q);
+            HIP_TRY(hipEventRecord(staged->fence, p->q));
+            staged->fenced = true;
+            std::swap(b->slot[k], staged->bank);
+            b->n_loaded += (b->slot[k].loaded ? 1u : 0u) - (staged->bank.loaded ? 1u : 0u);
+            return AIDAX_OK;
+        });
+    }
+    if (b) {
+        // a pool model (or an unload) under a bank in use: the slots are variants of the model that plays
+        bool ok = b->n_assigned.load(std::memory_order_relaxed) == 0;
+        if (ok && b->n_loaded != 0) {
+            const ModelSlot& n = staged->slot;
+            ok = n.has_model && n.kind == ModelSlot::TABLE && n.kernel && n.kernel->fn_pipe_bank;
+            for (const BankSlot& k : b->slot)
+                if (ok && k.loaded) ok = !bank_arch_diff({ n.cell, n.hidden, n.input_size, n.model_sr }, { k.cell, k.hidden, k.input_size, k.model_sr });
+        }
+        if (!ok) return fail(AIDAX_ERR_STATE, "empty the model bank first (streams are assigned to it, or a loaded slot does not fit the model being committed)");
+    }
     return guarded([&]() { return commit_impl(*p, staged); });
+}
+
+AIDAX_API int aidax_model_bank_compatible(const aidax_model* pool_model, const aidax_model* m)
+{
+    if (!pool_model || !m) return fail(AIDAX_ERR_ARG, "null model");
+    if (!bank_table_model(*pool_model)) return fail(AIDAX_ERR_ARCH, "model bank: the pool model is not a one-layer LSTM / GRU model of the table");
+    if (!bank_table_model(*m)) return fail(AIDAX_ERR_ARCH, "model bank: the model is not a one-layer LSTM / GRU model of the table");
+    if (const char* f = bank_arch_diff({ pool_model->cell, pool_model->hidden, pool_model->input_size, pool_model->samplerate },
+                                       { m->cell, m->hidden, m->input_size, m->samplerate }))
+        return fail(AIDAX_ERR_ARCH, std::string("model bank: the models differ in ") + f);
+    return AIDAX_OK;
+}
+
+// Worker thread: the slot's weights in the pool model's layout, uploaded on the worker stream; the first call allocates the bank.
+AIDAX_API int aidax_pool_prepare_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m, aidax_staged** out)
+{
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (slot >= static_cast<uint32_t>(AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be 0 .. 63");
+    const ModelSlot& cur = p->cur;
+    if (!cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model: the bank holds variants of the pool model");
+    if (m) {
+        if (!bank_table_model(*m)) return fail(AIDAX_ERR_ARCH, "model bank: the model is not a one-layer LSTM / GRU model of the table");
+        if (cur.kind != ModelSlot::TABLE || !cur.kernel)
+            return fail(AIDAX_ERR_ARCH, std::string("model bank: the pool's model runs ") + aidax_pool_kernel_name(p) + " at this pool size, not a table kernel");
+        if (const char* f = bank_arch_diff({ cur.cell, cur.hidden, cur.input_size, cur.model_sr }, { m->cell, m->hidden, m->input_size, m->samplerate }))
+            return fail(AIDAX_ERR_ARCH, std::string("model bank: the model differs from the pool's model in ") + f);
+        if (!cur.kernel->fn_pipe_bank) return fail(AIDAX_ERR_ARCH, "model bank: this cell has no three-wave pipeline kernel (LSTM-64 / LSTM-80)");
+        if (pipe_lds_bytes(cur.hidden, p->max_frames) > 64 * 1024) return fail(AIDAX_ERR_ARCH, "model bank: the pool's max_frames is too large for the pipeline's LDS block buffer");
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        std::unique_ptr<aidax_staged, void (*)(aidax_staged*)> sg(new aidax_staged(), staged_release);
+        sg->device = p->device;
+        sg->n_streams = p->n_streams;
+        sg->is_bank = true;
+        sg->bank_slot = slot;
+        HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+        std::vector<float> wp;
+        if (m) {
+            BankSlot& k = sg->bank;
+            wp = pack_weights(*m);
+            const int alt = (m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;
+            if (static_cast<int>(wp.size()) != cur.kernel->pack_regs * kWave + m->hidden + 1 + alt) return fail(AIDAX_ERR_STATE, "weight pack size mismatch");
+            k.cell = m->cell; k.hidden = m->hidden; k.input_size = m->input_size; k.input_skip = m->input_skip;
+            k.in_gain = m->input_gain; k.out_gain = m->output_gain; k.model_sr = m->samplerate;
+            HIP_TRY(hipMalloc(&k.d_wpack, wp.size() * sizeof(float)));
+            HIP_TRY(hipMemcpyAsync(k.d_wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p->wq));
+            k.loaded = true;
+        }
+        if (!p->bank.load(std::memory_order_acquire)) {
+            // first use: the per-stream selection records, so that no audio-side call ever allocates
+            std::unique_ptr<ModelBank, void (*)(ModelBank*)> nb(new ModelBank(), [](ModelBank* x) { x->release(); delete x; });
+            nb->assign.assign(p->n_streams, AIDAX_MODEL_POOL);
+            nb->h_rec.assign(p->n_streams, ModelRec{});
+            HIP_TRY(hipMalloc(&nb->d_rec, sizeof(ModelRec) * p->n_streams));
+            HIP_TRY(hipMemsetAsync(nb->d_rec, 0, sizeof(ModelRec) * p->n_streams, p->wq));
+            for (int i = 0; i < kCtlRing; ++i) {
+                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nb->ring[i]), sizeof(ModelRec) * p->n_streams, hipHostMallocDefault));
+                HIP_TRY(hipEventCreateWithFlags(&nb->ev[i], hipEventDisableTiming));
+            }
+            HIP_TRY(hipStreamSynchronize(p->wq));
+            p->bank.store(nb.release(), std::memory_order_release);
+        }
+        HIP_TRY(hipStreamSynchronize(p->wq));              // `wp` is pageable; the audio side must find the slot complete
+        *out = sg.release();
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_set_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m)
+{
+    aidax_staged* sg = nullptr;
+    int rc = aidax_pool_prepare_model_slot(p, slot, m, &sg);
+    if (rc != AIDAX_OK) return rc;
+    rc = aidax_pool_commit_model(p, sg);
+    aidax_staged_free(sg);
+    return rc;
+}
+
+// Audio side, between passes: the stream becomes a fresh DynamicModel of the slot's model (:822-825, :1046-1079) — host records plus
+// the launches aidax_pool_reset_stream issues for the same purpose, on the pool's stream behind every pass issued so far.
+AIDAX_API int aidax_pool_assign_model(aidax_pool* p, int32_t stream, int32_t slot, int start_mode)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range (one stream per call)");
+    if (slot != AIDAX_MODEL_POOL && (slot < 0 || slot >= AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be the pool model (-1) or 0 .. 63");
+    if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
+    ModelBank* b = p->bank.load(std::memory_order_acquire);
+    if (slot >= 0 && (!b || !b->slot[slot].loaded)) return fail(AIDAX_ERR_STATE, "model bank slot " + std::to_string(slot) + " is empty");
+    if (!p->cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model");
+    const uint32_t s = static_cast<uint32_t>(stream);
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        p->enter_stream(p->q);
+        const ModelSlot& m = p->cur;
+        HIP_TRY(launch_reset_for_model(p->d_st + s, m.d_nn + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), p->q));
+        if (start_mode == AIDAX_START_WARMUP) {
+            const uint32_t chunk = p->launch_chunk(m, kWarmupFrames);
+            for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
+                LaunchArgs a = p->args(m, p->d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+                if (slot >= 0) { const BankSlot& k = b->slot[slot]; a.wpack = k.d_wpack; a.in_gain = k.in_gain; a.out_gain = k.out_gain; a.input_skip = k.input_skip; }
+                a.ctl += s; a.st += s; a.nn += static_cast<size_t>(s) * m.nn_stride;
+                a.n_streams = 1;
+                HIP_TRY(p->launch(m, a, p->q));
+            }
+        }
+        if (!b) return AIDAX_OK;                            // (no bank: the stream was and stays on the pool model)
+        const int32_t old = b->assign[s];
+        if (old >= 0) { --b->users[old]; b->n_assigned.fetch_sub(1, std::memory_order_relaxed); }
+        b->assign[s] = slot;
+        if (slot >= 0) {
+            ++b->users[slot];
+            if (b->n_assigned.fetch_add(1, std::memory_order_relaxed) == 0) {
+                // the bank comes into force: the records of the streams on the pool model are written now, around the model that plays
+                // (it cannot change while a stream is assigned)
+                const ModelRec pr = p->pool_rec();
+                for (uint32_t i = 0; i < p->n_streams; ++i) b->h_rec[i] = pr;
+                b->mark_dirty(0, p->n_streams - 1);
+            }
+            const BankSlot& k = b->slot[slot];
+            ModelRec r{};
+            r.wpack = k.d_wpack; r.in_gain = k.in_gain; r.out_gain = k.out_gain; r.input_skip = k.input_skip;
+            b->h_rec[s] = r;
+        } else {
+            b->h_rec[s] = p->pool_rec();
+        }
+        b->mark_dirty(s, s);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_stream_model(const aidax_pool* p, uint32_t stream, int32_t* slot)
+{
+    if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const ModelBank* b = p->bank.load(std::memory_order_acquire);
+    *slot = b ? b->assign[stream] : AIDAX_MODEL_POOL;
+    return AIDAX_OK;
 }
 
 AIDAX_API void aidax_staged_free(aidax_staged* staged) { staged_release(staged); }
@@ -1310,6 +1587,7 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
                 const uint32_t chunk = p->launch_chunk(m, kWarmupFrames);
                 for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
                     LaunchArgs a = p->args(m, p->d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+                    p->apply_stream_model(a, stream);              // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
                     a.ctl += stream; a.st += stream; a.nn += static_cast<size_t>(stream) * m.nn_stride;
                     a.n_streams = 1;
                     HIP_TRY(p->launch(m, a, p->q));
@@ -1741,6 +2019,7 @@ AIDAX_API const char* aidax_pool_kernel_name(const aidax_pool* p)
     if (m.kind == ModelSlot::QUAD) return "k_chain+k_quad";
     if (m.kind == ModelSlot::CONV && m.conv_ms && m.conv_fused && m.cdesc.st_ok && p->max_frames >= 64) return "k_conv_st";      // (what a block of 64 / 128 / 256 frames runs; every other length: k_conv_ms)
     if (m.kind == ModelSlot::CONV) return m.conv_ms ? (m.conv_fused ? "k_conv_ms" : "k_chain+k_conv_ms") : m.conv_fused ? "k_conv_mfma" : m.conv_mfma ? "k_chain+k_conv_mfma" : "k_conv";
+    if (p->bank_in_force()) return m.kernel->name_pipe_bank;      // a stream plays a bank slot: every pass is the bank kernel's
     const int form = p->chain_form(m);
     // (form 1: what a block of the pool's full length runs with the controls as they stand — k_*_pipe4 where it serves, k_*_pipe otherwise)
     if (form == 1 && p->pipe4_serves(m, p->max_frames, m.input_size)) return m.kernel->name_pipe4;

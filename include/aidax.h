@@ -203,6 +203,60 @@ AIDAX_API int  aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged);
 AIDAX_API void aidax_staged_free(aidax_staged* staged);
 AIDAX_API int  aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode);
 
+/* Per-stream amp models: a bank of AIDAX_MODEL_SLOTS slots per pool beside the pool model above, and per stream the model it plays:
+ * AIDAX_MODEL_POOL (the default: whatever aidax_pool_set_model / commit_model put there) or a bank slot 0 .. 63. The bank holds WEIGHT
+ * VARIANTS OF THE POOL MODEL'S ARCHITECTURE: a slot's model has the pool model's cell, hidden size, input_size and sample rate, and brings
+ * its own weights, in_gain, out_gain and in_skip. The pool model keeps deciding everything else (state layout, the PARAM smoothers' time
+ * constant, the launch geometry). Opt-in: a pool that never prepares a slot allocates nothing for the bank, and while no stream is assigned
+ * to a slot (slots loaded or not) every pass issues exactly the launches it issues without a bank, bit for bit. While at least one stream
+ * is assigned, every pass of the pool — any block length, zero-length and ragged blocks, any pool size, prefix passes, passes under a rate
+ * adapter — goes out as ONE launch of k_lstm_pipe_bank<H> / k_gru_pipe_bank<H> (the three-wave pipeline with every workgroup reading the
+ * model of its own stream; streams on AIDAX_MODEL_POOL read the pool model's), and aidax_pool_kernel_name says so. A banked stream's
+ * output and state are bit-identical to the same stream of a pool whose pool model is that file, run on k_*_pipe.
+ * aidax_model_bank_compatible    pure (no device, any thread): AIDAX_OK when both models are one-layer LSTM / GRU models of the table with
+ *                                the same cell, hidden size, input_size and sample rate; else AIDAX_ERR_ARCH with the differing field in
+ *                                aidax_last_error(). in_skip, in_gain and out_gain may differ: they travel with the slot.
+ * aidax_pool_prepare_model_slot  WORKER thread: packs m's weights in the pool model's layout, allocates and uploads them on the worker
+ *                                stream, blocks until complete; m == NULL prepares emptying the slot. The first successful call also
+ *                                allocates the per-stream selection records, so no audio-side call ever allocates. Commit with
+ *                                aidax_pool_commit_model: the staged object knows its slot and afterwards holds what the commit retired,
+ *                                behind the usual fence (aidax_staged_free at any time after the commit). AIDAX_ERR_ARG for slot >=
+ *                                AIDAX_MODEL_SLOTS; AIDAX_ERR_STATE when the pool has no model; AIDAX_ERR_ARCH, with the reason, when m
+ *                                is not compatible with the pool's model, when the pool's model is not served as a table model at this
+ *                                pool size (a pool on k_quad or a matrix-core kernel carries no bank), when the cell has no three-wave
+ *                                pipeline (LSTM-64 / 80), or when max_frames does not fit the pipeline's LDS.
+ * aidax_pool_set_model_slot      prepare_model_slot + commit + free in one blocking call.
+ * aidax_pool_assign_model        AUDIO side, between passes: ONE stream (AIDAX_ALL_STREAMS is not accepted) plays `slot` from the next
+ *                                pass on. No allocation, no free, no wait: host records plus the launches aidax_pool_reset_stream issues,
+ *                                on the pool's stream. The stream gets what the reference's swap gives an instance (:822-825, :868-875,
+ *                                :1046-1079): a fresh DynamicModel (recurrent state zero, PARAM smoothers rebuilt around the targets they
+ *                                hold now, paramFirstRun set) and, with AIDAX_START_WARMUP, 2048 zeros through applyModel with the NEW
+ *                                slot's weights and gains; the seven biquad memories and both gain smoothers stay, and `loading` is not
+ *                                touched (a host that wants the reference's mute around the swap uses aidax_pool_set_loading). Assigning
+ *                                the slot a stream already has is a reload: still a fresh DynamicModel. AIDAX_ERR_ARG for a stream or
+ *                                slot out of range or a bad start_mode, AIDAX_ERR_STATE for an empty slot or a pool without a model.
+ * aidax_pool_stream_model        the assignment of one stream (AIDAX_ERR_ARG for a stream out of range).
+ * The rules:
+ *  - A commit into a slot (content or NULL) while any stream is assigned to it returns AIDAX_ERR_STATE and changes nothing. To replace a
+ *    model: load a free slot, move the streams, empty the old one.
+ *  - aidax_pool_commit_model of a POOL model (or of an unload) returns AIDAX_ERR_STATE ("empty the model bank first") and changes nothing
+ *    while any stream is assigned to a slot, or while a loaded slot is not compatible with the model being committed (for an unload: while
+ *    any slot is loaded). With an empty bank it behaves bit for bit as without one.
+ *  - The commit of a slot re-checks compatibility against the pool's current model (host integers only): AIDAX_ERR_STATE if the pool
+ *    model changed since the prepare.
+ *  - aidax_pool_reset_stream keeps the assignment and warms up with the assigned slot's weights, gains and skip.
+ *  - Each pass runs with the assignments and slot contents in force when it was issued (also the blocks in flight through
+ *    aidax_pool_submit*, passes on a caller's stream, prefix passes and passes under the rate adapter): the per-stream records reach the
+ *    device stream-ordered from a ring of four pinned snapshots, like the control records.
+ *  - k_*_pipe4, the split form, k_quad and the matrix-core kernels are not used while the bank is in force. */
+#define AIDAX_MODEL_SLOTS 64
+enum { AIDAX_MODEL_POOL = -1 };
+AIDAX_API int  aidax_model_bank_compatible(const aidax_model* pool_model, const aidax_model* m);
+AIDAX_API int  aidax_pool_prepare_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m, aidax_staged** out);
+AIDAX_API int  aidax_pool_set_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m);
+AIDAX_API int  aidax_pool_assign_model(aidax_pool* p, int32_t stream, int32_t slot, int start_mode);
+AIDAX_API int  aidax_pool_stream_model(const aidax_pool* p, uint32_t stream, int32_t* slot);
+
 /* Cabinet impulse response (IR): an optional last stage of every stream's run(), after the master gain ramp (rt-neural-generic.cpp:654-655).
  * A pool holds one pool IR h[0..L-1] (fp32, 1 <= L <= 8192: the length of the cabinet IRs the reference ships next to its models; up to 65536
  * in a pool whose IR capacity was raised, see "IR capacity" below) and a bank
@@ -405,14 +459,14 @@ AIDAX_API int      aidax_rate_process_device(aidax_rate* r, const float* d_in, f
 AIDAX_API int      aidax_rate_reset_stream(aidax_rate* r, uint32_t stream);
 
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, set_ir_fade, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_model, set_ir_fade, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
- * prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
+ * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
  * before the two threads start; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync / aidax_rate_process wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, and a changed IR plan (after an assign_ir or a commit_ir), go
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir or a commit_ir) and changed model-bank records (after an assign_model), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
