@@ -1,10 +1,11 @@
 // aidax_hip_host.h — what every host source that issues HIP calls for a pool shares: the error plumbing (HIP_TRY throws HipFail, guarded
 // turns it into AIDAX_ERR_DEVICE) and, in the test build, the call counting behind aidax_test_hip_calls. Include it last: its macros
-// rename the calls of the source that follow it.
+// rename the calls of the source that follow it (aidax_snapshot_ring.h and aidax_model_bank.h include it and are counted: they go last too).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
 
+#include <cstdio>
 #include <cstring>
 #include <sstream>
 #include <stdexcept>
@@ -26,6 +27,22 @@ inline void note_hip_call(const char* name)
     for (int i = 0; i < t.used; ++i)
         if (std::strcmp(t.name[i], name) == 0) { ++t.n[i]; return; }
     if (t.used < 48) { t.name[t.used] = name; t.n[t.used++] = 1; }
+}
+// aidax_test_hip_calls: the calling thread's counted calls since the last read, one "name count" line each, into `buf` (NUL-terminated,
+// cut at `cap` bytes); returns the number of entry points listed and starts the count afresh
+inline int read_hip_calls(char* buf, uint32_t cap)
+{
+    HipCallTable& t = hip_call_table();
+    size_t at = 0;
+    if (buf && cap) buf[0] = '\0';
+    for (int i = 0; i < t.used; ++i)
+        if (buf && at < cap) {
+            const int w = std::snprintf(buf + at, cap - at, "%s %llu\n", t.name[i], static_cast<unsigned long long>(t.n[i]));
+            if (w > 0) at += static_cast<size_t>(w);
+        }
+    const int n = t.used;
+    t.used = 0;
+    return n;
 }
 }  // namespace aidax
 #define AIDAX_COUNTED(fn, ...) (aidax::note_hip_call(#fn), ::fn(__VA_ARGS__))

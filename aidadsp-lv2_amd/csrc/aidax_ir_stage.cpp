@@ -4,24 +4,19 @@
 #include <memory>
 
 #include "aidax_ir_stage.h"
-#include "aidax_hip_host.h"
+#include "aidax_snapshot_ring.h"
 
 namespace aidax {
 
-constexpr int kPlanRing = 4;                             // pinned snapshots of the plan in flight
-
 // Per stream a ring of the last R >= capacity + max_frames dry samples (aidax_kernels.h: IrArgs), fed by every pass (k_ir_append), and
 // the K split's partial sums (aidax_ir_mfma.hip). With it, the device copy of the plan (IrPlan's layout) and the pinned snapshots it
-// is uploaded from, stream-ordered with the passes like the pool's control records.
+// is uploaded from, stream-ordered with the passes (aidax_snapshot_ring.h).
 struct IrHistory {
     float* ring = nullptr;
     float* part = nullptr;
     uint32_t ring_row = 0, mask = 0, split_cap = 1;
     uint8_t* d_plan = nullptr;
-    uint8_t* h_plan[kPlanRing] = {};
-    hipEvent_t plan_ev[kPlanRing] = {};
-    bool plan_used[kPlanRing] = {};
-    int plan_next = 0;                   // (audio side)
+    SnapshotRing plan_ring;              // (audio side)
     float* side = nullptr;               // the IR fade's side buffer, [n_streams][max_frames]: what the fade-out section of a fade pass convolves into
 };
 
@@ -32,10 +27,7 @@ static void free_ir_history(IrHistory* h)
     if (h->part) (void)hipFree(h->part);
     if (h->d_plan) (void)hipFree(h->d_plan);
     if (h->side) (void)hipFree(h->side);
-    for (int k = 0; k < kPlanRing; ++k) {
-        if (h->h_plan[k]) (void)hipHostFree(h->h_plan[k]);
-        if (h->plan_ev[k]) (void)hipEventDestroy(h->plan_ev[k]);
-    }
+    h->plan_ring.release();
     delete h;
 }
 
@@ -67,10 +59,7 @@ void IrStage::prepare(const float* taps, uint32_t n_taps, IrSlot& ir)
         HIP_TRY(hipMalloc(&h->side, sizeof(float) * block));
         const size_t plan_bytes = plan.plan_bytes();         // both sections, whether a fade length is set or not
         HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
-        for (int k = 0; k < kPlanRing; ++k) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h->h_plan[k]), plan_bytes, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&h->plan_ev[k], hipEventDisableTiming));
-        }
+        h->plan_ring.alloc(plan_bytes);
         HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, wq_));
         HIP_TRY(hipStreamSynchronize(wq_));
         pub_.store(h.release(), std::memory_order_release);
@@ -95,15 +84,9 @@ void IrStage::commit(int32_t slot, IrSlot& staged, hipEvent_t fence, hipStream_t
 // that no later rebuild touches while it is in flight
 void IrStage::flush_plan(hipStream_t s, bool any_pass)
 {
-    IrHistory* h = hist_;
     plan.rebuild(any_pass);
-    const int k = h->plan_next;
-    if (h->plan_used[k] && hipEventQuery(h->plan_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(h->plan_ev[k]));   // four rebuilds behind
-    const size_t bytes = plan.serialise(h->h_plan[k]);
-    HIP_TRY(hipMemcpyAsync(h->d_plan, h->h_plan[k], bytes, hipMemcpyHostToDevice, s));
-    HIP_TRY(hipEventRecord(h->plan_ev[k], s));
-    h->plan_used[k] = true;
-    h->plan_next = (k + 1) % kPlanRing;
+    const size_t bytes = plan.serialise(hist_->plan_ring.take());
+    hist_->plan_ring.send(hist_->d_plan, 0, bytes, s);
 }
 
 // k_ir_conv's arguments for one section of the plan, which lies at these offsets of the device copy

@@ -1,6 +1,6 @@
-// aidax_pool.cpp — the stream pool behind the C ABI: device residency, control
-// latching, model swap and the process launches. Host logic only; the kernels
-// are in aidax_kernels.hip. No CPU fallback: any HIP failure is AIDAX_ERR_DEVICE.
+// aidax_pool.cpp — the stream pool behind the C ABI: device residency, control latching, model swap and the process launches, around
+// the cabinet IR stage (aidax_ir_stage.h) and the model bank (aidax_model_bank.h); records reach the device through aidax_snapshot_ring.h.
+// Host logic only; the kernels are in aidax_kernels.hip. No CPU fallback: any HIP failure is AIDAX_ERR_DEVICE.
 #include <hip/hip_runtime_api.h>
 
 #include <algorithm>
@@ -16,8 +16,7 @@
 #include <string>
 
 #include "aidax_ir_stage.h"
-#include "aidax_hip_host.h"
-
+#include "aidax_model_bank.h"
 
 using namespace aidax;
 
@@ -280,59 +279,10 @@ struct ModelSlot {
     int gru_gs = 0;                  // ... as k_gru_gs (recurrent product on the bf16 matrix pipe, operands split into three bf16 terms): 6 or 9 term products; 0: the fp32 kernel
 
     float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
+    ModelRec rec() const { return model_rec(d_wpack, in_gain, out_gain, input_skip); }      // what a banked stream on this model reads of it
+    BankArch arch() const { return { cell, hidden, input_size, model_sr, has_model && kind == TABLE && kernel && kernel->fn_pipe_bank }; }
 };
 
-constexpr int kCtlRing = 4;                              // pinned snapshots of the control records in flight
-
-// The model bank (include/aidax.h, "Per-stream amp models"): weight variants of the pool model's architecture, one per slot, and per
-// stream the slot it plays. A slot's content is what a table model's prepare uploads (pack_weights) plus the file's three scalars; the
-// architecture fields are kept for the host-only re-checks at commit time.
-struct BankSlot {
-    bool loaded = false;
-    float* d_wpack = nullptr;
-    int cell = 0, hidden = 0, input_size = 0, input_skip = 0;
-    float in_gain = 1.f, out_gain = 1.f, model_sr = 48000.f;
-};
-// Allocated by the first aidax_pool_prepare_model_slot (worker thread) and published through aidax_pool::bank; everything in it but
-// the allocation itself is the audio side's. The per-stream records (h_rec, d_rec) are valid while a stream is assigned to a slot —
-// the assignment that makes the first one rewrites them all — and reach the device like the control records: by dirty range from a
-// ring of pinned snapshots, on the stream of the pass that follows.
-struct ModelBank {
-    BankSlot slot[AIDAX_MODEL_SLOTS];
-    uint32_t users[AIDAX_MODEL_SLOTS] = {};              // streams assigned to each slot
-    uint32_t n_loaded = 0;
-    std::atomic<uint32_t> n_assigned{0};                 // streams on any slot (read by aidax_pool_kernel_name from other threads)
-    std::vector<int32_t> assign;                         // per stream: AIDAX_MODEL_POOL or a slot
-    std::vector<ModelRec> h_rec;
-    ModelRec* d_rec = nullptr;
-    ModelRec* ring[kCtlRing] = {};
-    hipEvent_t ev[kCtlRing] = {};
-    bool used[kCtlRing] = {};
-    int next = 0;
-    uint32_t dirty_lo = 1, dirty_hi = 0;
-    void mark_dirty(uint32_t lo, uint32_t hi)
-    {
-        if (dirty_lo > dirty_hi) { dirty_lo = lo; dirty_hi = hi; }
-        else { dirty_lo = std::min(dirty_lo, lo); dirty_hi = std::max(dirty_hi, hi); }
-    }
-    void release()
-    {
-        for (BankSlot& b : slot)
-            if (b.d_wpack) (void)hipFree(b.d_wpack);
-        if (d_rec) (void)hipFree(d_rec);
-        for (int k = 0; k < kCtlRing; ++k) {
-            if (ring[k]) (void)hipHostFree(ring[k]);
-            if (ev[k]) (void)hipEventDestroy(ev[k]);
-        }
-    }
-};
-// the fields two models must share to sit in one bank; nullptr: none differs
-struct BankArch { int cell, hidden, input_size; float sr; };
-const char* bank_arch_diff(const BankArch& a, const BankArch& b)
-{
-    return a.cell != b.cell ? "cell" : a.hidden != b.hidden ? "hidden" : a.input_size != b.input_size ? "input_size" : a.sr != b.sr ? "samplerate" : nullptr;
-}
-bool bank_table_model(const aidax_model& m) { return !is_conv_model(m) && !is_stack_model(m) && m.n_rnn == 1 && (m.cell == AIDAX_CELL_LSTM || m.cell == AIDAX_CELL_GRU); }
 constexpr size_t kStagingLimit = size_t(64) << 20;      // pinned staging per direction for aidax_pool_process
 constexpr size_t kZeroCopyLimit = size_t(64) << 10;     // blocks up to this size are read / written by the kernels in place in pinned host memory
 
@@ -348,10 +298,9 @@ struct aidax_staged {
     StreamState* d_pst = nullptr;    // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
     hipEvent_t fence = nullptr;      // recorded by the commit: everything that may still touch the retired buffers precedes it
     bool fenced = false;
-    bool is_ir = false;              // an IR on its way (aidax_pool_prepare_ir / _slot): `ir` instead of `slot`
-    int32_t ir_slot = AIDAX_IR_POOL; // ... for the pool IR or for this bank slot
+    enum Payload { MODEL, IR, BANK_SLOT } payload = MODEL;      // what is on its way: `slot`, `ir` (aidax_pool_prepare_ir / _slot) or `bank` (aidax_pool_prepare_model_slot)
+    int32_t ir_slot = AIDAX_IR_POOL; // IR: for the pool IR or for this bank slot
     aidax::IrSlot ir;
-    bool is_bank = false;            // a model-bank slot's content on its way (aidax_pool_prepare_model_slot): `bank` instead of `slot`
     uint32_t bank_slot = 0;
     aidax::BankSlot bank;
 };
@@ -446,43 +395,11 @@ struct aidax_pool {
     std::vector<uint8_t> loading;
     std::vector<uint8_t> forced_off;                     // the hub parks a stream (raw copy, state does not move) without touching its controls
     std::vector<StreamCtl> h_ctl;
-    uint32_t dirty_lo = 1, dirty_hi = 0;                 // control records to upload: [lo, hi], empty when lo > hi
-    StreamCtl* ctl_ring[kCtlRing] = {};
-    hipEvent_t ctl_ev[kCtlRing] = {};
-    bool ctl_used[kCtlRing] = {};
-    int ctl_next = 0;
+    DirtyRange ctl_dirty;                                // control records to upload
+    SnapshotRing ctl_ring;
 
     ModelSlot cur;
-    std::atomic<ModelBank*> bank{nullptr};               // the model bank (nullptr until the first aidax_pool_prepare_model_slot)
-    // is a stream assigned to a bank slot? Then every MODE_CHAIN pass is one launch of k_*_pipe_bank over the per-stream records
-    ModelBank* bank_in_force() const
-    {
-        ModelBank* b = bank.load(std::memory_order_acquire);
-        return b && b->n_assigned.load(std::memory_order_relaxed) != 0 ? b : nullptr;
-    }
-    ModelRec pool_rec() const { ModelRec r{}; r.wpack = cur.d_wpack; r.in_gain = cur.in_gain; r.out_gain = cur.out_gain; r.input_skip = cur.input_skip; return r; }
-    // the model stream `s` plays, into launch arguments built for the pool model (warm-ups of one stream)
-    void apply_stream_model(LaunchArgs& a, uint32_t s) const
-    {
-        const ModelBank* b = bank.load(std::memory_order_acquire);
-        if (!b || b->assign[s] < 0) return;
-        const BankSlot& k = b->slot[b->assign[s]];
-        a.wpack = k.d_wpack; a.in_gain = k.in_gain; a.out_gain = k.out_gain; a.input_skip = k.input_skip;
-    }
-    // upload the changed per-stream model records, stream-ordered with the pass that follows (flush_ctl's scheme)
-    void flush_bank(ModelBank& b, hipStream_t s)
-    {
-        if (b.dirty_lo > b.dirty_hi) return;
-        const int k = b.next;
-        if (b.used[k] && hipEventQuery(b.ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(b.ev[k]));
-        const size_t cnt = static_cast<size_t>(b.dirty_hi - b.dirty_lo) + 1;
-        std::memcpy(b.ring[k] + b.dirty_lo, b.h_rec.data() + b.dirty_lo, cnt * sizeof(ModelRec));
-        HIP_TRY(hipMemcpyAsync(b.d_rec + b.dirty_lo, b.ring[k] + b.dirty_lo, cnt * sizeof(ModelRec), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(b.ev[k], s));
-        b.used[k] = true;
-        b.next = (k + 1) % kCtlRing;
-        b.dirty_lo = 1; b.dirty_hi = 0;
-    }
+    ModelBankStage bank;             // the model bank (aidax_model_bank.h; nothing until the first aidax_pool_prepare_model_slot)
     int tune = 0;                    // AIDAX_TUNE (measurement switches, see LaunchArgs)
     int cus = 0;                     // compute units of the device (form selection)
     int force_form = 0;              // AIDAX_KERNEL=wave|pipe|split|valu|mfma|quad overrides the heuristic (A/B testing)
@@ -523,7 +440,7 @@ struct aidax_pool {
     // does a MODE_CHAIN pass of this slot consist of one launch (it may then read and write host memory in place)?
     bool single_launch(const ModelSlot& m) const
     {
-        if (&m == &cur && bank_in_force()) return true;
+        if (&m == &cur && bank.in_force()) return true;
         if (!m.has_model) return chain_form(m) != 2;
         switch (m.kind) {
         case ModelSlot::TABLE: return chain_form(m) != 2;
@@ -558,16 +475,11 @@ struct aidax_pool {
     mutable uint32_t* pass_word = nullptr;   // aidax_pool_process -> launch(): the completion word and the number to write, for a pass of one workgroup
     mutable uint32_t pass_seq = 0;
     mutable bool pass_word_taken = false;
-    void mark_dirty(uint32_t lo, uint32_t hi)
-    {
-        if (dirty_lo > dirty_hi) { dirty_lo = lo; dirty_hi = hi; }
-        else { dirty_lo = std::min(dirty_lo, lo); dirty_hi = std::max(dirty_hi, hi); }
-    }
     void refresh_ctl(uint32_t s)
     {
         build_stream_ctl(controls[s], host_sr, cur.has_model, loading[s] != 0, gain_coef, cur.p_den(), &h_ctl[s]);
         if (forced_off[s]) h_ctl[s].flags &= ~static_cast<uint32_t>(CTL_ENABLED);
-        mark_dirty(s, s);
+        ctl_dirty.mark(s, s);
     }
     void refresh_all()
     {
@@ -582,7 +494,7 @@ struct aidax_pool {
         }
         for (uint32_t s = 0; s < n_streams; ++s)
             if (forced_off[s]) h_ctl[s].flags &= ~static_cast<uint32_t>(CTL_ENABLED);
-        mark_dirty(0, n_streams - 1);
+        ctl_dirty.mark(0, n_streams - 1);
     }
     // the fields of a control record that depend on the model and on `loading`, without redesigning the filters
     void patch_model_fields(uint32_t s)
@@ -596,19 +508,7 @@ struct aidax_pool {
     }
     // Upload the changed control records, stream-ordered with the pass that follows. The records leave from a
     // ring of pinned snapshots, so the copy is asynchronous and a later set_controls cannot overtake it.
-    void flush_ctl(hipStream_t s)
-    {
-        if (dirty_lo > dirty_hi) return;
-        const int k = ctl_next;
-        if (ctl_used[k] && hipEventQuery(ctl_ev[k]) != hipSuccess) HIP_TRY(hipEventSynchronize(ctl_ev[k]));   // four uploads behind: not seen in practice
-        const size_t cnt = static_cast<size_t>(dirty_hi - dirty_lo) + 1;
-        std::memcpy(ctl_ring[k] + dirty_lo, h_ctl.data() + dirty_lo, cnt * sizeof(StreamCtl));
-        HIP_TRY(hipMemcpyAsync(d_ctl + dirty_lo, ctl_ring[k] + dirty_lo, cnt * sizeof(StreamCtl), hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ctl_ev[k], s));
-        ctl_used[k] = true;
-        ctl_next = (k + 1) % kCtlRing;
-        dirty_lo = 1; dirty_hi = 0;
-    }
+    void flush_ctl(hipStream_t s) { ctl_ring.upload_dirty(d_ctl, h_ctl.data(), ctl_dirty, s); }
     // Passes and control pokes are issued in program order by the audio side but may sit on two streams (the pool's
     // own and one handed to aidax_pool_process_device): moving from one to the other puts an event edge between them.
     void enter_stream(hipStream_t s)
@@ -622,11 +522,11 @@ struct aidax_pool {
     LaunchArgs args(const ModelSlot& m, StreamState* st, const float* in, float* out, uint32_t n_frames, int mode) const
     {
         LaunchArgs a{};
-        a.ctl = d_ctl; a.st = st; a.nn = m.d_nn; a.wpack = m.d_wpack;
+        a.ctl = d_ctl; a.st = st; a.nn = m.d_nn;
         a.in = in; a.out = out;
         a.n_streams = n_streams; a.n_frames = n_frames; a.nn_stride = m.nn_stride;
-        a.mode = mode; a.input_size = m.input_size; a.input_skip = m.input_skip;
-        a.in_gain = m.in_gain; a.out_gain = m.out_gain;
+        a.mode = mode; a.input_size = m.input_size;
+        apply_model_rec(a, m.rec());
         a.tune = tune;
         return a;
     }
@@ -639,6 +539,13 @@ struct aidax_pool {
     }
     hipError_t launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s) const
     {
+        // the split form of a MODE_CHAIN pass: packed chains in -> out, the model's kernel in place (none for a block of no frames), packed chains
+        auto between_chains = [&](auto&& model_launch) {
+            hipError_t e = launch_chain_pass(true, a, s);
+            if (e == hipSuccess && a.n_frames != 0) e = model_launch();
+            if (e == hipSuccess) e = launch_chain_pass(false, a, s);
+            return e;
+        };
         if (m.has_model && m.kind == ModelSlot::MFMA) {
             // split form around the matrix-core kernel: packed chains in -> out, applyModel in place, packed chains
             // k_mfma_lp only for the passes themselves: warm-ups (worker stream, next to the passes) and the bare-model
@@ -685,17 +592,11 @@ struct aidax_pool {
                 const hipError_t e = m.lp_split ? launch_ls(true) : launch_mfma_lp_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, s, true);
                 if (!refused(e)) return e;
             }
-            hipError_t e = launch_chain_pass(true, a, s);
-            if (e == hipSuccess && a.n_frames != 0) e = model_kernel();
-            if (e == hipSuccess) e = launch_chain_pass(false, a, s);
-            return e;
+            return between_chains(model_kernel);
         }
         if (m.has_model && m.kind == ModelSlot::QUAD) {
             if (a.mode != MODE_CHAIN) return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s);
-            hipError_t e = launch_chain_pass(true, a, s);
-            if (e == hipSuccess && a.n_frames != 0) e = launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s);
-            if (e == hipSuccess) e = launch_chain_pass(false, a, s);
-            return e;
+            return between_chains([&] { return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s); });
         }
         if (m.has_model && m.kind == ModelSlot::STACK) return launch_stack_kernel(a, m.sdesc, s);
         if (m.has_model && m.kind == ModelSlot::CONV && m.conv_mfma) {
@@ -718,24 +619,27 @@ struct aidax_pool {
                 }
                 return e;
             }
-            hipError_t e = launch_chain_pass(true, a, s);
-            if (e == hipSuccess && a.n_frames != 0) e = conv_launch(a, false);
-            if (e == hipSuccess) e = launch_chain_pass(false, a, s);
-            return e;
+            return between_chains([&] { return conv_launch(a, false); });
         }
         if (m.has_model && m.kind == ModelSlot::CONV) return launch_conv_kernel(a, m.cdesc, s);
-        if (a.bank) {
-            // the model bank in force (pool_process_prefix set the records): the whole pass is one launch of k_*_pipe_bank, whatever form
-            // the pool model alone would take; the pass's end marker rides on it as on k_*_pipe
+        // A one-launch pass takes its end markers with it: the pipelined host path's "pass done" event rides on the dispatch (it saves the
+        // marker packet behind the kernel), and the blocking path's completion word is written by the one workgroup of a one-stream pool itself
+        auto take_end_markers = [&](LaunchArgs& b) {
             hipEvent_t done = pass_done;
             pass_done = nullptr;
             pass_done_taken = done != nullptr;
-            LaunchArgs b = a;
-            if (pass_word && a.n_streams == 1 && a.n_frames != 0) {
+            if (pass_word && b.n_streams == 1 && b.n_frames != 0) {
                 b.done_word = pass_word; b.done_seq = pass_seq;
                 pass_word = nullptr;
                 pass_word_taken = true;
             }
+            return done;
+        };
+        if (a.bank) {
+            // the model bank in force (pool_process_prefix set the records): the whole pass is one launch of k_*_pipe_bank, whatever form
+            // the pool model alone would take
+            LaunchArgs b = a;
+            hipEvent_t done = take_end_markers(b);
             return launch_pipe_bank_kernel(m.kernel, b, s, done);
         }
         const int form = a.mode == MODE_CHAIN ? chain_form(m) : 0;
@@ -745,32 +649,39 @@ struct aidax_pool {
             return launch_q4_kernel(m.hidden, b, s);
         }
         if (form == 1) {
-            // (the pipelined host path hands the pass its "pass done" event: riding on the dispatch it saves the marker packet behind the kernel)
-            hipEvent_t done = pass_done;
-            pass_done = nullptr;
-            pass_done_taken = done != nullptr;
             LaunchArgs b = a;
-            if (pass_word && a.n_streams == 1 && a.n_frames != 0) {      // ... or the blocking path's completion word, written by the one workgroup itself
-                b.done_word = pass_word; b.done_seq = pass_seq;
-                pass_word = nullptr;
-                pass_word_taken = true;
-            }
+            hipEvent_t done = take_end_markers(b);
             if (!pipe4_serves(m, a.n_frames, a.input_size)) return launch_pipe_kernel(m.kernel, b, s, done);
             return launch_pipe4_kernel(m.kernel, b, s, done);
         }
         if (form == 2) return launch_split_kernels(m.has_model ? m.kernel : nullptr, a, s);
         return launch_stream_kernel(m.has_model ? m.kernel : nullptr, a, lds_bytes(m, a.mode == MODE_CHAIN ? a.n_frames : 0), s);
     }
-    void release()
+    // A fresh DynamicModel for stream s alone (:1035, :1053-1061), with START_WARMUP 2048 zeros through applyModel (:1077-1078): the launch
+    // arguments view the pool as one stream, which plays the model of `rec` (m's own, or a bank slot's weights, gains and skip)
+    void fresh_stream_model(const ModelSlot& m, uint32_t s, int start_mode, const ModelRec& rec, hipStream_t on) const
+    {
+        HIP_TRY(launch_reset_for_model(d_st + s, m.d_nn + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), on));
+        const uint32_t chunk = launch_chunk(m, kWarmupFrames);
+        for (uint32_t done = 0; start_mode == AIDAX_START_WARMUP && done < kWarmupFrames; done += chunk) {
+            LaunchArgs a = args(m, d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+            apply_model_rec(a, rec);
+            a.ctl += s; a.st += s; a.nn += static_cast<size_t>(s) * m.nn_stride;
+            a.n_streams = 1;
+            HIP_TRY(launch(m, a, on));
+        }
+    }
+    // an audio-side call that issues work on the pool's own stream, behind everything issued so far
+    template <class F> int on_own_stream(F&& f) { return guarded([&]() -> int { HIP_TRY(hipSetDevice(device)); enter_stream(q); return f(); }); }
+    void release()                   // (both callers delete the pool next: nothing is reset)
     {
         ir.release();
-        if (ModelBank* b = bank.exchange(nullptr)) { b->release(); delete b; }
+        bank.release();
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);
         if (cur.d_nn) (void)hipFree(cur.d_nn);
         if (cur.d_wpack) (void)hipFree(cur.d_wpack);
         if (cur.d_wq4) (void)hipFree(cur.d_wq4);
-        cur.d_wq4 = nullptr;
         if (cur.d_ring) (void)hipFree(cur.d_ring);
         if (cur.d_counters) (void)hipFree(cur.d_counters);
         if (cur.lp_owner) { lp_gate().release(device, cur.lp_owner); cur.lp_owner = nullptr; }
@@ -778,7 +689,6 @@ struct aidax_pool {
             if (const char* f = AIDAX_HOOK_ENV("AIDAX_LP_TRACE_FILE"))
                 if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(h_lp_fault + 16, 4, 1536, fp); std::fclose(fp); }
         if (h_lp_fault) (void)hipHostFree(h_lp_fault);
-        h_lp_fault = nullptr;
         for (const HostRange& r : host_ranges) (void)hipHostUnregister(r.base);
         host_ranges.clear();
         for (int k = 0; k < kPipeSets; ++k) {
@@ -792,25 +702,16 @@ struct aidax_pool {
         }
         if (pipe.q_up) (void)hipStreamDestroy(pipe.q_up);
         if (pipe.q_down) (void)hipStreamDestroy(pipe.q_down);
-        pipe = Pipeline{};
         if (h_done) (void)hipHostFree(h_done);
         if (d_in) (void)hipFree(d_in);
         if (d_out) (void)hipFree(d_out);
         if (h_in) (void)hipHostFree(h_in);
         if (h_out) (void)hipHostFree(h_out);
-        for (int k = 0; k < kCtlRing; ++k) {
-            if (ctl_ring[k]) (void)hipHostFree(ctl_ring[k]);
-            if (ctl_ev[k]) (void)hipEventDestroy(ctl_ev[k]);
-            ctl_ring[k] = nullptr; ctl_ev[k] = nullptr;
-        }
+        ctl_ring.release();
         if (ev_x) (void)hipEventDestroy(ev_x);
         if (ev_adopt) (void)hipEventDestroy(ev_adopt);
-        ev_adopt = nullptr;
         if (q) (void)hipStreamDestroy(q);
         if (wq) (void)hipStreamDestroy(wq);
-        d_ctl = nullptr; d_st = nullptr; cur.d_nn = nullptr; cur.d_wpack = nullptr; d_in = nullptr; d_out = nullptr;
-        cur.d_ring = nullptr; cur.d_counters = nullptr;
-        h_in = nullptr; h_out = nullptr; ev_x = nullptr; q = nullptr; wq = nullptr;
     }
 };
 
@@ -834,16 +735,23 @@ void staged_release(aidax_staged* s)
     delete s;
 }
 
+// worker side: an empty staged object of pool p, with the fence its commit will record
+using StagedPtr = std::unique_ptr<aidax_staged, void (*)(aidax_staged*)>;
+StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload)
+{
+    StagedPtr sg(new aidax_staged(), staged_release);
+    sg->device = p.device; sg->n_streams = p.n_streams; sg->payload = payload;
+    HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+    return sg;
+}
+
 // loadModelFromPath's device half (rt-neural-generic.cpp:1034-1079) into buffers of its own. Worker thread:
 // packs, allocates, uploads and warms up on the pool's worker stream and waits for it; touches nothing the
 // audio side uses except for reading each stream's PARAM targets (as work() reads them at :822-825).
 int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_staged** out)
 {
     HIP_TRY(hipSetDevice(p.device));
-    std::unique_ptr<aidax_staged, void (*)(aidax_staged*)> sg(new aidax_staged(), staged_release);
-    sg->device = p.device;
-    sg->n_streams = p.n_streams;
-    HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+    StagedPtr sg = new_staged(p, aidax_staged::MODEL);
     if (!m) {                                             // unload: an empty slot to swap in
         *out = sg.release();
         return AIDAX_OK;
@@ -1005,8 +913,6 @@ int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_stag
 // pool's stream; no allocation, no free, no wait.
 int commit_impl(aidax_pool& p, aidax_staged* sg)
 {
-    HIP_TRY(hipSetDevice(p.device));
-    p.enter_stream(p.q);
     if (sg->slot.has_model) HIP_TRY(launch_install_params(p.d_st, sg->d_pst, p.n_streams, p.q));
     HIP_TRY(hipEventRecord(sg->fence, p.q));              // the retired buffers are free once this has passed
     sg->fenced = true;
@@ -1016,7 +922,7 @@ int commit_impl(aidax_pool& p, aidax_staged* sg)
         p.loading[s] = loading;
         p.patch_model_fields(s);
     }
-    p.mark_dirty(0, p.n_streams - 1);
+    p.ctl_dirty.mark(0, p.n_streams - 1);
     return AIDAX_OK;
 }
 
@@ -1042,10 +948,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (p->h_lp_fault && *static_cast<volatile uint32_t*>(p->h_lp_fault) != 0) p->lp_off.store(true, std::memory_order_relaxed);
         LaunchArgs a = p->args(p->cur, p->d_st, d_in, d_out, n_frames, MODE_CHAIN);
         a.n_streams = n_active;
-        if (ModelBank* b = p->bank_in_force()) {                     // the records this pass plays, ahead of it on its stream
-            p->flush_bank(*b, s);
-            a.bank = b->d_rec;
-        }
+        if (p->bank.in_force()) a.bank = p->bank.flush(s);           // the records this pass plays, ahead of it on its stream
         // with an IR history the pass ends behind the IR stage: its end marker (the submit path's event, the blocking path's completion
         // word) is not handed to the model's launch but issued after the stage by the caller
         const bool ir_on = n_frames != 0 && p->ir.adopt();
@@ -1071,7 +974,7 @@ int pool_park_stream(aidax_pool* p, uint32_t s, bool parked)
     StreamCtl& o = p->h_ctl[s];
     if (!parked && p->controls[s].enabled > 0.5f) o.flags |= CTL_ENABLED;
     else o.flags &= ~static_cast<uint32_t>(CTL_ENABLED);
-    p->mark_dirty(s, s);
+    p->ctl_dirty.mark(s, s);
     return AIDAX_OK;
 }
 
@@ -1085,11 +988,7 @@ int pool_device(const aidax_pool* p) { return p->device; }
 uint32_t pool_max_frames(const aidax_pool* p) { return p->max_frames; }
 int pool_enter_own_stream(aidax_pool* p)
 {
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
-        return AIDAX_OK;
-    });
+    return p->on_own_stream([] { return AIDAX_OK; });
 }
 
 }  // namespace aidax
@@ -1167,10 +1066,7 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
                     }
                 }
             }
-            for (int k = 0; k < kCtlRing; ++k) {
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->ctl_ring[k]), sizeof(StreamCtl) * n_streams, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&p->ctl_ev[k], hipEventDisableTiming));
-            }
+            p->ctl_ring.alloc(sizeof(StreamCtl) * n_streams);
             p->ir.init(n_streams, max_frames, p->cus, p->wq);
             p->controls.resize(n_streams);
             for (auto& c : p->controls) aidax_controls_default(&c);
@@ -1220,55 +1116,23 @@ AIDAX_API int aidax_pool_prepare_model(aidax_pool* p, const aidax_model* m, int 
 AIDAX_API int aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged)
 {
     if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
-    if (staged->is_ir) return fail(AIDAX_ERR_ARG, "staged object holds an IR: commit it with aidax_pool_commit_ir");
+    if (staged->payload == aidax_staged::IR) return fail(AIDAX_ERR_ARG, "staged object holds an IR: commit it with aidax_pool_commit_ir");
     if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged model was committed already");
     if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged model belongs to another pool");
-    ModelBank* b = p->bank.load(std::memory_order_acquire);
-    if (staged->is_bank) {
+    ModelBank* b = p->bank.adopt();
+    if (staged->payload == aidax_staged::BANK_SLOT) {
         // a bank slot's content: host integers, then the swap and the fence behind everything that may still read the retired weights
-        const uint32_t k = staged->bank_slot;
         if (!b) return fail(AIDAX_ERR_STATE, "the pool has no model bank");
-        if (b->users[k] != 0) return fail(AIDAX_ERR_STATE, "model bank slot " + std::to_string(k) + " has streams assigned: move them first");
-        const ModelSlot& cur = p->cur;
-        if (staged->bank.loaded) {
-            const BankSlot& n = staged->bank;
-            if (!cur.has_model || cur.kind != ModelSlot::TABLE || !cur.kernel || !cur.kernel->fn_pipe_bank ||
-                bank_arch_diff({ cur.cell, cur.hidden, cur.input_size, cur.model_sr }, { n.cell, n.hidden, n.input_size, n.model_sr }))
-                return fail(AIDAX_ERR_STATE, "the pool's model changed since aidax_pool_prepare_model_slot: prepare the slot again");
-        }
-        return guarded([&]() -> int {
-            HIP_TRY(hipSetDevice(p->device));
-            p->enter_stream(p->q);
+        if (const int rc = b->may_commit_slot(staged->bank_slot, staged->bank, p->cur.arch())) return rc;
+        return p->on_own_stream([&]() -> int {
             HIP_TRY(hipEventRecord(staged->fence, p->q));
             staged->fenced = true;
-            std::swap(b->slot[k], staged->bank);
-            b->n_loaded += (b->slot[k].loaded ? 1u : 0u) - (staged->bank.loaded ? 1u : 0u);
+            b->commit_slot(staged->bank_slot, staged->bank);
             return AIDAX_OK;
         });
     }
-    if (b) {
-        // a pool model (or an unload) under a bank in use: the slots are variants of the model that plays
-        bool ok = b->n_assigned.load(std::memory_order_relaxed) == 0;
-        if (ok && b->n_loaded != 0) {
-            const ModelSlot& n = staged->slot;
-            ok = n.has_model && n.kind == ModelSlot::TABLE && n.kernel && n.kernel->fn_pipe_bank;
-            for (const BankSlot& k : b->slot)
-                if (ok && k.loaded) ok = !bank_arch_diff({ n.cell, n.hidden, n.input_size, n.model_sr }, { k.cell, k.hidden, k.input_size, k.model_sr });
-        }
-        if (!ok) return fail(AIDAX_ERR_STATE, "empty the model bank first (streams are assigned to it, or a loaded slot does not fit the model being committed)");
-    }
-    return guarded([&]() { return commit_impl(*p, staged); });
-}
-
-AIDAX_API int aidax_model_bank_compatible(const aidax_model* pool_model, const aidax_model* m)
-{
-    if (!pool_model || !m) return fail(AIDAX_ERR_ARG, "null model");
-    if (!bank_table_model(*pool_model)) return fail(AIDAX_ERR_ARCH, "model bank: the pool model is not a one-layer LSTM / GRU model of the table");
-    if (!bank_table_model(*m)) return fail(AIDAX_ERR_ARCH, "model bank: the model is not a one-layer LSTM / GRU model of the table");
-    if (const char* f = bank_arch_diff({ pool_model->cell, pool_model->hidden, pool_model->input_size, pool_model->samplerate },
-                                       { m->cell, m->hidden, m->input_size, m->samplerate }))
-        return fail(AIDAX_ERR_ARCH, std::string("model bank: the models differ in ") + f);
-    return AIDAX_OK;
+    if (const int rc = b ? b->may_commit_pool_model(staged->slot.arch()) : AIDAX_OK) return rc;
+    return p->on_own_stream([&] { return commit_impl(*p, staged); });
 }
 
 // Worker thread: the slot's weights in the pool model's layout, uploaded on the worker stream; the first call allocates the bank.
@@ -1279,63 +1143,33 @@ AIDAX_API int aidax_pool_prepare_model_slot(aidax_pool* p, uint32_t slot, const 
     if (slot >= static_cast<uint32_t>(AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be 0 .. 63");
     const ModelSlot& cur = p->cur;
     if (!cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model: the bank holds variants of the pool model");
-    if (m) {
-        if (!bank_table_model(*m)) return fail(AIDAX_ERR_ARCH, "model bank: the model is not a one-layer LSTM / GRU model of the table");
-        if (cur.kind != ModelSlot::TABLE || !cur.kernel)
-            return fail(AIDAX_ERR_ARCH, std::string("model bank: the pool's model runs ") + aidax_pool_kernel_name(p) + " at this pool size, not a table kernel");
-        if (const char* f = bank_arch_diff({ cur.cell, cur.hidden, cur.input_size, cur.model_sr }, { m->cell, m->hidden, m->input_size, m->samplerate }))
-            return fail(AIDAX_ERR_ARCH, std::string("model bank: the model differs from the pool's model in ") + f);
-        if (!cur.kernel->fn_pipe_bank) return fail(AIDAX_ERR_ARCH, "model bank: this cell has no three-wave pipeline kernel (LSTM-64 / LSTM-80)");
-        if (pipe_lds_bytes(cur.hidden, p->max_frames) > 64 * 1024) return fail(AIDAX_ERR_ARCH, "model bank: the pool's max_frames is too large for the pipeline's LDS block buffer");
-    }
+    const char* other_kernel = !m || (cur.kind == ModelSlot::TABLE && cur.kernel) ? nullptr : aidax_pool_kernel_name(p);
+    if (const int rc = m ? bank_may_stage(*m, cur.arch(), other_kernel, pipe_lds_bytes(cur.hidden, p->max_frames) <= 64 * 1024) : AIDAX_OK) return rc;
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
-        std::unique_ptr<aidax_staged, void (*)(aidax_staged*)> sg(new aidax_staged(), staged_release);
-        sg->device = p->device;
-        sg->n_streams = p->n_streams;
-        sg->is_bank = true;
+        StagedPtr sg = new_staged(*p, aidax_staged::BANK_SLOT);
         sg->bank_slot = slot;
-        HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
-        std::vector<float> wp;
-        if (m) {
-            BankSlot& k = sg->bank;
-            wp = pack_weights(*m);
-            const int alt = (m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;
-            if (static_cast<int>(wp.size()) != cur.kernel->pack_regs * kWave + m->hidden + 1 + alt) return fail(AIDAX_ERR_STATE, "weight pack size mismatch");
-            k.cell = m->cell; k.hidden = m->hidden; k.input_size = m->input_size; k.input_skip = m->input_skip;
-            k.in_gain = m->input_gain; k.out_gain = m->output_gain; k.model_sr = m->samplerate;
-            HIP_TRY(hipMalloc(&k.d_wpack, wp.size() * sizeof(float)));
-            HIP_TRY(hipMemcpyAsync(k.d_wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p->wq));
-            k.loaded = true;
-        }
-        if (!p->bank.load(std::memory_order_acquire)) {
-            // first use: the per-stream selection records, so that no audio-side call ever allocates
-            std::unique_ptr<ModelBank, void (*)(ModelBank*)> nb(new ModelBank(), [](ModelBank* x) { x->release(); delete x; });
-            nb->assign.assign(p->n_streams, AIDAX_MODEL_POOL);
-            nb->h_rec.assign(p->n_streams, ModelRec{});
-            HIP_TRY(hipMalloc(&nb->d_rec, sizeof(ModelRec) * p->n_streams));
-            HIP_TRY(hipMemsetAsync(nb->d_rec, 0, sizeof(ModelRec) * p->n_streams, p->wq));
-            for (int i = 0; i < kCtlRing; ++i) {
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&nb->ring[i]), sizeof(ModelRec) * p->n_streams, hipHostMallocDefault));
-                HIP_TRY(hipEventCreateWithFlags(&nb->ev[i], hipEventDisableTiming));
-            }
-            HIP_TRY(hipStreamSynchronize(p->wq));
-            p->bank.store(nb.release(), std::memory_order_release);
-        }
-        HIP_TRY(hipStreamSynchronize(p->wq));              // `wp` is pageable; the audio side must find the slot complete
+        const int alt = (m && m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;
+        p->bank.prepare(p->n_streams, m, m ? cur.kernel->pack_regs * kWave + m->hidden + 1 + alt : 0, sg->bank, p->wq);
         *out = sg.release();
         return AIDAX_OK;
     });
 }
 
+// The set-up side's one-call forms: prepared content (rc: its prepare's result) committed at once, and what the swap retired (or, on
+// failure, the unused content) freed
+static int commit_and_free(aidax_pool* p, int rc, aidax_staged* sg, int (*commit)(aidax_pool*, aidax_staged*))
+{
+    if (rc == AIDAX_OK) rc = commit(p, sg);
+    aidax_staged_free(sg);
+    return rc;
+}
+
 AIDAX_API int aidax_pool_set_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m)
 {
     aidax_staged* sg = nullptr;
-    int rc = aidax_pool_prepare_model_slot(p, slot, m, &sg);
-    if (rc != AIDAX_OK) return rc;
-    rc = aidax_pool_commit_model(p, sg);
-    aidax_staged_free(sg);
-    return rc;
+    const int rc = aidax_pool_prepare_model_slot(p, slot, m, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_model);
 }
 
 // Audio side, between passes: the stream becomes a fresh DynamicModel of the slot's model (:822-825, :1046-1079) — host records plus
@@ -1346,46 +1180,14 @@ AIDAX_API int aidax_pool_assign_model(aidax_pool* p, int32_t stream, int32_t slo
     if (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range (one stream per call)");
     if (slot != AIDAX_MODEL_POOL && (slot < 0 || slot >= AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be the pool model (-1) or 0 .. 63");
     if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
-    ModelBank* b = p->bank.load(std::memory_order_acquire);
+    ModelBank* b = p->bank.adopt();
     if (slot >= 0 && (!b || !b->slot[slot].loaded)) return fail(AIDAX_ERR_STATE, "model bank slot " + std::to_string(slot) + " is empty");
     if (!p->cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model");
     const uint32_t s = static_cast<uint32_t>(stream);
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
+    return p->on_own_stream([&]() -> int {
         const ModelSlot& m = p->cur;
-        HIP_TRY(launch_reset_for_model(p->d_st + s, m.d_nn + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), p->q));
-        if (start_mode == AIDAX_START_WARMUP) {
-            const uint32_t chunk = p->launch_chunk(m, kWarmupFrames);
-            for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
-                LaunchArgs a = p->args(m, p->d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
-                if (slot >= 0) { const BankSlot& k = b->slot[slot]; a.wpack = k.d_wpack; a.in_gain = k.in_gain; a.out_gain = k.out_gain; a.input_skip = k.input_skip; }
-                a.ctl += s; a.st += s; a.nn += static_cast<size_t>(s) * m.nn_stride;
-                a.n_streams = 1;
-                HIP_TRY(p->launch(m, a, p->q));
-            }
-        }
-        if (!b) return AIDAX_OK;                            // (no bank: the stream was and stays on the pool model)
-        const int32_t old = b->assign[s];
-        if (old >= 0) { --b->users[old]; b->n_assigned.fetch_sub(1, std::memory_order_relaxed); }
-        b->assign[s] = slot;
-        if (slot >= 0) {
-            ++b->users[slot];
-            if (b->n_assigned.fetch_add(1, std::memory_order_relaxed) == 0) {
-                // the bank comes into force: the records of the streams on the pool model are written now, around the model that plays
-                // (it cannot change while a stream is assigned)
-                const ModelRec pr = p->pool_rec();
-                for (uint32_t i = 0; i < p->n_streams; ++i) b->h_rec[i] = pr;
-                b->mark_dirty(0, p->n_streams - 1);
-            }
-            const BankSlot& k = b->slot[slot];
-            ModelRec r{};
-            r.wpack = k.d_wpack; r.in_gain = k.in_gain; r.out_gain = k.out_gain; r.input_skip = k.input_skip;
-            b->h_rec[s] = r;
-        } else {
-            b->h_rec[s] = p->pool_rec();
-        }
-        b->mark_dirty(s, s);
+        p->fresh_stream_model(m, s, start_mode, slot >= 0 ? ModelBank::rec_of(b->slot[slot]) : m.rec(), p->q);
+        if (b) b->assign_stream(s, slot, m.rec());          // (no bank: the stream was and stays on the pool model)
         return AIDAX_OK;
     });
 }
@@ -1394,7 +1196,7 @@ AIDAX_API int aidax_pool_stream_model(const aidax_pool* p, uint32_t stream, int3
 {
     if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
     if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
-    const ModelBank* b = p->bank.load(std::memory_order_acquire);
+    const ModelBank* b = p->bank.adopt();
     *slot = b ? b->assign[stream] : AIDAX_MODEL_POOL;
     return AIDAX_OK;
 }
@@ -1404,11 +1206,8 @@ AIDAX_API void aidax_staged_free(aidax_staged* staged) { staged_release(staged);
 AIDAX_API int aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode)
 {
     aidax_staged* sg = nullptr;
-    int rc = aidax_pool_prepare_model(p, m, start_mode, &sg);
-    if (rc != AIDAX_OK) return rc;
-    rc = aidax_pool_commit_model(p, sg);
-    aidax_staged_free(sg);                                  // what the swap retired (or, on failure, the unused model)
-    return rc;
+    const int rc = aidax_pool_prepare_model(p, m, start_mode, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_model);
 }
 
 // The cabinet IR, split between the threads like a model swap (IrStage::prepare on the worker, IrStage::commit on the audio thread).
@@ -1428,22 +1227,15 @@ static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint3
     }
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
-        std::unique_ptr<aidax_staged, void (*)(aidax_staged*)> sg(new aidax_staged(), staged_release);
-        sg->device = p->device;
-        sg->n_streams = p->n_streams;
-        sg->is_ir = true;
+        StagedPtr sg = new_staged(*p, aidax_staged::IR);
         sg->ir_slot = slot;
-        HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
         p->ir.prepare(taps, n_taps, sg->ir);
         *out = sg.release();
         return AIDAX_OK;
     });
 }
 
-AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
-{
-    return prepare_ir_impl(p, AIDAX_IR_POOL, taps, n_taps, samplerate, out);
-}
+AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out) { return prepare_ir_impl(p, AIDAX_IR_POOL, taps, n_taps, samplerate, out); }
 
 AIDAX_API int aidax_pool_prepare_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
 {
@@ -1457,12 +1249,10 @@ AIDAX_API int aidax_pool_prepare_ir_slot(aidax_pool* p, uint32_t slot, const flo
 AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
 {
     if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
-    if (!staged->is_ir) return fail(AIDAX_ERR_ARG, "staged object holds a model: commit it with aidax_pool_commit_model");
+    if (staged->payload != aidax_staged::IR) return fail(AIDAX_ERR_ARG, "staged object holds a model: commit it with aidax_pool_commit_model");
     if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged IR was committed already");
     if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged IR belongs to another pool");
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
+    return p->on_own_stream([&]() -> int {
         p->ir.commit(staged->ir_slot, staged->ir, staged->fence, p->q);
         staged->fenced = true;
         return AIDAX_OK;
@@ -1472,21 +1262,15 @@ AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
 AIDAX_API int aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate)
 {
     aidax_staged* sg = nullptr;
-    int rc = aidax_pool_prepare_ir(p, taps, n_taps, samplerate, &sg);
-    if (rc != AIDAX_OK) return rc;
-    rc = aidax_pool_commit_ir(p, sg);
-    aidax_staged_free(sg);
-    return rc;
+    const int rc = aidax_pool_prepare_ir(p, taps, n_taps, samplerate, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_ir);
 }
 
 AIDAX_API int aidax_pool_set_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate)
 {
     aidax_staged* sg = nullptr;
-    int rc = aidax_pool_prepare_ir_slot(p, slot, taps, n_taps, samplerate, &sg);
-    if (rc != AIDAX_OK) return rc;
-    rc = aidax_pool_commit_ir(p, sg);
-    aidax_staged_free(sg);
-    return rc;
+    const int rc = aidax_pool_prepare_ir_slot(p, slot, taps, n_taps, samplerate, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_ir);
 }
 
 // Audio thread: host assignments only (the plan is rebuilt by the next pass).
@@ -1537,28 +1321,10 @@ AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t
     return AIDAX_OK;
 }
 
-AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode)
-{
-    return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr);
-}
+AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode) { return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr); }
 
 #ifdef AIDAX_TEST_HOOKS
-// Test build only (not in include/aidax.h): the calling thread's counted calls since the last read, one "name count" line each, into
-// `buf` (NUL-terminated, cut at `cap` bytes); returns the number of entry points listed and starts the count afresh.
-AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap)
-{
-    HipCallTable& hip_calls = hip_call_table();
-    size_t at = 0;
-    if (buf && cap) buf[0] = '\0';
-    for (int i = 0; i < hip_calls.used; ++i)
-        if (buf && at < cap) {
-            const int w = std::snprintf(buf + at, cap - at, "%s %llu\n", hip_calls.name[i], static_cast<unsigned long long>(hip_calls.n[i]));
-            if (w > 0) at += static_cast<size_t>(w);
-        }
-    const int n = hip_calls.used;
-    hip_calls.used = 0;
-    return n;
-}
+AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap) { return read_hip_calls(buf, cap); }      // (test build only, not in include/aidax.h)
 #endif
 
 }  // extern "C"
@@ -1572,28 +1338,13 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
     if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
     if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
+    return p->on_own_stream([&]() -> int {
         const ModelSlot& m = p->cur;
         HIP_TRY(launch_init_streams(p->d_st + stream, 1, p->q));      // instantiate(), :283-321
         p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st + stream, p_targets[0], p_targets[1], p->q));
-        if (m.has_model) {
-            // a fresh DynamicModel for this stream only: the launch arguments view the pool as one stream
-            HIP_TRY(launch_reset_for_model(p->d_st + stream, m.d_nn + static_cast<size_t>(stream) * m.nn_stride, 1,
-                                           m.nn_stride, m.p_den(), p->q));
-            if (start_mode == AIDAX_START_WARMUP) {
-                const uint32_t chunk = p->launch_chunk(m, kWarmupFrames);
-                for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
-                    LaunchArgs a = p->args(m, p->d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
-                    p->apply_stream_model(a, stream);              // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
-                    a.ctl += stream; a.st += stream; a.nn += static_cast<size_t>(stream) * m.nn_stride;
-                    a.n_streams = 1;
-                    HIP_TRY(p->launch(m, a, p->q));
-                }
-            }
-        }
+        const ModelBank* b = p->bank.adopt();                         // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
+        if (m.has_model) p->fresh_stream_model(m, stream, start_mode, b && b->assign[stream] >= 0 ? ModelBank::rec_of(b->slot[b->assign[stream]]) : m.rec(), p->q);
         p->loading[stream] = m.has_model ? 0 : 1;
         p->refresh_ctl(stream);
         return AIDAX_OK;
@@ -1644,9 +1395,7 @@ bool pool_has_model(const aidax_pool* p) { return p->cur.has_model; }
 int pool_peek_stream_state(aidax_pool* p, uint32_t stream, StreamState* pinned_out, void* done_event)
 {
     if (!p || !pinned_out || stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
+    return p->on_own_stream([&]() -> int {
         HIP_TRY(hipMemcpyAsync(pinned_out, p->d_st + stream, sizeof(StreamState), hipMemcpyDeviceToHost, p->q));
         HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(done_event), p->q));
         return AIDAX_OK;
@@ -1700,7 +1449,7 @@ AIDAX_API int aidax_pool_set_loading(aidax_pool* p, int32_t stream, int loading)
         p->loading[s] = loading ? 1 : 0;
         p->patch_model_fields(s);
     }
-    p->mark_dirty(lo, hi);
+    p->ctl_dirty.mark(lo, hi);
     return AIDAX_OK;
 }
 
@@ -1724,9 +1473,7 @@ AIDAX_API int aidax_pool_activate(aidax_pool* p, int32_t stream)
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
     if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
         return fail(AIDAX_ERR_ARG, "stream out of range");
-    return guarded([&]() -> int {
-        HIP_TRY(hipSetDevice(p->device));
-        p->enter_stream(p->q);
+    return p->on_own_stream([&]() -> int {
         // paramFirstRun is only re-armed when a model exists (rt-neural-generic.cpp:344-351)
         const uint32_t bits = PEND_ACTIVATE | (p->cur.has_model ? PEND_PARAM_FIRST : 0u);
         HIP_TRY(launch_set_pending(p->d_st, p->n_streams, stream, bits, p->q));
@@ -1749,19 +1496,8 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
         HIP_TRY(hipSetDevice(p->device));
         const size_t bytes = sizeof(float) * p->n_streams * static_cast<size_t>(n_frames);
         int rc;
-        if (!p->h_in) {                                     // blocks beyond the pinned staging: pageable copies
-            if (bytes) HIP_TRY(hipMemcpyAsync(p->d_in, in, bytes, hipMemcpyHostToDevice, p->q));
-            rc = aidax_pool_process_device(p, p->d_in, p->d_out, n_frames, p->q);
-            if (rc != AIDAX_OK) return rc;
-            if (bytes) HIP_TRY(hipMemcpyAsync(out, p->d_out, bytes, hipMemcpyDeviceToHost, p->q));
-            HIP_TRY(hipStreamSynchronize(p->q));
-            if (p->take_lp_fault()) {
-                if (bytes) std::memset(out, 0, bytes);
-                return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
-            }
-            return AIDAX_OK;
-        }
-        if (bytes) std::memcpy(p->h_in, in, bytes);
+        const bool staged = p->h_in != nullptr;             // (no pinned staging: pageable copies from and to the caller's buffers — and no zero_copy or spin_wait, which aidax_pool_create sets only behind h_in)
+        if (bytes && staged) std::memcpy(p->h_in, in, bytes);
         if (p->zero_copy) {
             // small blocks (the one-instance plugin): the pass reads its input straight from pinned host memory;
             // a one-launch pass also writes its output there, a multi-launch pass works in place on d_out
@@ -1773,10 +1509,10 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
             if (rc != AIDAX_OK) return rc;
             if (!direct && bytes) HIP_TRY(hipMemcpyAsync(p->h_out, p->d_out, bytes, hipMemcpyDeviceToHost, p->q));
         } else {
-            if (bytes) HIP_TRY(hipMemcpyAsync(p->d_in, p->h_in, bytes, hipMemcpyHostToDevice, p->q));
+            if (bytes) HIP_TRY(hipMemcpyAsync(p->d_in, staged ? p->h_in : in, bytes, hipMemcpyHostToDevice, p->q));
             rc = aidax_pool_process_device(p, p->d_in, p->d_out, n_frames, p->q);
             if (rc != AIDAX_OK) return rc;
-            if (bytes) HIP_TRY(hipMemcpyAsync(p->h_out, p->d_out, bytes, hipMemcpyDeviceToHost, p->q));
+            if (bytes) HIP_TRY(hipMemcpyAsync(staged ? p->h_out : out, p->d_out, bytes, hipMemcpyDeviceToHost, p->q));
         }
         uint32_t seq = 0;
         if (p->spin_wait && p->pass_word_taken) {
@@ -1811,7 +1547,7 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
             if (bytes) std::memset(out, 0, bytes);
             return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
         }
-        if (bytes) std::memcpy(out, p->h_out, bytes);
+        if (bytes && staged) std::memcpy(out, p->h_out, bytes);
         return AIDAX_OK;
     });
 }
@@ -2019,7 +1755,7 @@ AIDAX_API const char* aidax_pool_kernel_name(const aidax_pool* p)
     if (m.kind == ModelSlot::QUAD) return "k_chain+k_quad";
     if (m.kind == ModelSlot::CONV && m.conv_ms && m.conv_fused && m.cdesc.st_ok && p->max_frames >= 64) return "k_conv_st";      // (what a block of 64 / 128 / 256 frames runs; every other length: k_conv_ms)
     if (m.kind == ModelSlot::CONV) return m.conv_ms ? (m.conv_fused ? "k_conv_ms" : "k_chain+k_conv_ms") : m.conv_fused ? "k_conv_mfma" : m.conv_mfma ? "k_chain+k_conv_mfma" : "k_conv";
-    if (p->bank_in_force()) return m.kernel->name_pipe_bank;      // a stream plays a bank slot: every pass is the bank kernel's
+    if (p->bank.in_force()) return m.kernel->name_pipe_bank;      // a stream plays a bank slot: every pass is the bank kernel's
     const int form = p->chain_form(m);
     // (form 1: what a block of the pool's full length runs with the controls as they stand — k_*_pipe4 where it serves, k_*_pipe otherwise)
     if (form == 1 && p->pipe4_serves(m, p->max_frames, m.input_size)) return m.kernel->name_pipe4;

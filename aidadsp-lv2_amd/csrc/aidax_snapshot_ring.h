@@ -1,0 +1,68 @@
+// aidax_snapshot_ring.h — how host records reach the device: from a ring of pinned snapshots that nothing overwrites while an upload is
+// in flight, stream-ordered with the pass that follows (the pool's control records, the model bank's per-stream records, the IR plan).
+// It issues HIP calls and includes aidax_hip_host.h itself: include it where that header would go, last.
+#pragma once
+
+#include <algorithm>
+#include <cstring>
+
+#include "aidax_hip_host.h"
+
+namespace aidax {
+
+constexpr int kRing = 4;                                 // snapshots in flight
+
+struct DirtyRange {                                      // records [lo, hi] to upload; empty when lo > hi
+    uint32_t lo = 1, hi = 0;
+    bool empty() const { return lo > hi; }
+    void clear() { lo = 1; hi = 0; }
+    void mark(uint32_t l, uint32_t h) { const bool e = empty(); lo = e ? l : std::min(lo, l); hi = e ? h : std::max(hi, h); }
+};
+
+struct SnapshotRing {
+    uint8_t* snap[kRing] = {};
+    hipEvent_t ev[kRing] = {};
+    bool used[kRing] = {};
+    int next = 0;
+
+    void alloc(size_t bytes)                             // (set-up and worker side)
+    {
+        for (int k = 0; k < kRing; ++k) {
+            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&snap[k]), bytes, hipHostMallocDefault));
+            HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+        }
+    }
+    void release()
+    {
+        for (int k = 0; k < kRing; ++k) {
+            if (snap[k]) (void)hipHostFree(snap[k]);
+            if (ev[k]) (void)hipEventDestroy(ev[k]);
+            snap[k] = nullptr; ev[k] = nullptr;
+        }
+    }
+    // An upload is take(), fill what it returns, send(): the next snapshot (waited for only if its last upload, four back, is still in
+    // flight: not seen in practice), then its bytes [off, off + bytes) to the same offset of `d_dst` on `s`, asynchronously.
+    uint8_t* take()
+    {
+        if (used[next] && hipEventQuery(ev[next]) != hipSuccess) HIP_TRY(hipEventSynchronize(ev[next]));
+        return snap[next];
+    }
+    void send(void* d_dst, size_t off, size_t bytes, hipStream_t s)
+    {
+        HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(d_dst) + off, snap[next] + off, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[next], s));
+        used[next] = true;
+        next = (next + 1) % kRing;
+    }
+    template <class Rec>
+    void upload_dirty(Rec* d, const Rec* h, DirtyRange& dirty, hipStream_t s)      // records [lo, hi] of h to the same records of d
+    {
+        if (dirty.empty()) return;
+        const size_t off = sizeof(Rec) * dirty.lo, bytes = sizeof(Rec) * (static_cast<size_t>(dirty.hi - dirty.lo) + 1);
+        std::memcpy(take() + off, h + dirty.lo, bytes);
+        send(d, off, bytes, s);
+        dirty.clear();
+    }
+};
+
+}  // namespace aidax

@@ -16,6 +16,7 @@ import pytest
 
 from oracle import oracle as O
 from tests import errlog, modelgen
+from tests.test_gpu_ir_bank_rt import _Device, _quiet, calls        # noqa: F401  (the call-table fixture: it skips on the ship leg)
 
 pytestmark = pytest.mark.gpu
 ax = importlib.import_module("aidadsp-lv2_amd")
@@ -486,3 +487,52 @@ def test_a_one_stream_pool_on_a_slot_through_the_blocking_path(tmp_path):
     assert np.abs(a).max() > 1e-4
     pool.close()
     twin.close()
+
+
+# ---------------------------------------------------------------- 8: the audio-side calls in real time
+
+
+def test_assignments_and_slot_commits_allocate_free_and_wait_for_nothing(tmp_path, calls):
+    """aidax_pool_assign_model and the commit of a prepared slot on the audio thread, and the two passes behind each: nothing that
+    allocates, frees or waits among the pool's HIP calls (tests/test_gpu_ir_bank_rt.py's sets). The first pass behind an assignment
+    uploads the changed records — one hipMemcpyAsync more than a pass with nothing to upload — and the second one nothing."""
+    files = _files(tmp_path, "lstm", 16, 1)
+    pool = ax.Pool(6, 64)
+    pool.set_model(ax.Model(files[0][0]))
+    for k in range(2):
+        pool.set_model_slot(k, ax.Model(files[k + 1][0]))
+    dev = _Device(6, 64, seed=21)
+    dev.pass_(pool)
+    dev.wait()
+    calls()
+    dev.pass_(pool)
+    idle = calls()
+    _quiet(idle, "pass with nothing dirty")
+    dev.wait()
+
+    def two_passes(what, uploads):
+        for k in range(2):
+            dev.pass_(pool)
+            c = calls()
+            _quiet(c, f"pass {k} after {what}")
+            assert c.get("hipMemcpyAsync", 0) == idle.get("hipMemcpyAsync", 0) + (uploads if k == 0 else 0), (what, k, c, idle)
+        dev.wait()
+        calls()
+    # (stream 4 stays on its slot, so the bank is in force behind every assignment; the last one moves stream 1 back with a warm-up)
+    for stream, slot, mode in ((1, 0, ax.START_RESET), (4, 1, ax.START_RESET), (1, ax.MODEL_POOL, ax.START_WARMUP)):
+        pool.assign_model(stream, slot, mode)
+        _quiet(calls(), f"assign_model({stream}, {slot})")
+        assert pool.kernel_name == "k_lstm_pipe_bank<16>"
+        two_passes(f"assign_model({stream}, {slot})", 1)
+    assert [pool.stream_model(s) for s in range(6)] == [-1, -1, -1, -1, 1, -1]
+    for slot, m in ((0, ax.Model(files[3][0])), (2, ax.Model(files[3][0])), (0, None)):      # replace a loaded slot, load an empty one, empty one
+        sg = pool.prepare_model_slot(slot, m)               # (worker side)
+        calls()
+        pool.commit_model(sg)                               # audio side
+        c = calls()
+        _quiet(c, "commit_model of a slot")
+        assert c.get("hipEventRecord", 0) >= 1, c           # the fence the retired weights wait for
+        two_passes("commit_model of a slot", 0)
+        pool.staged_free(sg)                                # (worker side)
+        calls()
+    pool.close()
