@@ -209,6 +209,35 @@ __device__ __forceinline__ float lin_next(float& mem, float target, float step)
     return mem;
 }
 
+// ------------------------------------------------------------ a transparent EQ
+// A biquad stage that computes NOTHING: a 0 dB shelf or peak comes out of Biquad::calcBiquad (common/Biquad.cpp:108-161) with
+// a0 == 1, a1 == b1 and a2 == b2 exactly (V = 1: numerator and denominator are the same expression; one flat design in eight
+// has a0 an ulp off 1 and is not meant), and from z1 = z2 = 0 the step of Biquad.h:53-58 then gives, every line one IEEE operation,
+//   y = x * 1 + 0 = x        z1' = x a1 + 0 - b1 x = 0        z2' = x a2 - b2 x = 0
+// for every finite x: the output is the input to the bit (but -0.0 leaves as +0.0) and the state stays exactly zero. The values
+// are the ones a cascade lane has just loaded; plain compares, so a NaN anywhere says no.
+__device__ __forceinline__ bool eq_stage_transparent(double a0, double a1, double a2, double b1, double b2, double z1, double z2)
+{
+    return a0 == 1.0 && a1 == b1 && a2 == b2 && z1 == 0.0 && z2 == 0.0;
+}
+// A stream's post EQ is transparent for a launch when it is in circuit behind the model (CTL_EQ_POST), not in bandpass mode (there
+// four of its stages are bypassed and keep their state, whatever it is) and all five stages are transparent: the launch then runs
+// the post cascade with ONE stage (K = 1, as without CTL_EQ_POST), writes nothing back for the five, and stands in for them with
+// eq_skip_sample at the point where the EQ's output would have been. Decided at the head of every launch from what it has loaded:
+// a stream whose EQ was boosted and then flattened runs all six stages until its state has decayed to exactly zero.
+//
+// What the five identity stages do to a sample besides passing it on: -0.0 becomes +0.0 (x + 0), and a sample that is not finite
+// poisons the first stage's state (a1 Inf - b1 Inf = NaN) — that sample still leaves unchanged, every later one is NaN, in this launch
+// and in the ones after it. `p` (+0.0 at the head of a launch) carries both: + 0.0 while all is finite, NaN from the first bad sample
+// on; a launch that ends with p = NaN stores NaN into the five stages' state, and the next one sees state that is not zero and runs
+// the full cascade.
+__device__ __forceinline__ float eq_skip_sample(float y, float& p)
+{
+    const float o = y + p;
+    p = p + (y - y);
+    return o;
+}
+
 // ------------------------------------------------------------ systolic chain
 // One pass of up to 6 cascaded stages over buf[0..n) in LDS, in place.
 // Lane k < K owns stage k: an optional biquad (slot[k], enabled by act[k]) and,
@@ -218,6 +247,8 @@ struct ChainPass {
     bool active;          // this lane's biquad is in circuit
     double a0, a1, a2, b1, b2, z1, z2;
     ExpRamp g;
+    bool eq_skip;         // this lane's stage stands in for five transparent EQ stages behind it (eq_skip_sample; the forms that take the skip)
+    float eq_p;           // ... and their poison word
 };
 
 // One systolic step of one lane. CHECK = false is the steady state (every stage of the cascade has a
@@ -295,7 +326,9 @@ constexpr int kChainBlock = AIDAX_CHAIN_BLOCK;
 // and the two ramp instructions drop out — 12 instructions per sample and stage instead of 15, same values.
 // B frames per hand-over (kChainBlock, or more where the hand-over dominates: the fused conv kernel's lone chain wave), HL the
 // number of lanes that have a slot in `hand` ([2][HL][B] floats).
-template <bool PLAIN, int B = kChainBlock, int HL = kWave>
+// EQSKIP: lanes with c.eq_skip put every output through eq_skip_sample in front of the gain (a stream whose post EQ is transparent:
+// see eq_stage_transparent) — a branch per macro-step that no lane takes where no stream skips.
+template <bool PLAIN, int B = kChainBlock, int HL = kWave, bool EQSKIP = false>
 __device__ __forceinline__ void chain_macro_step(ChainPass& c, ExpRamp& g, int stage, bool run, bool last,
                                                  float* row, float* hand, int M, int m, int lane)
 {
@@ -317,12 +350,22 @@ __device__ __forceinline__ void chain_macro_step(ChainPass& c, ExpRamp& g, int s
             const double yd = xd * c.a0 + c.z1;
             c.z1 = xd * c.a1 + c.z2 - c.b1 * yd;
             c.z2 = xd * c.a2 - c.b2 * yd;
-            if constexpr (PLAIN) {
+            if constexpr (EQSKIP) {
+                v[i] = PLAIN || c.active ? (float)yd : x;       // (the gain follows below)
+            } else if constexpr (PLAIN) {
                 v[i] = (float)yd * g_fixed;
             } else {
                 const float y = c.active ? (float)yd : x;
                 v[i] = y * g.next();
             }
+        }
+        if constexpr (EQSKIP) {
+            if (c.eq_skip) {
+#pragma unroll
+                for (int i = 0; i < B; ++i) v[i] = eq_skip_sample(v[i], c.eq_p);
+            }
+#pragma unroll
+            for (int i = 0; i < B; ++i) v[i] = v[i] * (PLAIN ? g_fixed : g.next());
         }
 #pragma unroll
         for (int q = 0; q < B / 4; ++q)

@@ -1005,6 +1005,9 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
     } else {
         if (lane >= cp.K || !cp.active) { cp.z1 = q_z1o; cp.z2 = q_z2o; }      // a bypassed biquad keeps its state (:646)
         if (lane < cp.K) { st.z[slot][0] = cp.z1; st.z[slot][1] = cp.z2; }
+#ifdef AIDAX_TEST_HOOKS
+        if (lane == 0) st.pad = (uint32_t)cp.K;             // (test build: the post cascade's length this launch ran, for the tests of the skip)
+#endif
         if (lane == cp.K - 1) { st.master_mem = cp.g.mem; st.master_tgt = master_tgt; }
         post_done_word(a, lane);                            // (this wave has stored the block)
 #ifdef AIDAX_PIPE_TRACE
@@ -1136,7 +1139,12 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     const int I = kCond ? (int)a.input_size : 1;
 
     // every wave derives the launch's timing from the four control words (wave-uniform): the longest cascades set it
-    int Kp = 1, Kq = 1;
+    // (the post side's length is the helper's alone in the free-running form — it knows only behind its loads whether a stream's post EQ is
+    // transparent, see there; the barrier form, where every wave counts the ticks, keeps the control words' answer and never skips)
+    int Kp = 1;
+#ifdef AIDAX_P4_BARRIER
+    int Kq = 1;
+#endif
     uint32_t fw[kP4Streams];                              // the four control words' flags (scalar loads: registers of the scalar file)
 #pragma unroll
     for (int j = 0; j < kP4Streams; ++j) {
@@ -1147,10 +1155,14 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         const uint32_t f = a.ctl[jc].flags;
         fw[j] = s0 + j < (int)a.n_streams ? f : 0u;
         if ((f & CTL_EQ_PRE) && s0 + j < (int)a.n_streams) Kp = 6;
+#ifdef AIDAX_P4_BARRIER
         if ((f & CTL_EQ_POST) && s0 + j < (int)a.n_streams) Kq = 6;
+#endif
     }
     const int d1 = Kp / 2 + 1;                            // ticks between a tile entering the pre pass and the cell reading it
+#ifdef AIDAX_P4_BARRIER
     const int T = (n / B - 1 + (Kq - 1) + 2 * (d1 + 1)) / 2 + 1;
+#endif
 
     if (wave < kP4Streams) {
         // ---------------------------------------------------------------- a recurrent wave
@@ -1371,9 +1383,28 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     if (pending & PEND_ACTIVATE) { pre_mem = pre_tgt; master_mem = master_tgt; pending &= ~PEND_ACTIVATE; }     // activate(): :341-342
     pre_tgt = ctl_pre_target;
     if (live) master_tgt = ctl_master_target;
-    const int Kpj = (flags & CTL_EQ_PRE) ? 6 : 1, Kqj = (flags & CTL_EQ_POST) ? 6 : 1;
+    // A post EQ that is transparent for this launch (eq_stage_transparent, aidax_device.h: the flat default EQ once its state is zero) is
+    // not run: lanes 12 j + 7 .. 12 j + 11 hold stream j's five EQ stages as chain_load has just brought them, one ballot says whether all
+    // five compute nothing, and the stream's post cascade is then its first stage alone — K = 1, the gain on it, as without CTL_EQ_POST —
+    // with eq_skip_sample where the EQ's output would have been. Five macro-steps of drain behind the last tile go with it when none of the
+    // workgroup's streams runs an EQ (the longest cascade sets the launch's ticks; every stream runs its own K).
+    bool skipj = false;
+#ifndef AIDAX_P4_BARRIER
+    {
+        const unsigned long long flat = __builtin_amdgcn_ballot_w64(eq_stage_transparent(c.a0, c.a1, c.a2, c.b1, c.b2, c.z1, c.z2));
+        skipj = ((flat >> (12 * j + 7)) & 31u) == 31u && (flags & (CTL_EQ_POST | CTL_EQ_BANDPASS)) == CTL_EQ_POST
+             && !(AIDAX_TUNE(a) & kTuneEqFull);              // (test build: the full cascade, to compare the skip with)
+    }
+#endif
+    const int Kpj = (flags & CTL_EQ_PRE) ? 6 : 1, Kqj = (flags & CTL_EQ_POST) && !skipj ? 6 : 1;
+#ifndef AIDAX_P4_BARRIER
+    const int Kq = __builtin_amdgcn_ballot_w64(there && lane < kP4ChainLanes && Kqj == 6) != 0 ? 6 : 1;
+    const int T = (n / B - 1 + (Kq - 1) + 2 * (d1 + 1)) / 2 + 1;
+#endif
     c.K = isQ ? Kqj : Kpj;
     c.gain_lane = isQ ? Kqj - 1 : 0;
+    c.eq_skip = skipj && isQ && stage == 0;
+    c.eq_p = 0.f;
     c.active = stage == 0 ? (flags & (isQ ? CTL_DC_ON : CTL_LPF_ON)) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
     c.g.arm(isQ ? master_mem : pre_mem, isQ ? master_tgt : pre_tgt, isQ ? ctl_master_coef : ctl_pre_coef);
     const bool run = lane < kP4ChainLanes && stage < c.K && live;
@@ -1450,8 +1481,8 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         if (!(AIDAX_TUNE(a) & 262144))                          // (bit 262144, test build: no chain passes; wrong output)
 #pragma unroll
         for (int hs = 0; hs < 2; ++hs) {
-            if (plain) chain_macro_step<true, B, kP4ChainLanes>(c, g, stage, run, last, myrow, hand, n / B, 2 * tick + hs - m0, lane);
-            else chain_macro_step<false, B, kP4ChainLanes>(c, g, stage, run, last, myrow, hand, n / B, 2 * tick + hs - m0, lane);
+            if (plain) chain_macro_step<true, B, kP4ChainLanes, true>(c, g, stage, run, last, myrow, hand, n / B, 2 * tick + hs - m0, lane);
+            else chain_macro_step<false, B, kP4ChainLanes, true>(c, g, stage, run, last, myrow, hand, n / B, 2 * tick + hs - m0, lane);
         }
         // the tile the cells read next tick: times in_gain, in place (out[i] *= input_gain, :170; every stream's pre pass has finished it)
         const int ts = tick - d1 + 1;
@@ -1485,6 +1516,18 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     if (is_gain) c.g = g;
     if (!run || !c.active) { c.z1 = z1o; c.z2 = z2o; }                      // a bypassed biquad keeps its state (:622, :646)
     if (run) { st.z[slot][0] = c.z1; st.z[slot][1] = c.z2; }
+    {
+        // (a skipped EQ writes nothing back — its state stays the zero it was — unless it met a sample that was not finite: the five stages' state
+        // is NaN then, as the stages themselves would have left it, and the next launch runs them)
+        const float pj = __builtin_bit_cast(float, __builtin_amdgcn_ds_bpermute(4 * (lane - stage), __builtin_bit_cast(int, c.eq_p)));
+        if (skipj && live && lane < kP4ChainLanes && isQ && stage >= 1 && pj != pj) {
+            st.z[slot][0] = __builtin_nan("");
+            st.z[slot][1] = __builtin_nan("");
+        }
+    }
+#ifdef AIDAX_TEST_HOOKS
+    if (there && lane < kP4ChainLanes && r == 6) st.pad = (uint32_t)Kqj;      // (test build: the post cascade's length this launch ran, for the tests of the skip)
+#endif
     // (a disabled stream: the gain memories as activate() left them, the pre-gain target latched, nothing else — :612-619 and k_*_pipe's early-out)
     if (there && lane < kP4ChainLanes && !isQ && stage == 0) { st.pre_mem = c.g.mem; st.pre_tgt = pre_tgt; }
     if (there && lane < kP4ChainLanes && isQ && stage == c.K - 1) { st.master_mem = c.g.mem; st.master_tgt = master_tgt; }

@@ -310,6 +310,8 @@ struct alignas(16) ModelRec {
 };
 static_assert(sizeof(ModelRec) == 32, "ModelRec layout");
 
+constexpr int kTuneEqFull = 4;    // LaunchArgs::tune: the full post cascade where the EQ is transparent (eq_stage_transparent, aidax_device.h)
+
 struct LaunchArgs {
     const StreamCtl* ctl;
     StreamState*     st;
@@ -326,6 +328,7 @@ struct LaunchArgs {
     float            in_gain, out_gain;
     int32_t          tune;        // AIDAX_TUNE bit mask, measurement / test switches of the kernels (0 in production):
                                   // 1 = no issue priority for the recurrent wave of k_*_pipe, 2 = k_mfma_lp with a group's layers on adjacent workgroup ids,
+                                  // 4 (kTuneEqFull) = a transparent post EQ is run all the same (k_*_pipe4: the tests compare the skip with it),
                                   // 16 = k_mfma_lp reports a hand-over give-up that did not happen (tests of the fault path),
                                   // 32768 / 65536 = k_conv_st without its history stores / with every far tap reading one resident tile (scratch/r06_cfg4_ablate.sh),
                                   // 8192 = the last layer's workgroup of k_mfma_lp's one-launch form starts 100 us late (tests: nothing may lean on the layers' workgroups starting together)

@@ -1325,6 +1325,17 @@ AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_
 
 #ifdef AIDAX_TEST_HOOKS
 AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap) { return read_hip_calls(buf, cap); }      // (test build only, not in include/aidax.h)
+// (test build only: one stream's whole record as the kernels left it — `pending`, and in `pad` the length of the post cascade that the last
+// k_*_pipe4 launch ran for the stream, 1 where it skipped a transparent EQ: tests/test_gpu_eq_transparent.py)
+AIDAX_API int aidax_test_stream_state(aidax_pool* p, uint32_t stream, void* out, uint32_t cap)
+{
+    if (!out || cap < sizeof(StreamState)) return fail(AIDAX_ERR_ARG, "buffer too small for a stream's record");
+    StreamState st{};
+    const int rc = aidax::pool_read_stream_state(p, stream, &st);
+    if (rc != AIDAX_OK) return rc;
+    std::memcpy(out, &st, sizeof(StreamState));
+    return (int)sizeof(StreamState);
+}
 #endif
 
 }  // extern "C"
