@@ -67,6 +67,47 @@ __device__ __forceinline__ void fmac_row_ror_1_15(float& a0, float h, const floa
 }
 #undef AIDAX_ROR1
 
+// The LDS half of LstmCell<32>'s recurrent product in ONE asm statement: sixteen v_pk_fma_f32 — {a0, a1} += {w0[k], w1[k]} * {h[k], h[k]},
+// both gate rows per instruction, h[k] one half of a pair read from LDS — on four accumulator pairs A, B, C, D in turn, then A + B and
+// C + D; the caller adds the two sums. Unit k goes to chain k & 3 and reads half k & 1 of hq[k >> 1]: the operations, operands and order
+// of sixteen statements of one instruction each, which is how this was written before, with two differences in what is ISSUED:
+//   * the first links of B, C and D take the inline constant 0 as their addend (fma(w, h, +0), as with a zeroed register): no accumulator
+//     pair has to be zeroed — three v_mov_b64 per frame, which the compiler re-materialised in every frame of the unrolled stage;
+//   * the compiler assumes that ANY asm statement forwards its result like an instruction that writes half a register and wants one wait
+//     state between a statement that defines a register and the next reader of it, asm statements themselves counting as none: with
+//     sixteen statements every link of a chain needed an ordinary instruction somewhere behind the link before it, and where the
+//     scheduler had none to spare it put an s_nop 0 — in front of the D links, each the first statement to close such a gap, two or
+//     three per frame. v_pk_fma_f32 writes whole registers; a chain's links are three instructions apart here anyway.
+// Inside a statement nothing is padded. The one pair in here that the compiler pads in its own output — a packed instruction whose first
+// source reads both halves, its result read by the NEXT instruction — does not occur: A + B reads B two instructions after its last link
+// (C's and D's between), C + D reads D with A + B in between. The last add, (A + B) + (C + D), reads C + D at once and is left to the
+// compiler with its wait states (it is also what tells the compiler that the sum is no signalling NaN: on an asm statement's output the
+// clamp of tanh_rat costs a v_max_f32 more). B, C and D are written before the last input is read: early-clobber outputs.
+typedef float aidax_f32x2 __attribute__((ext_vector_type(2)));
+#define AIDAX_PKA(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", %" #ACC " op_sel_hi:[1,0,1]\n\t"
+#define AIDAX_PKB(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", %" #ACC " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
+#define AIDAX_PKA0(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", 0 op_sel_hi:[1,0,0]\n\t"
+#define AIDAX_PKB0(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", 0 op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"
+__device__ __forceinline__ aidax_f32x2 pk_fma_lds16(aidax_f32x2 pA, const aidax_f32x2* w, const aidax_f32x2* hq)
+{
+    aidax_f32x2 pB, pC, pD;
+    asm volatile(AIDAX_PKA(0, 4, 20) AIDAX_PKB0(1, 5, 20) AIDAX_PKA0(2, 6, 21) AIDAX_PKB0(3, 7, 21)
+                 AIDAX_PKA(0, 8, 22) AIDAX_PKB(1, 9, 22) AIDAX_PKA(2, 10, 23) AIDAX_PKB(3, 11, 23)
+                 AIDAX_PKA(0, 12, 24) AIDAX_PKB(1, 13, 24) AIDAX_PKA(2, 14, 25) AIDAX_PKB(3, 15, 25)
+                 AIDAX_PKA(0, 16, 26) AIDAX_PKB(1, 17, 26) AIDAX_PKA(2, 18, 27) AIDAX_PKB(3, 19, 27)
+                 "v_pk_add_f32 %0, %0, %1\n\t"
+                 "v_pk_add_f32 %2, %2, %3"
+                 : "+v"(pA), "=&v"(pB), "=&v"(pC), "=&v"(pD)
+                 : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]),
+                   "v"(w[11]), "v"(w[12]), "v"(w[13]), "v"(w[14]), "v"(w[15]),
+                   "v"(hq[0]), "v"(hq[1]), "v"(hq[2]), "v"(hq[3]), "v"(hq[4]), "v"(hq[5]), "v"(hq[6]), "v"(hq[7]));
+    return pA + pC;
+}
+#undef AIDAX_PKA
+#undef AIDAX_PKB
+#undef AIDAX_PKA0
+#undef AIDAX_PKB0
+
 // Cross-lane shares on the permlane swap network. (The swapped pair is copied to
 // scalars before the float bit_cast: __builtin_bit_cast applied directly to an
 // ext-vector element reads element 0 on ROCm 7.2's clang.)
@@ -137,6 +178,13 @@ constexpr float kTanhQ[4] = { 1.0f, 0.46417337453820245f, 0.02449517952619233f, 
 // forget gate "at 1" of an LSTM-12 let c decay, 1.8e-4 after 80 frames at |c| ~ 40 (tests/test_gpu_activations.py, clamp family).
 constexpr float kTanhClamp = 0x1.f9b3c2p+2f;      // 7.90159655
 __device__ __forceinline__ float tanh_rat_clamp(float v) { return __builtin_fminf(__builtin_fmaxf(v, -kTanhClamp), kTanhClamp); }     // (v_max + v_med3; a bare v_med3 lets a NaN through and is no faster)
+// kUFirst (LstmCell<32>'s frame only, where a no-op is an issue slot of the lone recurrent wave): the packed Horner steps written
+// {u, u} * {p, q} + c instead of {p, q} * {u, u} + c — the same products, so the same bits. The compiler puts a wait state behind a packed
+// instruction whose FIRST source reads both halves (op_sel_hi[0] = 1) when the next instruction reads its result, and none behind the
+// broadcast {u, u} in that place (op_sel_hi:[0,1,1]: how the first step has always come out, its {p, q} being a constant). This holds as
+// long as the compiler keeps the operand order it is given — it does not canonicalise the two factors of an fma today; the per-frame tally
+// in profiles/lstm32_frame_slots.txt is what shows it if that changes. Every other caller keeps the form, and so the schedule, it had.
+template <bool kUFirst = false>
 __device__ __forceinline__ float tanh_rat(float v)
 {
     const float x = tanh_rat_clamp(v);
@@ -147,10 +195,11 @@ __device__ __forceinline__ float tanh_rat(float v)
     // (profiles/r05_lone_wave_issue.txt), and the recurrent wave's frame is its instruction count (profiles/r05_cfg2_frame_trace.txt): two rationals per frame.
     typedef float f32x2_t __attribute__((ext_vector_type(2)));
     const f32x2_t uu = { u, u };
+    auto step = [&](f32x2_t pq, f32x2_t c) { return kUFirst ? __builtin_elementwise_fma(uu, pq, c) : __builtin_elementwise_fma(pq, uu, c); };
     f32x2_t pq = { kTanhP[6], kTanhQ[3] };
-    pq = __builtin_elementwise_fma(pq, uu, f32x2_t{ kTanhP[5], kTanhQ[2] });
-    pq = __builtin_elementwise_fma(pq, uu, f32x2_t{ kTanhP[4], kTanhQ[1] });
-    pq = __builtin_elementwise_fma(pq, uu, f32x2_t{ kTanhP[3], kTanhQ[0] });
+    pq = step(pq, f32x2_t{ kTanhP[5], kTanhQ[2] });
+    pq = step(pq, f32x2_t{ kTanhP[4], kTanhQ[1] });
+    pq = step(pq, f32x2_t{ kTanhP[3], kTanhQ[0] });
     float pp = pq.x;
     pp = __builtin_fmaf(pp, u, kTanhP[2]);
     pp = __builtin_fmaf(pp, u, kTanhP[1]);

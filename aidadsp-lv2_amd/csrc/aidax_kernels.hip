@@ -206,17 +206,11 @@ struct LstmCell {
             // one half of the h pair selected for both results — on FOUR accumulator pairs in turn: a lone wave issues a packed FMA in the interval
             // of a plain one, but a DEPENDENT instruction only ~8.7 cycles after the one it waits for, an independent one after ~5.8
             // (scratch/ub/upk.hip). One pair chain of sixteen: 67.3 us (slower than the 32 plain FMAs on two chains, 66.2); four chains of four: 64.25.
-            f32x2 pA = { a0, a1 }, pB = { 0.f, 0.f }, pC = { 0.f, 0.f }, pD = { 0.f, 0.f };
+            // (the sixteen links and the three adds are ONE asm statement, pk_fma_lds16 in aidax_device.h: as sixteen statements they drew
+            // three v_mov_b64 and three s_nop 0 per frame from the compiler — eight issue slots of this wave; profiles/lstm32_frame_slots.txt)
             const f32x2 hq[8] = { f32x2{ q0.x, q0.y }, f32x2{ q0.z, q0.w }, f32x2{ q1.x, q1.y }, f32x2{ q1.z, q1.w },
                                   f32x2{ q2.x, q2.y }, f32x2{ q2.z, q2.w }, f32x2{ q3.x, q3.y }, f32x2{ q3.z, q3.w } };
-#pragma unroll
-            for (int k2 = 0; k2 < 8; k2 += 2) {
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(pA) : "v"(wl2[2 * k2]), "v"(hq[k2]));
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(pB) : "v"(wl2[2 * k2 + 1]), "v"(hq[k2]));
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel_hi:[1,0,1]" : "+v"(pC) : "v"(wl2[2 * k2 + 2]), "v"(hq[k2 + 1]));
-                asm volatile("v_pk_fma_f32 %0, %1, %2, %0 op_sel:[0,1,0] op_sel_hi:[1,1,1]" : "+v"(pD) : "v"(wl2[2 * k2 + 3]), "v"(hq[k2 + 1]));
-            }
-            const f32x2 a01 = (pA + pB) + (pC + pD);
+            const f32x2 a01 = pk_fma_lds16(f32x2{ a0, a1 }, wl2, hq);
             acc[0][0] = a01.x; acc[0][1] = a01.y;
             PT_STAMP(2);                                    // products done
         } else {
@@ -245,11 +239,11 @@ struct LstmCell {
 #pragma unroll
             for (int e = 0; e < GPL; ++e) {
                 if constexpr (S == 1) {                     // gate = e, known at compile time
-                    act[e] = e == 2 ? tanh_rat(acc[m][e]) : sigmoid_pre(acc[m][e]);
+                    act[e] = e == 2 ? tanh_rat<ROT>(acc[m][e]) : sigmoid_pre(acc[m][e]);
                 } else if (S == 2 && e == 0) {              // (i | f): sigmoid in both halves
                     act[e] = sigmoid_pre(acc[m][e]);
                 } else {
-                    act[e] = __builtin_fmaf(tanh_rat(acc[m][e]), aka[e], akb[e]);
+                    act[e] = __builtin_fmaf(tanh_rat<ROT>(acc[m][e]), aka[e], akb[e]);
                 }
             }
             PT_STAMP(3);                                    // gate activations issued
@@ -275,7 +269,7 @@ struct LstmCell {
 #ifdef AIDAX_TANHC_EXP
             const float hn = go * tanh_exp(cn);             // experiment: the exp form for tanh(c) only (scratch/ab_tanhc.sh)
 #else
-            const float hn = go * tanh_rat(cn);
+            const float hn = go * tanh_rat<ROT>(cn);
 #endif
             if constexpr (ROT) h[m] = share_halves(hn).hi;  // the (f, o) half's h into both halves: the rotations read it
             else h[m] = hn;

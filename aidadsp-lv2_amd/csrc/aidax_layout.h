@@ -74,6 +74,9 @@ struct alignas(16) StreamState {
     uint32_t pad;
 };
 static_assert(sizeof(StreamState) == 160, "StreamState layout");
+// (tests read the record through aidax_test_stream_state by these offsets: tests/test_gpu_eq_transparent.py, tests/test_gpu_lstm32_frame.py)
+static_assert(offsetof(StreamState, pre_mem) == 112 && offsetof(StreamState, p_mem) == 128 && offsetof(StreamState, p_step) == 136 &&
+              offsetof(StreamState, p_tgt) == 144 && offsetof(StreamState, pending) == 152 && offsetof(StreamState, pad) == 156, "StreamState layout");
 
 // ---------------------------------------------------------------- lane mapping
 // One wavefront (64 lanes) per stream. A recurrent layer with G gates and H
