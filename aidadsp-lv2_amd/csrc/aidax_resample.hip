@@ -13,10 +13,13 @@
 // One summation order per output sample, whatever the tile, the block boundary or the cut of the input into calls: four fp32
 // accumulators, tap ii of the row (ii = i + H, ascending) into accumulator ii mod 4 by FMA, then (acc0 + acc1) + (acc2 + acc3). Whether a
 // frame comes from LDS, the ring or the new block does not touch its bits. Equal rates are a bit copy (x[q], no arithmetic).
-// A ratio whose window would not fit kRsWindow floats (far outside the audio rates: M / L beyond about 15) reads its frames in place
-// instead of staging them: the same sums in the same order.
+// A ratio whose window would not fit kRsWindow floats reads its frames in place instead of staging them: the same sums in the same
+// order. The window is ceil(255 M / L) + 2 ceil(32 M / L) + 1 floats, about 319 M / L: the in-place form starts at M / L of about 12.84
+// (77 -> 6 fills the 4096 floats exactly and is still staged, 90 -> 7 is the first pair in place; of the audio pairs only those at
+// 16 : 1 and beyond, such as 192000 -> 8000). AIDAX_RS_STAGED=0 (test build) forces the in-place form at any ratio.
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 #include "aidax_kernels.h"
 
 namespace aidax {
@@ -85,7 +88,9 @@ hipError_t launch_resample(const ResampleArgs& a, hipStream_t q)
     if (a.n_in == 0 && a.n_out == 0) return hipSuccess;
     const uint32_t tiles = a.n_out ? (a.n_out + kRsTile - 1u) / kRsTile : 1u;
     const dim3 grid(tiles, a.n_streams);
-    if (resample_window(a.L, a.M, a.H) <= kRsWindow) k_resample<true><<<grid, kRsThreads, 0, q>>>(a);
+    // (read on every call: tests switch forms within one process)
+    const bool in_place = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_RS_STAGED"); return e && e[0] == '0'; }();
+    if (!in_place && resample_window(a.L, a.M, a.H) <= kRsWindow) k_resample<true><<<grid, kRsThreads, 0, q>>>(a);
     else k_resample<false><<<grid, kRsThreads, 0, q>>>(a);
     return hipGetLastError();
 }

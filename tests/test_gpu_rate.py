@@ -15,6 +15,7 @@ import numpy as np
 import pytest
 
 from tests import errlog, modelgen, rateref as rr
+from tests.ratehelp import adapter_and_its_parts, feed as _feed, noise as _noise, pool as _pool, stage as _stage
 
 pytestmark = pytest.mark.gpu
 ax = importlib.import_module("aidadsp-lv2_amd")
@@ -23,34 +24,6 @@ RAGGED = (1, 7, 64, 255, 256, 17)                                          # 600
 N_IN = sum(RAGGED)
 # (rate_in, rate_out, d_in, d_out): the five ratios, with and without delays on either side
 STAGES = ((44100, 48000, 32, 0), (48000, 44100, 0, 34), (96000, 48000, 64, 0), (48000, 96000, 0, 0), (192000, 44100, 5, 3))
-
-
-def _noise(S, n, seed):
-    return np.random.default_rng(seed).uniform(-1.0, 1.0, (S, n)).astype(np.float32)
-
-
-def _feed(rs, x, cuts, reset=None):
-    """x through the resampler in calls of `cuts` frames, every ready output taken after each call; reset = (stream, frames received
-    when it happens). Calls alternate between append-then-ask (two launches, the first without outputs) and one call for both."""
-    got, at = [], 0
-    for k, n in enumerate(cuts):
-        if reset is not None and at == reset[1]:
-            rs.reset_stream(reset[0])
-        blk = np.ascontiguousarray(x[:, at:at + n])
-        at += n
-        if k % 2 == 0:
-            got.append(rs.process(blk))
-        else:
-            ready = rr.ready(at, *rs.spec) - sum(g.shape[1] for g in got)
-            got.append(rs.process(blk, ready))
-        assert rs.ready == 0
-    return np.concatenate(got, axis=1)
-
-
-def _stage(S, ri, ro, d_in, d_out, max_in):
-    rs = ax.Resampler(S, float(ri), float(ro), d_in, d_out, max_in)
-    rs.spec = (ri, ro, d_in, d_out)
-    return rs
 
 
 @pytest.mark.parametrize("ri,ro,d_in,d_out", STAGES)
@@ -146,15 +119,6 @@ def model(tmp_path_factory):
     return ax.Model(p)
 
 
-def _pool(model, S, max_frames, controls, ir=None):
-    p = ax.Pool(S, max_frames, 48000.0)
-    p.set_model(model)
-    p.set_controls(controls)
-    if ir is not None:
-        p.set_ir(ir)
-    return p
-
-
 @pytest.mark.parametrize("host", [44100, 96000])
 def test_the_adapter_around_a_transparent_pool(model, host):
     S, pool_rate = 3, 48000
@@ -192,38 +156,8 @@ HOST_BLOCKS = (64, 1, 0, 255, 17, 256, 0, 7, 128)
 
 
 def _adapter_and_its_parts(model, ir):
-    """(adapter's output, hand composition's output, the adapter's pool and adapter, the twin pool): LSTM-16 with the EQ and the gains
-    on, 5 streams at 44.1 kHz around pools at 48 kHz, ragged host blocks with n = 1 and n = 0, everything on one torch stream"""
-    import torch
-    S, host, pool_rate = 5, 44100, 48000
-    ctl = ax.default_controls(eq_bypass=0.0, bass_boost_db=4.0, mid_boost_db=-3.0, treble_boost_db=2.5, pregain_db=3.0, master_db=-2.0)
-    p1, p2 = _pool(model, S, 288, ctl, ir), _pool(model, S, 288, ctl, ir)
-    ad = ax.RateAdapter(p1, float(host), 256)
-    H_A, d_B = rr.delays(host, pool_rate)
-    A = ax.Resampler(S, float(host), float(pool_rate), H_A, 0, 256)
-    B = ax.Resampler(S, float(pool_rate), float(host), 0, d_B, 288)
-    x = modelgen.signal(S, sum(HOST_BLOCKS), seed=77)
-    s = torch.cuda.Stream()
-    got, want, at = [], [], 0
-    with torch.cuda.stream(s):
-        for n, m in zip(HOST_BLOCKS, rr.pool_frames(HOST_BLOCKS, host, pool_rate)):
-            d_x = torch.from_numpy(np.ascontiguousarray(x[:, at:at + n])).cuda()
-            at += n
-            y1, y2 = torch.empty((S, n), dtype=torch.float32, device="cuda"), torch.empty((S, n), dtype=torch.float32, device="cuda")
-            ya, yb = torch.empty((S, m), dtype=torch.float32, device="cuda"), torch.empty((S, m), dtype=torch.float32, device="cuda")
-            ad.process_device(d_x.data_ptr() if n else 0, y1.data_ptr() if n else 0, n, s.cuda_stream)
-            if n == 0:
-                p2.process_device(0, 0, 0, s.cuda_stream)                   # the pre-run, and nothing else
-            else:
-                A.process_device(d_x.data_ptr(), n, ya.data_ptr() if m else 0, m, s.cuda_stream)
-                p2.process_device(ya.data_ptr() if m else 0, yb.data_ptr() if m else 0, m, s.cuda_stream)
-                B.process_device(yb.data_ptr() if m else 0, m, y2.data_ptr(), n, s.cuda_stream)
-            s.synchronize()
-            got.append(y1.cpu().numpy())
-            want.append(y2.cpu().numpy())
-    A.close()
-    B.close()
-    return np.concatenate(got, axis=1), np.concatenate(want, axis=1), p1, ad, p2
+    """LSTM-16 with the EQ and the gains on, 5 streams at 44.1 kHz around pools at 48 kHz, ragged host blocks with n = 1 and n = 0"""
+    return adapter_and_its_parts(model, ir, HOST_BLOCKS)
 
 
 @pytest.mark.parametrize("with_ir", [False, True])

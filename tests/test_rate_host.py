@@ -18,8 +18,12 @@ ERR_ARG = -1
 NEW = ("aidax_resampler_create", "aidax_resampler_destroy", "aidax_resampler_row", "aidax_resampler_process_device", "aidax_resampler_process",
        "aidax_resampler_ready", "aidax_resampler_reset_stream", "aidax_pool_samplerate", "aidax_rate_create", "aidax_rate_destroy",
        "aidax_rate_latency_frames", "aidax_rate_latency", "aidax_rate_process", "aidax_rate_process_device", "aidax_rate_reset_stream")
-# (rate_in, rate_out): L / M = 160 / 147, 147 / 160, 1 / 2, 2 / 1, 147 / 640, with the row length T = 2 ceil(32 max(L, M) / L) + 1
-ROW_PAIRS = (((44100, 48000), 160, 65), ((48000, 44100), 147, 71), ((96000, 48000), 1, 129), ((48000, 96000), 2, 65), ((192000, 44100), 147, 281))
+# (rate_in, rate_out): L / M = 160 / 147, 147 / 160, 1 / 2, 2 / 1, 147 / 640, with the row length T = 2 ceil(32 max(L, M) / L) + 1;
+# then the pairs of tests/test_gpu_rate_wide.py around the staged form's limit (77 -> 6 fills the LDS window, 90 -> 7 is the first in
+# place), the longest row the API admits (640 -> 1) and the most phases at the largest term (640 -> 639: all 639 run once)
+ROW_PAIRS = (((44100, 48000), 160, 65), ((48000, 44100), 147, 71), ((96000, 48000), 1, 129), ((48000, 96000), 2, 65), ((192000, 44100), 147, 281),
+             ((13, 1), 1, 833), ((77, 6), 6, 823), ((90, 7), 7, 825), ((96000, 7000), 7, 879), ((192000, 8000), 1, 1537), ((640, 1), 1, 40961),
+             ((640, 639), 639, 67))
 _fp = C.POINTER(C.c_float)
 
 
