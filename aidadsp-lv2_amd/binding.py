@@ -50,6 +50,17 @@ class Controls(C.Structure):
     _fields_ = [(n, C.c_float) for n in CONTROL_FIELDS]
 
 
+class StreamMeter(C.Structure):
+    """aidax_stream_meter: one stream's record (64 bytes)"""
+    _fields_ = [("frames", C.c_uint64), ("passes", C.c_uint64), ("in_nonfinite", C.c_uint64), ("out_nonfinite", C.c_uint64),
+                ("out_over", C.c_uint64), ("in_energy", C.c_double), ("out_energy", C.c_double), ("in_peak", C.c_float),
+                ("out_peak", C.c_float)]
+
+
+METER_DTYPE = np.dtype([("frames", "<u8"), ("passes", "<u8"), ("in_nonfinite", "<u8"), ("out_nonfinite", "<u8"), ("out_over", "<u8"),
+                        ("in_energy", "<f8"), ("out_energy", "<f8"), ("in_peak", "<f4"), ("out_peak", "<f4")])
+
+
 def lib_path() -> str:
     # AIDAX_LIB: another build of the library (A/B measurements of two builds in one gpurun call)
     return os.environ.get("AIDAX_LIB") or os.path.join(_HERE, "lib", "libaidax_hip.so")
@@ -200,6 +211,10 @@ def lib() -> C.CDLL:
     L.aidax_rate_process.argtypes = [vp, _fp, _fp, u32]
     L.aidax_rate_process_device.argtypes = [vp, vp, vp, u32, vp]
     L.aidax_rate_reset_stream.argtypes = [vp, u32]
+    if hasattr(L, "aidax_pool_read_meters"):       # (AIDAX_LIB may name a build from before the stream meters: A/B runs against it)
+        L.aidax_pool_set_metering.argtypes = [vp, C.c_int]
+        L.aidax_pool_metering.argtypes = [vp]
+        L.aidax_pool_read_meters.argtypes = [vp, u32, u32, C.POINTER(StreamMeter), C.c_int]
     _lib = L
     return L
 
@@ -505,6 +520,23 @@ class Pool:
 
     def ir_capacity(self) -> int:
         return int(lib().aidax_pool_ir_capacity(self.h))
+
+    def set_metering(self, on: bool):
+        """aidax_pool_set_metering: the per-stream meters on or off (the first enabling call allocates: a set-up side call)"""
+        _check(lib().aidax_pool_set_metering(self.h, 1 if on else 0))
+
+    @property
+    def metering(self) -> bool:
+        return bool(lib().aidax_pool_metering(self.h))
+
+    def read_meters(self, first: int = 0, count: Optional[int] = None, clear: bool = False) -> np.ndarray:
+        """aidax_pool_read_meters: the records of `count` streams from `first` (default: all from `first` on) as a structured array with
+        aidax_stream_meter's field names, behind every pass issued so far; clear zeroes exactly those records behind the copy"""
+        if count is None:
+            count = self.n_streams - first
+        out = np.zeros(max(count, 0), METER_DTYPE)
+        _check(lib().aidax_pool_read_meters(self.h, first, count, out.ctypes.data_as(C.POINTER(StreamMeter)), 1 if clear else 0))
+        return out
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

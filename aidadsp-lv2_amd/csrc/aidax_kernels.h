@@ -157,6 +157,18 @@ struct ResampleArgs {
 uint32_t resample_window(uint32_t L, uint32_t M, uint32_t H);      // floats of a full tile's input window
 hipError_t launch_resample(const ResampleArgs& a, hipStream_t q);
 
+// The stream meters (aidax_meter.hip, k_meter): one launch folds the rows of a pass's block, [n_active][n_frames], into the streams'
+// records, a wave per stream. MeterRec is aidax_stream_meter of include/aidax.h, field for field. side kMeterIn: the block the pass was
+// handed (in_nonfinite, in_energy, in_peak); kMeterOut: the block it returns (every other field, `frames` and `passes` among them).
+struct MeterRec {
+    uint64_t frames, passes, in_nonfinite, out_nonfinite, out_over;
+    double in_energy, out_energy;
+    float in_peak, out_peak;
+};
+static_assert(sizeof(MeterRec) == 64, "a stream's meter record is 64 bytes");
+enum { kMeterIn = 0, kMeterOut = 1 };
+hipError_t launch_meter(const float* buf, MeterRec* rec, uint32_t n_active, uint32_t n_frames, int side, hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdio>
 #include <cstdlib>
 #include <atomic>
@@ -363,6 +364,13 @@ struct aidax_pool {
 
     IrStage ir;                      // the cabinet IR stage behind every pass (aidax_ir_stage.h)
     bool any_pass = false;           // the pool has issued a pass of n_frames > 0 (its first one has nothing for an IR change to fade from)
+    // The stream meters (aidax_pool_set_metering; k_meter, aidax_meter.hip): nothing until the first call that switches them on, which
+    // allocates both; from then on `on` is a host record of the audio side
+    struct MeterStage {
+        MeterRec* d_rec = nullptr;   // [n_streams], nullptr: never enabled
+        MeterRec* h_rec = nullptr;   // pinned staging of aidax_pool_read_meters, [n_streams]
+        bool on = false;
+    } meter;
 
     // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
     // block k and the download of the blocks in front of it run under the pass of block k (allocated by the first submit).
@@ -677,6 +685,8 @@ struct aidax_pool {
     {
         ir.release();
         bank.release();
+        if (meter.d_rec) (void)hipFree(meter.d_rec);
+        if (meter.h_rec) (void)hipHostFree(meter.h_rec);
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);
         if (cur.d_nn) (void)hipFree(cur.d_nn);
@@ -952,12 +962,15 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         // with an IR history the pass ends behind the IR stage: its end marker (the submit path's event, the blocking path's completion
         // word) is not handed to the model's launch but issued after the stage by the caller
         const bool ir_on = n_frames != 0 && p->ir.adopt();
-        if (ir_on) {
-            p->pass_done = nullptr; p->pass_word = nullptr;
-            p->ir.begin_pass(s, p->any_pass);                          // the plan this pass is issued with, ahead of it
-        }
+        // ... and a metered pass behind k_meter's reading of the block it returns: the same rule, so that a pass that has ended for the host
+        // (aidax_pool_process has returned, the submit path's download may start) has also been metered
+        const bool meter_on = n_frames != 0 && p->meter.on;
+        if (ir_on || meter_on) { p->pass_done = nullptr; p->pass_word = nullptr; }
+        if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
+        if (meter_on) HIP_TRY(launch_meter(d_in, p->meter.d_rec, n_active, n_frames, kMeterIn, s));      // (ahead of the pass: it may work in place)
         HIP_TRY(p->launch(p->cur, a, s));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
+        if (meter_on) HIP_TRY(launch_meter(d_out, p->meter.d_rec, n_active, n_frames, kMeterOut, s));
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
@@ -1312,6 +1325,54 @@ AIDAX_API int aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps)
 }
 
 AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p) { return p ? p->ir.capacity.load(std::memory_order_relaxed) : 0; }
+
+// The stream meters. The first call that switches them on is the set-up side's: the records, zeroed, and the pinned staging of the read.
+// Every later call flips a host record of the audio side.
+static_assert(sizeof(aidax_stream_meter) == sizeof(MeterRec) && offsetof(aidax_stream_meter, out_over) == offsetof(MeterRec, out_over) &&
+                  offsetof(aidax_stream_meter, out_energy) == offsetof(MeterRec, out_energy) && offsetof(aidax_stream_meter, out_peak) == offsetof(MeterRec, out_peak),
+              "k_meter's record is aidax_stream_meter");
+AIDAX_API int aidax_pool_set_metering(aidax_pool* p, int on)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (!on || p->meter.d_rec) {
+        p->meter.on = on != 0;
+        return AIDAX_OK;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        const size_t bytes = sizeof(MeterRec) * p->n_streams;
+        if (!p->meter.h_rec) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->meter.h_rec), bytes, hipHostMallocDefault));
+        MeterRec* d = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
+        hipError_t cleared = hipMemsetAsync(d, 0, bytes, p->q);
+        if (cleared == hipSuccess) cleared = hipStreamSynchronize(p->q);      // (a pass on a caller's stream must find them zeroed)
+        if (cleared != hipSuccess) {
+            (void)hipFree(d);
+            HIP_TRY(cleared);
+        }
+        p->meter.d_rec = d;
+        p->meter.on = true;
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_metering(const aidax_pool* p) { return p && p->meter.on ? 1 : 0; }
+
+// Audio side, waits: the copy (and the clear behind it) enters the pool's own stream behind every pass issued so far, whatever stream carried it
+AIDAX_API int aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_stream_meter* out, int clear)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
+    if (!p->meter.d_rec) return fail(AIDAX_ERR_STATE, "metering was never enabled (aidax_pool_set_metering)");
+    return p->on_own_stream([&]() -> int {
+        const size_t bytes = sizeof(MeterRec) * count;
+        HIP_TRY(hipMemcpyAsync(p->meter.h_rec + first, p->meter.d_rec + first, bytes, hipMemcpyDeviceToHost, p->q));
+        if (clear) HIP_TRY(hipMemsetAsync(p->meter.d_rec + first, 0, bytes, p->q));
+        HIP_TRY(hipStreamSynchronize(p->q));
+        std::memcpy(out, p->meter.h_rec + first, bytes);
+        return AIDAX_OK;
+    });
+}
 
 AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
 {

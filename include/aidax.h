@@ -458,14 +458,66 @@ AIDAX_API int      aidax_rate_process(aidax_rate* r, const float* in, float* out
 AIDAX_API int      aidax_rate_process_device(aidax_rate* r, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream);
 AIDAX_API int      aidax_rate_reset_stream(aidax_rate* r, uint32_t stream);
 
+/* Stream meters: what is on each stream of a pool, computed where the blocks are. Opt-in: a pool that never switches them on allocates
+ * and launches exactly what it did before these calls existed, bit for bit, and a metered pool's audio is bit-identical to an unmetered
+ * pool's (the meters only read). While metering is on, every pass of n_frames > 0 folds each of its streams' rows into that stream's
+ * 64-byte record on the device, with two launches of k_meter on the pass's stream: one over the block the pass was handed, ahead of the
+ * model's launch, and one over the block it returns, behind the last stage.
+ * Input and output:
+ *  - "Input" is the stream's row of the block the pass was handed, before PREGAIN and everything else.
+ *  - "Output" is its row of the block the pass returns: behind the master ramp and, where the pool has an IR history, behind the IR stage
+ *    and its fade.
+ *  - A stream with `enabled` = 0 is metered like any other; its output is its input.
+ *  - Under a rate adapter the blocks, and so the frames counted, are the pool's: the pool-rate blocks between the adapter's two stages.
+ * Which passes are metered:
+ *  - A pass is metered when metering is on at the moment it is issued: the blocking path, aidax_pool_submit* / collect (the blocks in
+ *    flight too), aidax_pool_process_device on the pool's or a caller's stream, passes under aidax_rate_*.
+ *  - A pass of n_frames == 0 touches nothing, and a pass issued while metering is off is not counted.
+ *  - The records survive switching off and on, aidax_pool_reset_stream, model and IR swaps and assignments; only `clear` zeroes them.
+ *  - `frames` and `passes` are counted by the output side: a pass that fails on its way may leave its input side counted.
+ * Arithmetic:
+ *  - Peaks, counts and `frames` are exact.
+ *  - Each square is formed in fp64 from the fp32 sample (exact: 48 significant bits) and the squares are summed in fp64 in an unspecified
+ *    order. All terms are non-negative, so an energy is within frames x 2^-52 relative of the exact sum.
+ *  - A sample that is NaN or +-Inf is counted as non-finite and enters neither the peak nor the energy of its side.
+ * aidax_pool_set_metering  the FIRST call with on != 0 is a SET-UP side call, like aidax_pool_set_ir_capacity: it allocates n_streams
+ *                          zeroed records on the device and the pinned staging of the read, and may wait. Every later call is an AUDIO
+ *                          side host record, between passes: no allocation, no free, no wait. A call with on == 0 before any with
+ *                          on != 0 changes nothing. AIDAX_ERR_ARG for a null pool.
+ * aidax_pool_metering      1 while metering is on, else 0 (0 for a null pool).
+ * aidax_pool_read_meters   AUDIO side, and it waits, like aidax_pool_export_stream_dsp: the copy of `count` records from stream `first`
+ *                          enters the pool's own stream behind every pass issued so far, on whatever stream; with clear != 0 exactly those
+ *                          records are zeroed behind the copy, stream-ordered, so no sample between copy and clear is lost; then the
+ *                          call waits for that stream only. AIDAX_ERR_ARG for a null argument, count == 0 or first + count > n_streams
+ *                          (nothing is changed), AIDAX_ERR_STATE when metering was never enabled.
+ * A stream whose biquad memories went non-finite (one NaN or Inf in its input is enough) stays that way until aidax_pool_reset_stream,
+ * as an instance of the reference does. Where the model lets the NaN through to the output (in_skip = 1, for one) its out_nonfinite
+ * grows from pass to pass while its in_nonfinite does not; the recurrent kernels clamp their tanh arguments in a way that turns a NaN
+ * into a saturated finite value, so without such a path the stuck stream's output is finite and only in_nonfinite tells. A host
+ * resets a stream on either count ("Stream meters"). Hub seats are not metered (a hub parks seats as disabled raw copies of stale rows: aidax_hub never switches its pool's meters on). */
+typedef struct {
+    uint64_t frames;           /* frames metered since the last clear                                 */
+    uint64_t passes;           /* passes of n_frames > 0 metered since the last clear                 */
+    uint64_t in_nonfinite;     /* input samples that are NaN or +-Inf                                 */
+    uint64_t out_nonfinite;    /* output samples that are NaN or +-Inf                                */
+    uint64_t out_over;         /* finite output samples with |x| > 1.0f                               */
+    double   in_energy;        /* sum of x*x over the finite input samples, in fp64                   */
+    double   out_energy;       /* ... over the finite output samples                                  */
+    float    in_peak;          /* max |x| over the finite input samples, 0 if none                    */
+    float    out_peak;         /* ... output samples                                                  */
+} aidax_stream_meter;          /* 64 bytes, no padding */
+AIDAX_API int  aidax_pool_set_metering(aidax_pool* p, int on);
+AIDAX_API int  aidax_pool_metering(const aidax_pool* p);
+AIDAX_API int  aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_stream_meter* out, int clear);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_model, set_ir_fade, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side); aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_sync / aidax_rate_process wait for the GPU (for the stream that carries the pass, never for the
+ * aidax_pool_process / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters wait for the GPU (for the stream that carries the pass, never for the
  * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir or a commit_ir) and changed model-bank records (after an assign_model), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
