@@ -92,6 +92,14 @@ build/asan/asan_ir_harness: $(ASAN_IR_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_IR_SRCS) -o $@
 asan_ir: build/asan/asan_ir_harness
 
+# ... and the IR blend's rules (IrPlan's second assignment, ramps, blend section and list): tests/asan_ir_blend_harness.cpp, tests/test_asan_ir_blend.py
+ASAN_IR_BLEND_SRCS := tests/asan_ir_blend_harness.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
+build/asan/asan_ir_blend_harness: $(ASAN_IR_BLEND_SRCS) $(HDRS) $(SRC)/json_min.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_IR_BLEND_SRCS) -o $@
+asan_ir_blend: build/asan/asan_ir_blend_harness
+
 # ... and the model bank's host half (ModelBank: who plays which slot, the per-stream records, the commit rules): tests/asan_bank_harness.cpp, tests/test_asan_bank.py
 ASAN_BANK_SRCS := tests/asan_bank_harness.cpp $(SRC)/aidax_model_bank.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
 build/asan/asan_bank_harness: $(ASAN_BANK_SRCS) $(HDRS) $(SRC)/json_min.h
@@ -108,4 +116,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_bank
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank

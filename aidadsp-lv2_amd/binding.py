@@ -211,6 +211,10 @@ def lib() -> C.CDLL:
     L.aidax_rate_process.argtypes = [vp, _fp, _fp, u32]
     L.aidax_rate_process_device.argtypes = [vp, vp, vp, u32, vp]
     L.aidax_rate_reset_stream.argtypes = [vp, u32]
+    if hasattr(L, "aidax_pool_set_ir_mix"):        # (... or from before the IR blend)
+        L.aidax_pool_assign_ir_b.argtypes = [vp, i32, i32]
+        L.aidax_pool_set_ir_mix.argtypes = [vp, i32, C.c_float, u32]
+        L.aidax_pool_stream_ir_mix.argtypes = [vp, u32, C.POINTER(i32), _fp, _fp, C.POINTER(u32)]
     if hasattr(L, "aidax_pool_read_meters"):       # (AIDAX_LIB may name a build from before the stream meters: A/B runs against it)
         L.aidax_pool_set_metering.argtypes = [vp, C.c_int]
         L.aidax_pool_metering.argtypes = [vp]
@@ -505,6 +509,22 @@ class Pool:
         v = C.c_int32(0)
         _check(lib().aidax_pool_stream_ir(self.h, stream, C.byref(v)))
         return v.value
+
+    def assign_ir_b(self, stream: int, slot: int):
+        """aidax_pool_assign_ir_b: the second IR of `stream` (ALL_STREAMS: every stream), the one its mix blends in (IR_POOL, IR_NONE, the
+        default, or a bank slot)"""
+        _check(lib().aidax_pool_assign_ir_b(self.h, stream, slot))
+
+    def set_ir_mix(self, stream: int, mix: float, ramp_frames: int = 0):
+        """aidax_pool_set_ir_mix: the weight of the second IR moves to `mix` (0 .. 1) over the stream's next `ramp_frames` frames (0: a jump
+        at the block boundary)"""
+        _check(lib().aidax_pool_set_ir_mix(self.h, stream, mix, ramp_frames))
+
+    def stream_ir_mix(self, stream: int):
+        """aidax_pool_stream_ir_mix: (slot_b, mix_now, mix_target, frames_left) behind the last pass issued"""
+        b, now, target, left = C.c_int32(0), C.c_float(0), C.c_float(0), C.c_uint32(0)
+        _check(lib().aidax_pool_stream_ir_mix(self.h, stream, C.byref(b), C.byref(now), C.byref(target), C.byref(left)))
+        return b.value, now.value, target.value, left.value
 
     def set_ir_fade(self, frames: int):
         """aidax_pool_set_ir_fade: crossfade old and new IR over the first min(frames, n_frames) frames of the pass behind an IR change

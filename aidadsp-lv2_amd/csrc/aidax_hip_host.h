@@ -71,6 +71,7 @@ inline int read_hip_calls(char* buf, uint32_t cap)
 #define launch_ir_append(...) (aidax::note_hip_call("launch_ir_append"), aidax::launch_ir_append(__VA_ARGS__))
 #define launch_ir_conv(...) (aidax::note_hip_call("launch_ir_conv"), aidax::launch_ir_conv(__VA_ARGS__))
 #define launch_ir_fade(...) (aidax::note_hip_call("launch_ir_fade"), aidax::launch_ir_fade(__VA_ARGS__))
+#define launch_ir_mix(...) (aidax::note_hip_call("launch_ir_mix"), aidax::launch_ir_mix(__VA_ARGS__))
 #define launch_meter(...) (aidax::note_hip_call("launch_meter"), aidax::launch_meter(__VA_ARGS__))
 #endif
 

@@ -47,6 +47,12 @@ void IrPlan::init(uint32_t n)
     fade_out.streams.resize(n);
     mix.resize(n);
     src.resize(n);
+    assign_b.assign(n, AIDAX_IR_NONE);
+    ramp.assign(n, Ramp{});
+    was_blended.assign(n, 0);
+    blend.items.resize(runs + kKeys);
+    blend.streams.resize(n);
+    blend_list.resize(n);
 }
 
 // A section from src[]: the streams with src[s] >= 0 grouped by source, the sources in index order, each one's streams in stream order,
@@ -80,24 +86,73 @@ uint32_t IrPlan::group(IrSection& sec, int n_sources)
 // switches without a fade too.
 void IrPlan::rebuild(bool any_pass)
 {
-    for (uint32_t s = 0; s < n_streams; ++s) src[s] = static_cast<int16_t>(key(s));
+    for (uint32_t s = 0; s < n_streams; ++s) src[s] = static_cast<int16_t>(eff_key(s));
     identity = group(main, kKeys) == n_streams;
     const bool fading = any_pass && fade != 0;
     spend_fade();
     for (uint32_t s = 0; s < n_streams; ++s) {
         const int nk = src[s], ok = played_key[s];
         const uint64_t ng = nk >= 0 ? live[nk].gen : 0, og = played_gen[s];
+        const bool blended = rest(s) < 0, hand_over = blended || was_blended[s];      // coming to rest and leaving it is no IR change
         src[s] = -2;                                               // no fade
         played_key[s] = static_cast<int8_t>(nk);
         played_gen[s] = ng;
-        if (!fading || (nk == ok && ng == og)) continue;
+        was_blended[s] = blended;
+        if (!fading || hand_over || (nk == ok && ng == og)) continue;
         if (ok < 0) src[s] = -1;                                   // from the dry block
         else if (live[ok].d_frag && live[ok].gen == og) src[s] = static_cast<int16_t>(ok);
         else if (parked[ok].d_frag && parked[ok].gen == og) src[s] = static_cast<int16_t>(kKeys + ok);
         if (src[s] >= -1) mix[n_mix++] = s | (src[s] < 0 ? kIrFadeDry : 0u);
     }
     if (n_mix) group(fade_out, 2 * kKeys);
+    // the blended streams: their B sides, and each one's ramp as it stands
+    blend.clear();
+    n_blend = since_build = rest_in = blend_hi = 0;
+    for (uint32_t s = 0; s < n_streams; ++s) {
+        src[s] = -1;
+        if (!was_blended[s]) continue;
+        const Ramp& r = ramp[s];
+        src[s] = static_cast<int16_t>(key_b(s));
+        blend_list[n_blend++] = IrBlendEntry{ s | (src[s] < 0 ? kIrBlendDry : 0u), r.m0, r.m1, r.len, r.k };
+        blend_hi = s;
+        if (r.m1 == 0.f || r.m1 == 1.f) {                          // (blended: at least two frames left)
+            const uint32_t in = frames_left(s) - 1u;
+            rest_in = rest_in ? std::min(rest_in, in) : in;
+        }
+    }
+    if (n_blend) group(blend, kKeys);
     dirty = false;
+}
+
+void IrPlan::set_mix(uint32_t s, float mix, uint32_t len)
+{
+    Ramp& r = ramp[s];
+    const int before = rest(s);
+    if (frames_left(s) != 0) --n_moving;
+    r.m0 = r.now;
+    r.m1 = mix + 0.f;                                              // (-0 is 0)
+    r.len = len;
+    r.k = 0;
+    if (r.m0 == r.m1) r.len = 0, r.k = 1;
+    else ++n_moving;
+    if (before < 0 || rest(s) != before) dirty = true;
+}
+
+void IrPlan::advance(uint32_t n_active, uint32_t n_frames)
+{
+    if (n_frames == 0) return;
+    if (n_blend) {
+        since_build = std::min(since_build + n_frames, kIrMaxRampOffset);
+        if (blend_hi >= n_active) dirty = true;                    // a prefix pass: the streams it left out are where they were
+    }
+    if (n_moving == 0) return;
+    for (uint32_t s = 0; s < n_active; ++s) {
+        if (frames_left(s) == 0) continue;
+        Ramp& r = ramp[s];
+        r.k += std::min(n_frames, frames_left(s));
+        r.now = weight(r, r.k - 1u);
+        if (frames_left(s) == 0) --n_moving;
+    }
 }
 
 void IrPlan::commit(int key, IrSlot& staged)
@@ -117,12 +172,20 @@ size_t IrPlan::serialise(uint8_t* snapshot) const
 {
     std::memcpy(snapshot, main.items.data(), main.n_items * sizeof(IrItem));
     std::memcpy(snapshot + plan_items_bytes(), main.streams.data(), main.n_listed * sizeof(uint32_t));
-    if (n_mix == 0) return plan_items_bytes() + main.n_listed * sizeof(uint32_t);
+    if (n_mix == 0 && n_blend == 0) return plan_items_bytes() + main.n_listed * sizeof(uint32_t);
+    if (n_blend != 0) {
+        // (one copy up to the end of the blend list, over the fade-out section's place whether that holds a section or not)
+        std::memcpy(snapshot + blend_items_off(), blend.items.data(), blend.n_items * sizeof(IrItem));
+        std::memcpy(snapshot + blend_streams_off(), blend.streams.data(), blend.n_listed * sizeof(uint32_t));
+        std::memcpy(snapshot + blend_list_off(), blend_list.data(), n_blend * sizeof(IrBlendEntry));
+        if (n_mix == 0) return blend_list_off() + n_blend * sizeof(IrBlendEntry);
+    }
     // the fade-out section rides in the same upload: one copy up to the end of the mix list. It also carries the snapshot's gaps
     // (stream-list entries past n_listed, items past n_items), which no kernel reads: the counts travel as arguments
     std::memcpy(snapshot + fade_items_off(), fade_out.items.data(), fade_out.n_items * sizeof(IrItem));
     std::memcpy(snapshot + fade_streams_off(), fade_out.streams.data(), fade_out.n_listed * sizeof(uint32_t));
     std::memcpy(snapshot + fade_mix_off(), mix.data(), n_mix * sizeof(uint32_t));
+    if (n_blend != 0) return blend_list_off() + n_blend * sizeof(IrBlendEntry);
     return fade_mix_off() + n_mix * sizeof(uint32_t);
 }
 

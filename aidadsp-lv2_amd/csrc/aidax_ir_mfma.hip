@@ -253,6 +253,40 @@ __global__ __launch_bounds__(256) void k_ir_fade(IrFadeArgs a)
     a.out[at] = __builtin_fmaf(w, a.out[at], u * was);
 }
 
+// The blend of two IRs, in place on ALL frames of the blended streams' output rows (which hold the A side: the main section's
+// convolution, or the dry block of a stream whose A is no IR). The B side is the blend section's row of the side buffer, or the dry
+// samples out of the history ring. Thread i: entry i / n_frames of `list`, frame i % n_frames. The weight is a function of the ramp
+// frame alone (aidax_kernels.h): every fp64 operation is rounded on its own (no contraction in here; the v_fma_f64 of the disassembly
+// are the division's own refinement steps), so a ramp gives the same bits however the host cuts it into blocks.
+__global__ __launch_bounds__(256) void k_ir_mix(IrBlendArgs a)
+{
+#pragma clang fp contract(off)
+    const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.n_blend * a.n_frames) return;
+    const uint32_t j = i / a.n_frames, t = i - j * a.n_frames;
+    const IrBlendEntry e = a.list[j];
+    const uint32_t s = e.stream & ~kIrBlendDry;
+    if (s >= a.n_streams) return;
+    const uint32_t k = e.k + a.k_off + t;                              // (<= 2^24 + 2^25 + the block: no wrap)
+    float w = e.m1;
+    double ud = 1.0 - static_cast<double>(e.m1);
+    if (k + 1u < e.ramp) {
+        const double step = static_cast<double>(e.m1) - static_cast<double>(e.m0);
+        const double run = step * static_cast<double>(k + 1u);
+        const double part = run / static_cast<double>(e.ramp);
+        const double wd = static_cast<double>(e.m0) + part;
+        w = static_cast<float>(wd);
+        ud = 1.0 - wd;
+    }
+    const float u = static_cast<float>(ud);
+    const size_t at = static_cast<size_t>(s) * a.n_frames + t;
+    if (w == 0.f) return;                                              // A's bits, as they are
+    const float yb = (e.stream & kIrBlendDry) ? a.ring[static_cast<size_t>(s) * a.ring_row + ((a.pos + t) & a.mask)] : a.side[at];
+    if (w == 1.f) { a.out[at] = yb; return; }
+    const float ua = u * a.out[at];
+    a.out[at] = __builtin_fmaf(w, yb, ua);
+}
+
 }  // namespace
 
 uint32_t ir_diagonals(uint32_t n_taps) { return (n_taps + 30u) / 16u + 1u; }
@@ -295,6 +329,14 @@ hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q)
     if (a.n_mix == 0 || a.lf == 0 || a.n_frames == 0) return hipSuccess;
     const uint32_t count = a.n_mix * a.lf;
     hipLaunchKernelGGL(k_ir_fade, dim3((count + 255u) / 256u), dim3(256), 0, q, a);
+    return hipGetLastError();
+}
+
+hipError_t launch_ir_mix(const IrBlendArgs& a, hipStream_t q)
+{
+    if (a.n_blend == 0 || a.n_frames == 0) return hipSuccess;
+    const uint32_t count = a.n_blend * a.n_frames;
+    hipLaunchKernelGGL(k_ir_mix, dim3((count + 255u) / 256u), dim3(256), 0, q, a);
     return hipGetLastError();
 }
 

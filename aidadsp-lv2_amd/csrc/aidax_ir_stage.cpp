@@ -57,7 +57,7 @@ void IrStage::prepare(const float* taps, uint32_t n_taps, IrSlot& ir)
         HIP_TRY(hipMalloc(&h->ring, ring_bytes));
         if (h->split_cap > 1) HIP_TRY(hipMalloc(&h->part, sizeof(float) * block * h->split_cap));
         HIP_TRY(hipMalloc(&h->side, sizeof(float) * block));
-        const size_t plan_bytes = plan.plan_bytes();         // both sections, whether a fade length is set or not
+        const size_t plan_bytes = plan.total_bytes();        // every section, whether a fade length is set or a stream blended or not
         HIP_TRY(hipMalloc(&h->d_plan, plan_bytes));
         h->plan_ring.alloc(plan_bytes);
         HIP_TRY(hipMemsetAsync(h->ring, 0, ring_bytes, wq_));
@@ -136,7 +136,24 @@ void IrStage::issue(hipStream_t s, float* d_out, uint32_t n_active, uint32_t n_f
         fm.lf = std::min(plan.fade, n_frames);
         HIP_TRY(launch_ir_fade(fm, s));
     }
-    plan.pass_issued();
+    if (plan.n_blend) {
+        // blended streams: their B sides over the same history into their rows of the side buffer (the blend section: the same kernel,
+        // K split and fixed-order reduce, `part` reused behind the earlier reduces), then the mix over all frames in place on d_out, at
+        // the ramp positions of the plan plus the frames issued since it was built
+        if (plan.blend.n_items) {
+            IrArgs ba = conv_args(plan.blend, plan.blend_items_off(), plan.blend_streams_off(), h->side, n_active, n_frames);
+            ba.n_splits = ir_k_splits(ba.n_items, n_frames, plan.blend.max_diag, cus_, h->split_cap);
+            HIP_TRY(launch_ir_conv(ba, s));
+        }
+        IrBlendArgs bm{};
+        bm.list = reinterpret_cast<const IrBlendEntry*>(h->d_plan + plan.blend_list_off());
+        bm.side = h->side; bm.ring = h->ring; bm.out = d_out;
+        bm.n_blend = plan.n_blend; bm.ring_row = h->ring_row; bm.mask = h->mask; bm.pos = pos_;
+        bm.n_streams = n_active; bm.n_frames = n_frames;
+        bm.k_off = plan.since_build;
+        HIP_TRY(launch_ir_mix(bm, s));
+    }
+    plan.pass_issued(n_active, n_frames);
     pos_ = (pos_ + n_frames) & h->mask;
 }
 

@@ -2,6 +2,7 @@
 // the work items k_ir_conv runs for that), and IrStage, the device half around it (aidax_ir_stage.cpp: the history, the uploads, the launches).
 #pragma once
 
+#include <algorithm>
 #include <atomic>
 #include <cstdint>
 #include <vector>
@@ -36,6 +37,15 @@ struct IrSection {
 // stream to the fade-out section: the old IRs (still live, or parked, see commit) with the streams fading from them, and to the mix list
 // (k_ir_fade: stream index, kIrFadeDry set where the old side is the dry block). That section serves the one pass it was built for:
 // pass_issued() ends it, and so does spend_fade() for a pass that failed on its way.
+//
+// The blend (include/aidax.h, "IR blend"). A stream has a second assignment B and a mix, the weight of B, that ramps over the frames
+// issued for the stream (Ramp). A stream whose coming frames all carry a weight of exactly 0 or 1 is at rest: it is listed once, in the
+// main section, under A or under B (eff_key), like any one-IR stream. Every other stream is blended: in `main` under A, in the `blend`
+// section under B (live slots only; either side may be nothing: the dry block) and in blend_list with its ramp as the rebuild found it.
+// The plan is NOT rebuilt as a ramp moves on: the frames issued since the rebuild travel as k_ir_mix's k_off (since_build, the same for
+// every blended stream, since a pass advances them all). It is rebuilt when a blended stream comes to rest on 0 or 1 (stale()), after
+// set_mix and assignments of B, and after a prefix pass that left a blended stream out (advance). A stream that is blended in the last
+// pass issued or in this one never joins the fade-out section.
 struct IrPlan {
     static constexpr int kKeys = AIDAX_IR_SLOTS + 1;
     uint32_t n_streams = 0;
@@ -52,6 +62,19 @@ struct IrPlan {
     std::vector<uint32_t> mix;               // [n_streams]
     uint32_t n_mix = 0;
     bool identity = false, dirty = true;
+    // a ramp m0 -> m1 over `len` frames, `k` of which have been issued (saturating at max(len, 1): frames_left() == 0); `now` is the
+    // weight of the last frame issued. Ramp frame k carries m1 once k + 1 >= len, so a ramp of 0 or 1 frames is a jump at the boundary.
+    struct Ramp { float m0 = 0.f, m1 = 0.f, now = 0.f; uint32_t len = 0, k = 1; };
+    std::vector<int32_t> assign_b;           // [n_streams]
+    std::vector<Ramp> ramp;                  // [n_streams]
+    std::vector<uint8_t> was_blended;        // [n_streams]: blended in the plan of the last rebuild
+    IrSection blend;                         // items: [ceil(n_streams / 64) + 65]
+    std::vector<IrBlendEntry> blend_list;    // [n_streams]
+    uint32_t n_blend = 0;
+    uint32_t since_build = 0;                // frames issued since the rebuild, while streams are blended (saturating at kIrMaxRampOffset)
+    uint32_t rest_in = 0;                    // ... at which the first blended stream comes to rest on 0 or 1 (0: none will)
+    uint32_t blend_hi = 0;                   // the last blended stream
+    uint32_t n_moving = 0;                   // streams with frames_left() != 0
 
     void init(uint32_t n);
     int key(uint32_t s) const                // the key of the IR stream s goes through; -1: none (also an empty slot)
@@ -60,9 +83,39 @@ struct IrPlan {
         const int k = 1 + assign[s];
         return k >= 0 && live[k].d_frag ? k : -1;
     }
-    // both sections for the pass about to be issued, and every stream's played record brought up to that pass
+    int key_b(uint32_t s) const
+    {
+        const int k = 1 + assign_b[s];
+        return k >= 0 && live[k].d_frag ? k : -1;
+    }
+    uint32_t frames_left(uint32_t s) const { return std::max(ramp[s].len, 1u) - ramp[s].k; }
+    // 0 / 1: every coming frame of the stream has exactly that weight (at rest on A / on B); -1: the stream is blended
+    int rest(uint32_t s) const
+    {
+        const Ramp& r = ramp[s];
+        if (frames_left(s) > 1u) return -1;
+        return r.m1 == 0.f ? 0 : r.m1 == 1.f ? 1 : -1;
+    }
+    int eff_key(uint32_t s) const { return rest(s) == 1 ? key_b(s) : key(s); }       // a stream at rest: its effective IR
+    // the weight of ramp frame k (aidax_kernels.h: k_ir_mix computes the same, operation by operation)
+    static float weight(const Ramp& r, uint32_t k)
+    {
+        if (k + 1u >= r.len) return r.m1;
+        const double step = static_cast<double>(r.m1) - static_cast<double>(r.m0);
+        const double run = step * static_cast<double>(k + 1u);
+        const double part = run / static_cast<double>(r.len);
+        return static_cast<float>(static_cast<double>(r.m0) + part);
+    }
+    // aidax_pool_set_ir_mix for one stream: a ramp from the weight of the last frame issued; between equal weights it has ended already
+    void set_mix(uint32_t s, float mix, uint32_t len);
+    // the sections for the pass about to be issued, and every stream's played record brought up to that pass
     void rebuild(bool any_pass);
+    // has a blended stream of the plan come to rest on 0 or 1 with the frames issued since the rebuild?
+    bool stale() const { return n_blend != 0 && rest_in != 0 && since_build >= rest_in; }
     void pass_issued() { ++pass_seq; spend_fade(); }
+    // ... of n_frames for the first n_active streams: their ramps move on
+    void pass_issued(uint32_t n_active, uint32_t n_frames) { pass_issued(); advance(n_active, n_frames); }
+    void advance(uint32_t n_active, uint32_t n_frames);
     void spend_fade() { fade_out.clear(); n_mix = 0; }
     // the host half of aidax_pool_commit_ir: `staged` becomes the content of `key` and gets back what is to be freed
     void commit(int key, IrSlot& staged);
@@ -74,6 +127,11 @@ struct IrPlan {
     size_t fade_streams_off() const { return fade_items_off() + fade_out.items.size() * sizeof(IrItem); }
     size_t fade_mix_off() const { return fade_streams_off() + sizeof(uint32_t) * n_streams; }
     size_t plan_bytes() const { return fade_mix_off() + sizeof(uint32_t) * n_streams; }
+    // ... and behind them, in a plan with blended streams only, the blend section's items and stream list and the blend list
+    size_t blend_items_off() const { return (plan_bytes() + 7u) & ~size_t(7); }
+    size_t blend_streams_off() const { return blend_items_off() + blend.items.size() * sizeof(IrItem); }
+    size_t blend_list_off() const { return blend_streams_off() + sizeof(uint32_t) * n_streams; }
+    size_t total_bytes() const { return blend_list_off() + sizeof(IrBlendEntry) * n_streams; }
     size_t serialise(uint8_t* snapshot) const;
 
   private:
@@ -112,9 +170,11 @@ struct IrStage {
     void begin_pass(hipStream_t s, bool any_pass)
     {
         plan.spend_fade();
+        if (plan.stale()) plan.dirty = true;                 // a ramp has ended on 0 or 1: that stream is a one-IR stream from this pass on
         if (plan.dirty) flush_plan(s, any_pass);
     }
-    // behind it: the block's dry samples into the history, the convolution in place on d_out, the fade-out section and the mix
+    // behind it: the block's dry samples into the history, the convolution in place on d_out, the fade-out section and its mix, the
+    // blend section and its mix; the ramps of the pass's streams move on by n_frames
     void issue(hipStream_t s, float* d_out, uint32_t n_active, uint32_t n_frames);
     void clear_stream(uint32_t stream, hipStream_t q);       // one stream's past, if there is a history
     void clear_all(hipStream_t q);                           // every stream's (errors ignored: the k_mfma_lp give-up path)

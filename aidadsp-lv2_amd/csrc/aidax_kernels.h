@@ -136,6 +136,29 @@ struct IrFadeArgs {
     uint32_t n_mix, ring_row, mask, pos, n_streams, n_frames, lf;
 };
 hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q);
+// The blend of two IRs (k_ir_mix), behind launch_ir_conv of the pass and of its blend section: for every entry of `list` ALL frames of
+// the stream's row of `out` (its A side: the main section's convolution, or the dry block) become u[k] A + w[k] B, B being the stream's
+// row of `side` or, with kIrBlendDry set in `stream`, its dry block out of the ring at pos + t. Frame t of the pass is ramp frame
+// k = entry.k + k_off + t of a ramp m0 -> m1 over `ramp` frames: for k + 1 < ramp, wd = m0 + (m1 - m0) (k + 1) / ramp in fp64 (one
+// subtraction, one multiplication, one division, one addition, each rounded), w = (float)wd, u = (float)(1 - wd); from then on w = m1,
+// u = (float)(1 - (double)m1). w == 0 leaves A's bits, w == 1 gives B's, otherwise fmaf(w, B, u * A) with the product rounded to fp32.
+// entry.k <= 2^24 and k_off <= 2^25 (the host saturates it: beyond any ramp's end). An entry at or beyond n_streams is skipped.
+constexpr uint32_t kIrBlendDry = 0x80000000u;
+constexpr uint32_t kIrMaxRamp = 1u << 24;
+constexpr uint32_t kIrMaxRampOffset = 1u << 25;
+struct IrBlendEntry {
+    uint32_t stream;
+    float m0, m1;
+    uint32_t ramp, k;
+};
+struct IrBlendArgs {
+    const IrBlendEntry* list;
+    const float* side;
+    const float* ring;
+    float* out;
+    uint32_t n_blend, ring_row, mask, pos, n_streams, n_frames, k_off;
+};
+hipError_t launch_ir_mix(const IrBlendArgs& a, hipStream_t q);
 
 // The streaming resampler (aidax_resample.hip, k_resample): one launch appends the call's n_in new frames per stream to the history ring
 // (per stream a row of mask + 1 floats, frame k in slot k & mask) and writes the call's n_out outputs per stream. Output t of the call has

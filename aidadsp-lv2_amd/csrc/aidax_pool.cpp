@@ -970,6 +970,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (meter_on) HIP_TRY(launch_meter(d_in, p->meter.d_rec, n_active, n_frames, kMeterIn, s));      // (ahead of the pass: it may work in place)
         HIP_TRY(p->launch(p->cur, a, s));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
+        else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
         if (meter_on) HIP_TRY(launch_meter(d_out, p->meter.d_rec, n_active, n_frames, kMeterOut, s));
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
@@ -1311,6 +1312,50 @@ AIDAX_API int aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames)
 }
 
 AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir.plan.fade : 0; }
+
+// Audio thread: host assignments only. A stream at rest on A does not play its B side: the plan stands.
+AIDAX_API int aidax_pool_assign_ir_b(aidax_pool* p, int32_t stream, int32_t slot)
+{
+    if (slot != AIDAX_IR_POOL && slot != AIDAX_IR_NONE && (slot < 0 || slot >= AIDAX_IR_SLOTS))
+        return fail(AIDAX_ERR_ARG, "IR slot must be the pool IR (-1), none (-2) or 0 .. 63");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    IrPlan& plan = p->ir.plan;
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    for (uint32_t s = lo; s < hi; ++s) {
+        if (plan.assign_b[s] == slot) continue;
+        plan.assign_b[s] = slot;
+        if (plan.rest(s) != 0) plan.dirty = true;
+    }
+    return AIDAX_OK;
+}
+
+// Audio thread: host records (every stream's ramp starts from its own weight of the last frame issued).
+AIDAX_API int aidax_pool_set_ir_mix(aidax_pool* p, int32_t stream, float mix, uint32_t ramp_frames)
+{
+    if (!(mix >= 0.f && mix <= 1.f)) return fail(AIDAX_ERR_ARG, "IR mix must be a finite value in [0, 1]");
+    if (ramp_frames > kIrMaxRamp) return fail(AIDAX_ERR_ARG, "IR mix ramp must be 0 .. 16777216 frames");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    IrPlan& plan = p->ir.plan;
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    for (uint32_t s = lo; s < hi; ++s) plan.set_mix(s, mix, ramp_frames);
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_stream_ir_mix(const aidax_pool* p, uint32_t stream, int32_t* slot_b, float* mix_now, float* mix_target, uint32_t* frames_left)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const IrPlan& plan = p->ir.plan;
+    if (slot_b) *slot_b = plan.assign_b[stream];
+    if (mix_now) *mix_now = plan.ramp[stream].now;
+    if (mix_target) *mix_target = plan.ramp[stream].m1;
+    if (frames_left) *frames_left = plan.frames_left(stream);
+    return AIDAX_OK;
+}
 
 // Set-up side: a host record that the first prepare reads when it sizes the history ring (R >= capacity + max_frames); the kernels take
 // the ring's mask and row, and every IR's diagonal count, at run time.

@@ -338,6 +338,43 @@ AIDAX_API int  aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_
 AIDAX_API int      aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames);
 AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p);
 
+/* IR blend: a stream through two IRs at once, and crossfades longer than a pass. Besides its assignment A (aidax_pool_assign_ir) a stream
+ * has a second assignment B (AIDAX_IR_NONE by default) and a mix w in [0, 1], the weight of B (0 by default):
+ *     y[t] = u (h_A * x)[t] + w (h_B * x)[t]
+ * with "nothing" on either side (AIDAX_IR_NONE, an empty slot, the pool IR of a pool without one) the unit impulse: that side is the dry
+ * block, so B = AIDAX_IR_NONE with a mix is a wet / dry control. The mix moves in ramps that outlive a pass. m_now is the fp32 weight of
+ * the last frame issued for the stream (0 for a stream that never had a mix); aidax_pool_set_ir_mix(.., mix, R) starts a ramp from
+ * m0 = m_now to m1 = mix whose frame k = 0 is the stream's next issued frame (several calls between two passes: the last one wins, m0 is
+ * unchanged; a ramp between equal weights has ended when it is set). Ramp frame k has, in fp64 with every operation rounded on its own,
+ *     k + 1 <  R:  wd = (double)m0 + ((double)m1 - (double)m0) * (double)(k + 1) / (double)R,  w = (float)wd,  u = (float)(1.0 - wd)
+ *     k + 1 >= R:  w = m1,  u = (float)(1.0 - (double)m1)                                    (R = 0: a jump at the block boundary)
+ * and k counts the stream's issued frames, not passes: a ramp's weights do not depend on how the host cuts the stream into blocks. A frame
+ * with w == 0 returns A's bits, one with w == 1 B's, any other fmaf(w, yB, u * yA) with the product rounded to fp32 (k_ir_mix).
+ * At rest: a stream all of whose coming frames have a weight of exactly 0 or 1 is an ordinary one-IR stream. It costs and returns exactly
+ * what a stream assigned to that IR (A on 0, B on 1) returns, and that IR is its effective IR in the sense of the IR fade. Every pass issued
+ * after the one in which a ramp ends on 0 or 1 is bit-identical, for that stream, to a pool in which the stream was assigned that IR with
+ * aidax_pool_assign_ir. Coming to rest and leaving rest is never an IR change for the IR fade. A stream that rests strictly inside (0, 1)
+ * stays blended at a constant weight.
+ * While blended (a ramp is running, or the stream rests inside (0, 1)) a change of A or B (an assignment, a commit into the slot that side
+ * plays) takes effect on that side at the block boundary, unfaded: to replace a cabinet without a click, move the mix off that side first
+ * (INTEGRATION.md). The IR fade applies to a stream only when it is at rest in the last pass issued and in this one.
+ * Ramp positions are host integers, advanced by n_frames for the streams of every pass issued (not by a pass of 0 frames or one that failed
+ * on its way; a prefix pass of the hub advances the streams of the prefix). Each pass runs with the weights in force when it was issued
+ * (blocks in flight through aidax_pool_submit and passes on a caller's stream too). aidax_pool_reset_stream keeps A, B and the mix, and a
+ * running ramp goes on. A pass with blended streams costs one more k_ir_conv launch (the B sides, over the blended streams only) and
+ * k_ir_mix; a running ramp uploads no plan, and a pass without a blended stream issues exactly the launches it issued before. In a pool
+ * that never prepared an IR the stage does not run and both sides are the dry block: the output is the dry block, the ramps run on.
+ * aidax_pool_assign_ir_b     AUDIO thread, between passes: the stream's (AIDAX_ALL_STREAMS: every stream's) B is `slot`: AIDAX_IR_POOL,
+ *                            AIDAX_IR_NONE or 0 .. 63. Host records only: no allocation, no free, no wait.
+ * aidax_pool_set_ir_mix      AUDIO thread, between passes: a ramp to `mix` over `ramp_frames` frames (AIDAX_ALL_STREAMS: every stream from
+ *                            its own m_now). Host records only. AIDAX_ERR_ARG for a null pool, a stream or slot out of range, a mix that is
+ *                            not finite or outside [0, 1], ramp_frames > 2^24 (both calls; a refused call changes nothing).
+ * aidax_pool_stream_ir_mix   the state behind the last pass issued (any pointer may be NULL): B, m_now, the ramp's target, and the frames
+ *                            still to be issued until m_now is the target (0: the ramp has ended; a jump has 1 until a frame is issued). */
+AIDAX_API int aidax_pool_assign_ir_b(aidax_pool* p, int32_t stream, int32_t slot);
+AIDAX_API int aidax_pool_set_ir_mix(aidax_pool* p, int32_t stream, float mix, uint32_t ramp_frames);
+AIDAX_API int aidax_pool_stream_ir_mix(const aidax_pool* p, uint32_t stream, int32_t* slot_b, float* mix_now, float* mix_target, uint32_t* frames_left);
+
 /* IR rate conversion (host only: no device, no pool, any thread). The IRs the reference ships, like most commercial cabinet IRs, are
  * 48 kHz files; a pool at another host rate plays them after
  * aidax_ir_resample   `in` (n_in taps at rate_in) converted to rate_out by a Kaiser-windowed sinc. Both rates are positive integers (as
@@ -511,14 +548,14 @@ AIDAX_API int  aidax_pool_metering(const aidax_pool* p);
 AIDAX_API int  aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_stream_meter* out, int clear);
 
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
  * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side); aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir or a commit_ir) and changed model-bank records (after an assign_model), go
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) and changed model-bank records (after an assign_model), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */

@@ -20,15 +20,23 @@
   --rate R      a pool at host rate R playing a 48 kHz cabinet of 8192 frames brought to R by aidax_ir_resample ("rate": the host time
                 of the conversion, the taps it gives, cfg2 and the one-stream round trip with them; the capacity is raised as needed)
 
+  --blend       the IR blend (aidax_pool_assign_ir_b / aidax_pool_set_ir_mix): cfg2 with an 8192-tap IR in slot 0 and another in slot 1,
+                every stream on slot 0, and no stream, 64 of 1024 streams and all streams blended at a mix of 0.5 ("cfg2_blend": us per
+                block of each, --rounds times in turn, and the medians). With --parent-lib PATH (the library of the commit before the
+                blend) the unblended pool IR of that build and of this one, alternating, each in a child process of its own
+                ("cfg2_vs_parent")
+
 The IR is seeded exponentially decaying noise of 8192 taps (the length of the reference's cabinet IRs) unless --taps says otherwise. Under rocprofv3 --kernel-trace
 --stats the k_ir_conv / k_ir_reduce / k_ir_append rows are the stage's kernels alone.
 
     python3 tools/ir_bench.py [--steps 400] [--warmup 50] [--calls 400] [--irs 1,4,16,64] [--fade 256] [--taps 65536] [--rate 96000]
+                               [--blend [--rounds 5] [--parent-lib PATH]]
 """
 import argparse
 import importlib
 import json
 import os
+import subprocess
 import sys
 import tempfile
 import time
@@ -68,7 +76,7 @@ def load_bank(pool, S, K, pattern):
         pool.assign_ir(s, s * K // S if pattern == "runs" else s % K)
 
 
-def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None, fade=0):
+def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None, fade=0, blend=None):
     S, n = 1024, 256
     pool = new_pool(ax, S, n)
     pool.set_model(ax.Model(path))
@@ -78,6 +86,13 @@ def cfg2_us(ax, W, torch, path, with_ir, steps, warmup, bank=None, fade=0):
         pool.set_ir(cabinet_ir())
     if bank:
         load_bank(pool, S, *bank)
+    if blend is not None:
+        # two IRs in the bank, every stream through slot 0 and every (S // blend)-th one half way over to slot 1
+        load_bank(pool, S, 1, "runs")
+        pool.set_ir_slot(1, cabinet_ir(seed=8193))
+        pool.assign_ir_b(ax.ALL_STREAMS, 1)
+        for k in range(blend):
+            pool.set_ir_mix(k * (S // blend), 0.5, 0)
     x = torch.from_numpy(W.signal(S, n, seed=5)).cuda()
     y = torch.empty_like(x)
     s = torch.cuda.Stream()
@@ -177,6 +192,32 @@ def one_stream(ax, W, path, with_ir, frames, calls, bank=False):
     return {"p50_us": round(float(np.percentile(t, 50)) * 1e6, 2), "p99_us": round(float(np.percentile(t, 99)) * 1e6, 2)}
 
 
+def blend_report(ax, W, torch, path, a):
+    rounds = {"none": [], "64_of_1024": [], "all_1024": []}
+    dry = cfg2_us(ax, W, torch, path, False, a.steps, a.warmup)
+    for _ in range(a.rounds):
+        for name, k in (("none", 0), ("64_of_1024", 64), ("all_1024", 1024)):
+            rounds[name].append(round(cfg2_us(ax, W, torch, path, False, a.steps, a.warmup, blend=k), 2))
+    med = {k: round(float(np.median(v)), 2) for k, v in rounds.items()}
+    stage = med["none"] - dry
+    return {"us_per_block_no_ir": round(dry, 2), "rounds": rounds, "median_us_per_block": med, "ir_stage_us": round(stage, 2),
+            "extra_us": {k: round(v - med["none"], 2) for k, v in med.items() if k != "none"},
+            "all_blended_over_ir_stage": round((med["all_1024"] - dry) / stage, 3)}
+
+
+def vs_parent(a):
+    """cfg2 with the pool IR, no stream blended, on the parent's library and on this one in turn: every measurement a fresh process"""
+    libs = {"parent": os.path.abspath(a.parent_lib), "new": os.path.join(ROOT, "aidadsp-lv2_amd", "lib", "libaidax_hip.so")}
+    rounds = {k: [] for k in libs}
+    for _ in range(a.rounds):
+        for name, lib in libs.items():
+            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--steps", str(a.steps), "--warmup", str(a.warmup), "--cfg2-only"],
+                               env=dict(os.environ, AIDAX_LIB=lib), capture_output=True, text=True, timeout=300, check=True)
+            rounds[name].append(json.loads(r.stdout.strip().splitlines()[-1])["us_per_block_ir"])
+    med = {k: round(float(np.median(v)), 2) for k, v in rounds.items()}
+    return {"rounds": rounds, "median_us_per_block_ir": med, "new_minus_parent_us": round(med["new"] - med["parent"], 2)}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--steps", type=int, default=400)
@@ -186,7 +227,13 @@ def main():
     ap.add_argument("--fade", type=int, default=0, help="fade length in frames: the IR fade's steady state and the cost of one fade pass")
     ap.add_argument("--taps", type=int, default=8192, help="IR length; above 8192 the pools' IR capacity is raised to it")
     ap.add_argument("--rate", type=int, default=0, help="host rate of the pools: a 48 kHz cabinet of 8192 frames converted to it")
+    ap.add_argument("--blend", action="store_true", help="the IR blend: cfg2 with no, 64 and all 1024 streams blended, in turn")
+    ap.add_argument("--rounds", type=int, default=5, help="--blend: how often each variant is measured")
+    ap.add_argument("--parent-lib", default="", help="--blend: the library of the commit before the blend, for the unblended stage against it")
+    ap.add_argument("--cfg2-only", action="store_true", help="(what --parent-lib runs in a child: cfg2 with the pool IR, one JSON line)")
     a = ap.parse_args()
+    if a.blend and a.parent_lib:
+        against = vs_parent(a)                      # (ahead of this process's own use of the device)
     import torch
     ax = importlib.import_module("aidadsp-lv2_amd")
     global TAPS, IR, SR
@@ -206,6 +253,15 @@ def main():
     cfg2 = W.write_model(W.make_model("lstm", 32, 1, seed=32), os.path.join(d, "lstm32.json"))
     lv2 = os.path.join(ROOT, "tests", "golden", "models", "tw40_california_clean_deerinkstudios.json")
     out = {"lib": os.path.relpath(ax.lib_path(), ROOT), "ir_taps": int(cabinet_ir().size), "steps": a.steps}
+    if a.cfg2_only:
+        print(json.dumps({"lib": out["lib"], "us_per_block_ir": round(cfg2_us(ax, W, torch, cfg2, True, a.steps, a.warmup), 2)}))
+        return
+    if a.blend:
+        out["cfg2_blend"] = blend_report(ax, W, torch, cfg2, a)
+        if a.parent_lib:
+            out["cfg2_vs_parent"] = against
+        print(json.dumps(out))
+        return
     if rate:
         out["rate"] = rate
     floor_us = FLOOR_US * cabinet_ir().size / 8192
