@@ -61,6 +61,26 @@ METER_DTYPE = np.dtype([("frames", "<u8"), ("passes", "<u8"), ("in_nonfinite", "
                         ("in_energy", "<f8"), ("out_energy", "<f8"), ("in_peak", "<f4"), ("out_peak", "<f4")])
 
 
+class GateParams(C.Structure):
+    """aidax_gate_params: a noise gate as a user sets it (levels in dB, times in ms)"""
+    _fields_ = [("open_db", C.c_float), ("close_db", C.c_float), ("floor_db", C.c_float), ("attack_ms", C.c_float),
+                ("hold_ms", C.c_float), ("release_ms", C.c_float)]
+
+
+class GateRec(C.Structure):
+    """aidax_gate_rec: the record k_gate reads (32 bytes), what aidax_gate_design makes of GateParams at a sample rate"""
+    _fields_ = [("t_open", C.c_float), ("t_close", C.c_float), ("floor", C.c_float), ("span", C.c_float),
+                ("hold", C.c_uint32), ("up", C.c_uint32), ("down", C.c_uint32), ("on", C.c_uint32)]
+
+
+class GateState(C.Structure):
+    """aidax_gate_state: a stream's gate state (hold frames left, attenuation position 0 .. 2^24)"""
+    _fields_ = [("hold_left", C.c_uint32), ("atten", C.c_uint32)]
+
+
+GATE_STATE_DTYPE = np.dtype([("hold_left", "<u4"), ("atten", "<u4")])
+
+
 def lib_path() -> str:
     # AIDAX_LIB: another build of the library (A/B measurements of two builds in one gpurun call)
     return os.environ.get("AIDAX_LIB") or os.path.join(_HERE, "lib", "libaidax_hip.so")
@@ -219,6 +239,11 @@ def lib() -> C.CDLL:
         L.aidax_pool_set_metering.argtypes = [vp, C.c_int]
         L.aidax_pool_metering.argtypes = [vp]
         L.aidax_pool_read_meters.argtypes = [vp, u32, u32, C.POINTER(StreamMeter), C.c_int]
+    if hasattr(L, "aidax_pool_set_gate"):          # (... or from before the noise gate)
+        L.aidax_gate_design.argtypes = [C.POINTER(GateParams), C.c_double, C.POINTER(GateRec)]
+        L.aidax_pool_set_gate.argtypes = [vp, i32, C.POINTER(GateParams)]
+        L.aidax_pool_stream_gate.argtypes = [vp, u32, C.POINTER(GateParams), C.POINTER(C.c_int)]
+        L.aidax_pool_read_gate.argtypes = [vp, u32, u32, C.POINTER(GateState)]
     _lib = L
     return L
 
@@ -254,6 +279,13 @@ def biquad_design(kind: int, fc: float, q: float, gain_db: float) -> np.ndarray:
     out = (C.c_double * 5)()
     _check(lib().aidax_biquad_design(kind, fc, q, gain_db, out))
     return np.array(list(out), np.float64)
+
+
+def gate_design(params: GateParams, samplerate: float) -> GateRec:
+    """aidax_gate_design: the record of `params` at `samplerate` (pure, host only)"""
+    out = GateRec()
+    _check(lib().aidax_gate_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
+    return out
 
 
 def load_ir_wav(path: str):
@@ -556,6 +588,26 @@ class Pool:
             count = self.n_streams - first
         out = np.zeros(max(count, 0), METER_DTYPE)
         _check(lib().aidax_pool_read_meters(self.h, first, count, out.ctypes.data_as(C.POINTER(StreamMeter)), 1 if clear else 0))
+        return out
+
+    def set_gate(self, params: Optional[GateParams], stream: int = ALL_STREAMS):
+        """aidax_pool_set_gate: the stream's (default: every stream's) noise gate ahead of the model, None: off (the first enabling call
+        allocates: a set-up side call)"""
+        _check(lib().aidax_pool_set_gate(self.h, stream, C.byref(params) if params is not None else None))
+
+    def stream_gate(self, stream: int):
+        """aidax_pool_stream_gate: (the stream's GateParams as last set, whether its gate is on)"""
+        out, on = GateParams(), C.c_int(0)
+        _check(lib().aidax_pool_stream_gate(self.h, stream, C.byref(out), C.byref(on)))
+        return out, bool(on.value)
+
+    def read_gate(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """aidax_pool_read_gate: the gate states of `count` streams from `first` (default: all from `first` on) as a structured array with
+        aidax_gate_state's field names, behind every pass issued so far"""
+        if count is None:
+            count = self.n_streams - first
+        out = np.zeros(max(count, 0), GATE_STATE_DTYPE)
+        _check(lib().aidax_pool_read_gate(self.h, first, count, out.ctypes.data_as(C.POINTER(GateState))))
         return out
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):

@@ -7,6 +7,7 @@
 // kernels are bit-exact against it. Each filter family is written as
 // "denominator polynomial, numerator polynomial, normalise", keeping the
 // reference's association order inside every sum and product.
+#include <algorithm>
 #include <cmath>
 
 #include "aidax_internal.h"
@@ -230,6 +231,44 @@ AIDAX_API int aidax_pick_hub(const int* hub_device, const uint32_t* hub_free_sea
     for (int i = 0; i < n_hubs; ++i)
         if (hub_free_seats[i] > 0) { *index_out = i; *device_out = hub_device[i]; return AIDAX_OK; }
     return aidax_pick_device(spec, device_count, load, device_out);
+}
+
+// The noise gate's record (include/aidax.h, "Noise gate"): everything in fp64, the thresholds rounded once to fp32, the ramps as integer
+// steps of P = 2^24 per frame, rounded up so that a ramp of n frames ends within n frames.
+AIDAX_API int aidax_gate_design(const aidax_gate_params* params, double samplerate, aidax_gate_rec* out)
+{
+    using aidax::fail;
+    if (!params || !out) return fail(AIDAX_ERR_ARG, "gate_design: null argument");
+    const aidax_gate_params& g = *params;
+    if (!std::isfinite(g.open_db) || !std::isfinite(g.close_db) || !std::isfinite(g.floor_db) || !std::isfinite(g.attack_ms) ||
+        !std::isfinite(g.hold_ms) || !std::isfinite(g.release_ms))
+        return fail(AIDAX_ERR_ARG, "gate_design: every parameter must be finite");
+    if (!(g.open_db >= -120.f && g.open_db <= 0.f)) return fail(AIDAX_ERR_ARG, "gate_design: open_db must be in [-120, 0]");
+    if (!(g.close_db >= -120.f && g.close_db <= 0.f)) return fail(AIDAX_ERR_ARG, "gate_design: close_db must be in [-120, 0]");
+    if (g.close_db > g.open_db) return fail(AIDAX_ERR_ARG, "gate_design: close_db must not exceed open_db");
+    if (g.floor_db > 0.f) return fail(AIDAX_ERR_ARG, "gate_design: floor_db must not exceed 0");
+    for (const float ms : { g.attack_ms, g.hold_ms, g.release_ms })
+        if (!(ms >= 0.f && ms <= 10000.f)) return fail(AIDAX_ERR_ARG, "gate_design: attack_ms, hold_ms and release_ms must be in [0, 10000]");
+    if (!(samplerate > 0.0) || !std::isfinite(samplerate)) return fail(AIDAX_ERR_ARG, "gate_design: samplerate must be positive");
+
+    constexpr long long P = 1ll << 24;
+    auto frames = [&](float ms) {
+        const double f = static_cast<double>(ms) * samplerate / 1000.0;
+        return f >= static_cast<double>(P) ? P : std::min(P, std::max(1ll, std::llround(f)));
+    };
+    auto level = [](float db) { return static_cast<float>(std::pow(10.0, static_cast<double>(db) / 20.0)); };
+    const long long attack = frames(g.attack_ms), release = frames(g.release_ms);
+    aidax_gate_rec r;
+    r.t_open = level(g.open_db);
+    r.t_close = level(g.close_db);
+    r.floor = g.floor_db <= -120.f ? 0.f : level(g.floor_db);
+    r.span = static_cast<float>(1.0 - static_cast<double>(r.floor));
+    r.hold = static_cast<uint32_t>(frames(g.hold_ms));
+    r.up = static_cast<uint32_t>((P + attack - 1) / attack);
+    r.down = static_cast<uint32_t>((P + release - 1) / release);
+    r.on = 1u;
+    *out = r;
+    return AIDAX_OK;
 }
 
 }  // extern "C"

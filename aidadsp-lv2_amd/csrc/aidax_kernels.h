@@ -192,6 +192,22 @@ static_assert(sizeof(MeterRec) == 64, "a stream's meter record is 64 bytes");
 enum { kMeterIn = 0, kMeterOut = 1 };
 hipError_t launch_meter(const float* buf, MeterRec* rec, uint32_t n_active, uint32_t n_frames, int side, hipStream_t q);
 
+// The noise gate ahead of the model (aidax_gate.hip, k_gate): one launch turns the block a pass was handed, [n_active][n_frames], into
+// the gated block `out` of the same shape (never the same memory), a wave per stream, by the per-frame rule of include/aidax.h ("Noise
+// gate"). GateRec is aidax_gate_rec and GateState aidax_gate_state, field for field. A stream whose record is off, or whose control
+// record lacks CTL_ENABLED, has its row copied bit for bit and its state left alone.
+constexpr uint32_t kGateUnit = 1u << 24;       // P: the attenuation position of a fully closed gate
+struct GateRec {
+    float t_open, t_close, floor, span;
+    uint32_t hold, up, down, on;
+};
+struct GateState {
+    uint32_t hold_left, atten;                 // c, q
+};
+static_assert(sizeof(GateRec) == 32 && sizeof(GateState) == 8, "a stream's gate record is 32 bytes, its state 8");
+hipError_t launch_gate(const float* in, float* out, const GateRec* rec, GateState* state, const StreamCtl* ctl, uint32_t n_active, uint32_t n_frames,
+                       hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

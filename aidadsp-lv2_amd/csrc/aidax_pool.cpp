@@ -371,6 +371,27 @@ struct aidax_pool {
         MeterRec* h_rec = nullptr;   // pinned staging of aidax_pool_read_meters, [n_streams]
         bool on = false;
     } meter;
+    // The noise gate ahead of the model (aidax_pool_set_gate; k_gate, aidax_gate.hip): nothing until the first call that enables one,
+    // which allocates all of it; from then on the records are host records of the audio side, uploaded ahead of the pass that follows
+    struct GateStage {
+        GateRec* d_rec = nullptr;        // [n_streams], nullptr: never enabled
+        GateState* d_state = nullptr;    // [n_streams]
+        GateState* h_state = nullptr;    // pinned staging of aidax_pool_read_gate, [n_streams]
+        float* d_side = nullptr;         // the gated block a pass's model launch reads: [n_streams][max_frames]
+        std::vector<GateRec> h_rec;
+        std::vector<aidax_gate_params> params;
+        DirtyRange dirty;
+        SnapshotRing ring;
+        uint32_t n_on = 0;               // streams whose gate is on: a pass launches k_gate while this is not 0
+        void release()
+        {
+            if (d_rec) (void)hipFree(d_rec);
+            if (d_state) (void)hipFree(d_state);
+            if (d_side) (void)hipFree(d_side);
+            if (h_state) (void)hipHostFree(h_state);
+            ring.release();
+        }
+    } gate;
 
     // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
     // block k and the download of the blocks in front of it run under the pass of block k (allocated by the first submit).
@@ -685,6 +706,7 @@ struct aidax_pool {
     {
         ir.release();
         bank.release();
+        gate.release();
         if (meter.d_rec) (void)hipFree(meter.d_rec);
         if (meter.h_rec) (void)hipHostFree(meter.h_rec);
         if (d_ctl) (void)hipFree(d_ctl);
@@ -968,6 +990,14 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on || meter_on) { p->pass_done = nullptr; p->pass_word = nullptr; }
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) HIP_TRY(launch_meter(d_in, p->meter.d_rec, n_active, n_frames, kMeterIn, s));      // (ahead of the pass: it may work in place)
+        if (n_frames != 0 && p->gate.n_on != 0) {
+            // the gate ahead of the model: the records this pass plays under, then the gated block into the side block, which the model's
+            // launch reads in place of d_in (the pass's end markers stay with that launch: the gate is ahead of it)
+            aidax_pool::GateStage& g = p->gate;
+            g.ring.upload_dirty(g.d_rec, g.h_rec.data(), g.dirty, s);
+            HIP_TRY(launch_gate(d_in, g.d_side, g.d_rec, g.d_state, p->d_ctl, n_active, n_frames, s));
+            a.in = g.d_side;
+        }
         HIP_TRY(p->launch(p->cur, a, s));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
@@ -1419,6 +1449,107 @@ AIDAX_API int aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t cou
     });
 }
 
+// The noise gate. The first call that enables one is the set-up side's: records, states (zeroed), the side block, the snapshots and the
+// pinned staging of the read. Every later call changes host records of the audio side; a stream that goes from off to on has its state
+// zeroed on the pool's own stream, behind every pass issued so far (the next pass, on whatever stream, is ordered behind that).
+static_assert(sizeof(aidax_gate_rec) == sizeof(GateRec) && offsetof(aidax_gate_rec, hold) == offsetof(GateRec, hold) && offsetof(aidax_gate_rec, on) == offsetof(GateRec, on) &&
+                  sizeof(aidax_gate_state) == sizeof(GateState) && offsetof(aidax_gate_state, atten) == offsetof(GateState, atten),
+              "k_gate's record and state are aidax_gate_rec and aidax_gate_state");
+AIDAX_API int aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_gate_params* params)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    aidax_gate_rec designed{};
+    if (params)
+        if (const int rc = aidax_gate_design(params, aidax_pool_samplerate(p), &designed)) return rc;
+    aidax_pool::GateStage& g = p->gate;
+    if (!g.d_rec) {
+        if (!params) return AIDAX_OK;                       // (off before any on: nothing to change)
+        const int rc = guarded([&]() -> int {
+            HIP_TRY(hipSetDevice(p->device));
+            const size_t n = p->n_streams;
+            aidax_pool::GateStage fresh;
+            auto build = [&]() -> hipError_t {
+                hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.d_rec), sizeof(GateRec) * n);
+                if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_state), sizeof(GateState) * n);
+                if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_side), sizeof(float) * n * p->max_frames);
+                if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&fresh.h_state), sizeof(GateState) * n, hipHostMallocDefault);
+                if (e == hipSuccess) e = hipMemsetAsync(fresh.d_rec, 0, sizeof(GateRec) * n, p->q);
+                if (e == hipSuccess) e = hipMemsetAsync(fresh.d_state, 0, sizeof(GateState) * n, p->q);
+                if (e == hipSuccess) e = hipStreamSynchronize(p->q);      // (a pass on a caller's stream must find them zeroed)
+                return e;
+            };
+            try {
+                HIP_TRY(build());
+                fresh.ring.alloc(sizeof(GateRec) * n);
+                fresh.h_rec.assign(n, GateRec{});
+                fresh.params.assign(n, aidax_gate_params{});
+            } catch (...) {
+                fresh.release();
+                throw;
+            }
+            g = std::move(fresh);
+            return AIDAX_OK;
+        });
+        if (rc != AIDAX_OK) return rc;
+    }
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    // the streams that go from off to on restart at unity gain: their states are zeroed behind the passes issued so far, run by run
+    bool restart = false;
+    for (uint32_t s = lo; s < hi && !restart; ++s) restart = params && !g.h_rec[s].on;
+    if (restart) {
+        const int rc = p->on_own_stream([&]() -> int {
+            for (uint32_t s = lo; s < hi;) {
+                if (g.h_rec[s].on) { ++s; continue; }
+                uint32_t e = s + 1;
+                while (e < hi && !g.h_rec[e].on) ++e;
+                HIP_TRY(hipMemsetAsync(g.d_state + s, 0, sizeof(GateState) * (e - s), p->q));
+                s = e;
+            }
+            return AIDAX_OK;
+        });
+        if (rc != AIDAX_OK) return rc;
+    }
+    for (uint32_t s = lo; s < hi; ++s) {
+        GateRec& r = g.h_rec[s];
+        g.n_on += (params ? 1u : 0u) - (r.on ? 1u : 0u);
+        if (params) {
+            std::memcpy(&r, &designed, sizeof r);
+            g.params[s] = *params;
+        } else {
+            r.on = 0u;
+        }
+    }
+    g.dirty.mark(lo, hi - 1);
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_stream_gate(const aidax_pool* p, uint32_t stream, aidax_gate_params* out, int* on)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const aidax_pool::GateStage& g = p->gate;
+    if (out) *out = g.d_rec ? g.params[stream] : aidax_gate_params{};
+    if (on) *on = g.d_rec && g.h_rec[stream].on ? 1 : 0;
+    return AIDAX_OK;
+}
+
+// Audio side, waits: the copy enters the pool's own stream behind every pass issued so far, whatever stream carried it
+AIDAX_API int aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count, aidax_gate_state* out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
+    if (!p->gate.d_rec) return fail(AIDAX_ERR_STATE, "no gate was ever enabled (aidax_pool_set_gate)");
+    return p->on_own_stream([&]() -> int {
+        const size_t bytes = sizeof(GateState) * count;
+        HIP_TRY(hipMemcpyAsync(p->gate.h_state + first, p->gate.d_state + first, bytes, hipMemcpyDeviceToHost, p->q));
+        HIP_TRY(hipStreamSynchronize(p->q));
+        std::memcpy(out, p->gate.h_state + first, bytes);
+        return AIDAX_OK;
+    });
+}
+
 AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
 {
     if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
@@ -1459,6 +1590,7 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
         const ModelSlot& m = p->cur;
         HIP_TRY(launch_init_streams(p->d_st + stream, 1, p->q));      // instantiate(), :283-321
         p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
+        if (p->gate.d_state) HIP_TRY(hipMemsetAsync(p->gate.d_state + stream, 0, sizeof(GateState), p->q));      // ... and its gate starts at unity gain, hold expired
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st + stream, p_targets[0], p_targets[1], p->q));
         const ModelBank* b = p->bank.adopt();                         // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
         if (m.has_model) p->fresh_stream_model(m, stream, start_mode, b && b->assign[stream] >= 0 ? ModelBank::rec_of(b->slot[b->assign[stream]]) : m.rec(), p->q);

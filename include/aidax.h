@@ -501,7 +501,8 @@ AIDAX_API int      aidax_rate_reset_stream(aidax_rate* r, uint32_t stream);
  * 64-byte record on the device, with two launches of k_meter on the pass's stream: one over the block the pass was handed, ahead of the
  * model's launch, and one over the block it returns, behind the last stage.
  * Input and output:
- *  - "Input" is the stream's row of the block the pass was handed, before PREGAIN and everything else.
+ *  - "Input" is the stream's row of the block the pass was handed, before PREGAIN and everything else, the noise gate included
+ *    ("Noise gate" below): a gated stream's in_peak and in_energy describe the ungated block.
  *  - "Output" is its row of the block the pass returns: behind the master ramp and, where the pool has an IR history, behind the IR stage
  *    and its fade.
  *  - A stream with `enabled` = 0 is metered like any other; its output is its input.
@@ -547,15 +548,72 @@ AIDAX_API int  aidax_pool_set_metering(aidax_pool* p, int on);
 AIDAX_API int  aidax_pool_metering(const aidax_pool* p);
 AIDAX_API int  aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_stream_meter* out, int clear);
 
+/* Noise gate: a per-stream gate AHEAD of the amp model, computed where the blocks are (k_gate, aidax_gate.hip). Opt-in: a pool that never
+ * enables one allocates and launches exactly what it did before these calls existed, bit for bit, and so does every pass issued while no
+ * stream's gate is on. While at least one stream's gate is on, every pass of n_frames > 0 issues one launch of k_gate on the pass's stream,
+ * ahead of the model's launch: it reads the block the pass was handed and writes the gated block into a side block of the pool's
+ * (n_streams x max_frames floats), which the model's launch takes as its input. The caller's input block is never written, and a pass
+ * may work in place as before.
+ * The rule, per stream and frame by frame, with P = 2^24 and the stream's record (aidax_gate_rec) and state (aidax_gate_state: c =
+ * hold_left, q = atten; all zero is "unity gain, hold expired"):
+ *     a = |x|                                          (a NaN compares false everywhere: a quiet frame)
+ *     if      a >= t_open:             c = hold
+ *     else if a >= t_close and c > 0:  c = hold        (hysteresis: the close level only keeps an open gate open)
+ *     else if c > 0:                   c = c - 1
+ *     if c > 0: q = max(q - up, 0)   else   q = min(q + down, P)
+ *     if q == 0: y = x                                 (the input's bits, NaN payloads included)
+ *     else:      w = (float)(P - q) * 2^-24            (exact)
+ *                g = floor + span * w                  (two fp32 operations, each rounded, no fma)
+ *                y = x * g
+ * Before use c is clipped to the record's `hold` (a parameter change while the stream plays). Everything stateful is an integer, so the
+ * kernel's parallel evaluation matches this sequential statement bit for bit; there is no look-ahead and no latency, and the state
+ * carries across passes: the output does not depend on how the host cuts the stream into blocks.
+ * Which rows are gated:
+ *  - A pass plays under the gate records in force when it was issued (they reach the device from a ring of snapshots, like the control
+ *    records): the blocking path, aidax_pool_submit* / collect (the blocks in flight too), aidax_pool_process_device on the pool's or a
+ *    caller's stream, passes under aidax_rate_* (the gate then sees the pool-rate block between the adapter's two stages).
+ *  - A stream whose gate is off, and a stream with `enabled` = 0, get their row as it was handed in, bit for bit, and their state does not
+ *    move: a disabled stream's output is its input, and that is the UNGATED input.
+ *  - The stream meters' "input" stays the block the pass was handed, before the gate.
+ *  - Turning a stream's gate from off to on zeroes its state, and so does aidax_pool_reset_stream, stream-ordered behind the passes issued
+ *    so far: a gate switched on in mid-signal starts at unity gain and closes along the release ramp, it never steps. A parameter change
+ *    while on keeps the state.
+ * aidax_gate_design        pure, host only, any thread: the record of `params` at `samplerate`, in fp64: t_open / t_close =
+ *                          (float)pow(10, dB / 20); floor likewise, and exactly 0 for floor_db <= -120; span = (float)(1.0 - (double)floor);
+ *                          frames = min(2^24, max(1, llround(ms * samplerate / 1000))) for hold, attack and release; up = ceil(P /
+ *                          attack frames), down = ceil(P / release frames); on = 1. AIDAX_ERR_ARG (the reason in aidax_last_error()) for a
+ *                          null pointer, a non-finite field, open_db or close_db outside [-120, 0], close_db > open_db, floor_db > 0, a
+ *                          time outside [0, 10000] ms, a samplerate that is not positive.
+ * aidax_pool_set_gate      `stream` (AIDAX_ALL_STREAMS: every stream) is gated with `params`, designed at aidax_pool_samplerate (under a
+ *                          rate adapter: the model's rate), from the next pass on; params == NULL switches the gate off. The FIRST call
+ *                          with params != NULL is a SET-UP side call, like the first aidax_pool_set_metering(.., 1): it allocates the
+ *                          records, the states, the side block and the snapshots, and may wait. Every later call is an AUDIO side host
+ *                          record, between passes (plus, for streams that go from off to on, an asynchronous clear of their states on the
+ *                          pool's own stream): no allocation, no free, no wait. A refused call changes nothing. AIDAX_ERR_ARG for a null
+ *                          pool, a stream out of range and whatever aidax_gate_design refuses.
+ * aidax_pool_stream_gate   the stream's host record: its parameters as last set (zeros if never) and whether its gate is on.
+ * aidax_pool_read_gate     AUDIO side, and it waits, like aidax_pool_read_meters: the states of `count` streams from `first`, behind every
+ *                          pass issued so far. AIDAX_ERR_ARG for a null argument, count == 0 or first + count > n_streams,
+ *                          AIDAX_ERR_STATE when no gate was ever enabled.
+ * Not covered: hub seats (aidax_hub never enables a gate on its pool) and so the LV2 shell (the reference's TTL has no ports for it), a
+ * side-chain or look-ahead gate, a gate behind the model. */
+typedef struct { float open_db, close_db, floor_db, attack_ms, hold_ms, release_ms; } aidax_gate_params;
+typedef struct { float t_open, t_close, floor, span; uint32_t hold, up, down, on; } aidax_gate_rec;   /* 32 bytes */
+typedef struct { uint32_t hold_left, atten; } aidax_gate_state;                                        /* c, q */
+AIDAX_API int  aidax_gate_design(const aidax_gate_params* params, double samplerate, aidax_gate_rec* out);
+AIDAX_API int  aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_gate_params* params);
+AIDAX_API int  aidax_pool_stream_gate(const aidax_pool* p, uint32_t stream, aidax_gate_params* out, int* on);
+AIDAX_API int  aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count, aidax_gate_state* out);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side); aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side); aidax_gate_design is pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) and changed model-bank records (after an assign_model), go
+ * aidax_pool_process / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate wait for the GPU (for the stream that carries the pass, never for the
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) and changed gate records (after a set_gate), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
