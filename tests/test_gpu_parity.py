@@ -857,6 +857,82 @@ def test_conv_stacks_on_the_split_kernel_corners(name, l0, rest, tmp_path, monke
     errlog.bound(np.abs(outs["k_conv_ms"] - outs["k_conv_mfma"]).max() / scale, 2e-6, "gpu_parity:conv_ms_vs_mfma")
 
 
+_LONG_PERIODS = {"odd dilations": 20574, "history = the plane's": 8064, "four taps, 64 apart": 4032}
+_RING_RUNS = {}
+
+
+def _ring_period_case(name, tmp_path):
+    """One of the stacks whose ring period is long, on ragged blocks until the stream's time (kept modulo the least common multiple of the
+    layers' history lengths: conv_ms_period, ConvDesc::ms_pos_mod) has wrapped twice, both times INSIDE a block: (path, spec, sizes, x,
+    controls, the oracle's run)."""
+    from math import gcd
+    _, l0, rest = next(s for s in _MS_STACKS if s[0] == name)
+    period = 1
+    for k, dil, _ in rest:
+        h = (k - 1) * dil
+        period = period // gcd(period, h) * h
+    assert period == _LONG_PERIODS[name] and period < (1 << 24)
+    sizes = []
+    while sum(sizes) <= 2 * period + 300:
+        sizes += _MS_SIZES
+    starts = set(np.cumsum([0] + sizes).tolist())
+    assert sum(sizes) > 2 * period and period not in starts and 2 * period not in starts
+    cg, co = _ctl_pair(pregain_db=1.0, treble_boost_db=2.0)
+    if name not in _RING_RUNS:                                  # (the input and the oracle's run: computed once, shared by the two tests, read-only)
+        path, spec = _ms_stack_model(name, l0, rest, tmp_path)
+        x = modelgen.signal(6, sum(sizes), seed=43)
+        want = O.run_streams(spec, co, x, 256)
+        for a in (x, want):
+            a.setflags(write=False)
+        _RING_RUNS[name] = dict(json=open(path).read(), x=x, want=want)
+    return _RING_RUNS[name], sizes, cg
+
+
+def _ring_period_run(r, sizes, cg, kname):
+    pool = ax.Pool(6, 256)
+    pool.set_model(ax.Model(text=r["json"]))
+    assert pool.kernel_name == kname, (pool.kernel_name, kname)
+    pool.set_controls(cg)
+    got = np.empty_like(r["x"])
+    pos = 0
+    for n in sizes:
+        got[:, pos:pos + n] = pool.process(np.ascontiguousarray(r["x"][:, pos:pos + n]))
+        pos += n
+    pool.close()
+    assert np.isfinite(got).all()
+    return got
+
+
+@pytest.mark.parametrize("name", sorted(_LONG_PERIODS))
+def test_conv_stacks_run_past_their_ring_period(name, tmp_path):
+    """The runs above are 2241 frames long and the time word of these three stacks wraps after 20574, 8064 and 4032: here it wraps twice, in
+    the middle of a block, with every ring at whatever phase the ragged blocks left it — as the pool runs them (no switch: the ship leg too)."""
+    r, sizes, cg = _ring_period_case(name, tmp_path)
+    got = _ring_period_run(r, sizes, cg, "k_conv_ms")
+    scale = max(1.0, float(np.abs(r["want"]).max()))
+    errlog.bound(np.abs(got - r["want"]).max() / scale, 3e-6, "gpu_parity:conv_ring_period")
+    # ... and no worse behind the second wrap than before the first
+    period = _LONG_PERIODS[name]
+    errlog.bound(np.abs(got - r["want"])[:, 2 * period:].max() / scale, 3e-6, "gpu_parity:conv_ring_period_after_two_wraps")
+
+
+@pytest.mark.parametrize("name", sorted(_LONG_PERIODS))
+def test_conv_stacks_past_their_ring_period_on_the_other_forms(name, tmp_path, monkeypatch):
+    """... bit for bit the split-launch form's run (the same rings, the same time word), and within the layouts' usual distance of
+    k_conv_mfma, whose histories have no period."""
+    r, sizes, cg = _ring_period_case(name, tmp_path)
+    base = _ring_period_run(r, sizes, cg, "k_conv_ms")
+    scale = max(1.0, float(np.abs(r["want"]).max()))
+    monkeypatch.setenv("AIDAX_CONV_FUSED", "0")
+    split = _ring_period_run(r, sizes, cg, "k_chain+k_conv_ms")
+    monkeypatch.delenv("AIDAX_CONV_FUSED")
+    monkeypatch.setenv("AIDAX_CONV_MS", "0")
+    mfma = _ring_period_run(r, sizes, cg, "k_conv_mfma")
+    assert np.array_equal(base, split), np.argwhere(base != split)[0]
+    errlog.bound(np.abs(mfma - r["want"]).max() / scale, 3e-6, "gpu_parity:conv_ring_period")
+    errlog.bound(np.abs(base - mfma).max() / scale, 2e-6, "gpu_parity:conv_ring_period_vs_mfma")
+
+
 @pytest.mark.parametrize("seed", range(8))
 def test_random_recurrent_stacks(seed, tmp_path, monkeypatch):
     """Stacked / wide recurrent models drawn at random — LSTM or GRU, 2..4 layers or one layer wider than the table,
