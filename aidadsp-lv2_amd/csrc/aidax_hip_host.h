@@ -1,6 +1,6 @@
 // aidax_hip_host.h — what every host source that issues HIP calls for a pool shares: the error plumbing (HIP_TRY throws HipFail, guarded
 // turns it into AIDAX_ERR_DEVICE) and, in the test build, the call counting behind aidax_test_hip_calls. Include it last: its macros
-// rename the calls of the source that follow it (aidax_snapshot_ring.h and aidax_model_bank.h include it and are counted: they go last too).
+// rename the calls of the source that follow it (aidax_snapshot_ring.h, aidax_model_bank.h, aidax_stream_stages.h and aidax_pool.h include it and are counted: they go last too).
 #pragma once
 
 #include <hip/hip_runtime_api.h>

@@ -48,8 +48,10 @@ float exp_smoother_coef(float samplerate, float t60);
 void  build_stream_ctl(const aidax_controls& c, double host_samplerate, bool has_model, bool loading,
                        float gain_coef, float p_den, StreamCtl* out);
 
-// aidax_pool_process_device restricted to the first n_active streams (aidax_pool.cpp; used by the hub)
-int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active);
+// aidax_pool_process_device restricted to the first n_active streams (aidax_pool.cpp; used by the hub and the rate adapter). `end`: the
+// pass's end markers (aidax_pool.h), which only the pool's own host-buffer paths hand in
+struct PassEnd;
+int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active, PassEnd* end = nullptr);
 
 // park / unpark a stream (behaves disabled while parked; its controls stay what they are) — aidax_pool.cpp, used by the hub
 int pool_park_stream(aidax_pool* p, uint32_t stream, bool parked);

@@ -1,0 +1,427 @@
+// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: forms, launches, create / destroy,
+// controls and stream state), aidax_pool_model.cpp (everything that builds or commits an aidax_staged) and aidax_pool_io.cpp (the
+// host-buffer entry points). Private to them. Issues HIP calls: include it last, like aidax_model_bank.h.
+#pragma once
+
+#include <algorithm>
+#include <atomic>
+#include <cstdlib>
+#include <memory>
+#include <mutex>
+
+#include "aidax_ir_stage.h"
+#include "aidax_model_bank.h"
+#include "aidax_stream_stages.h"
+
+namespace aidax {
+
+constexpr uint32_t kWarmupFrames = 2048;        // rt-neural-generic.cpp:1077
+constexpr uint32_t kMaxFrames = 8192;           // LDS block buffer bound (32 KiB)
+enum ManyForm { MANY_NONE = 0, MANY_QUAD = 1, MANY_MFMA = 2 };
+bool model_supported(const aidax_model& m);      // which models have a device path (aidax_pool.cpp)
+// the form heuristics (aidax_pool.cpp): which many-streams form serves a table model best, and where k_mfma_ls1 / k_lstm_gs pay
+bool lone_split_pays(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames);
+bool lstm_gs_pays(int cell, int hidden, uint32_t n, int cus);
+ManyForm many_streams_form(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames);
+
+// a flag written on the launch path and read by other threads (aidax_pool_kernel_name, lp_in_use from the worker): an atomic that
+// a struct assignment of its owner (a model swap is one) may copy
+struct RelaxedFlag {
+    std::atomic<bool> v{false};
+    RelaxedFlag() = default;
+    RelaxedFlag(const RelaxedFlag& o) : v(o.v.load(std::memory_order_relaxed)) {}
+    RelaxedFlag& operator=(const RelaxedFlag& o) { v.store(o.v.load(std::memory_order_relaxed), std::memory_order_relaxed); return *this; }
+    RelaxedFlag& operator=(bool b) { v.store(b, std::memory_order_relaxed); return *this; }
+    operator bool() const { return v.load(std::memory_order_relaxed); }
+};
+
+// k_mfma_lp needs every workgroup of its grid resident at once, which the pool can promise only for ONE grid on the
+// device: one pool per device holds the right to use the kernel (a pool's staged model shares its own pool's hold), the
+// others serve their stacked models with k_mfma. Process-wide; another process on the same GPU is beyond its reach
+// and ends in a reported give-up (aidax_mfmalp.hip).
+struct LpGate {
+    std::mutex mu;
+    // `off`: the owner's "I have stopped using the kernel" flag (a pool whose hand-over gave up serves its model with
+    // k_mfma from then on): a hold whose owner has raised it is void, the next pool that asks takes the device over
+    struct Hold { const void* owner = nullptr; int refs = 0; const std::atomic<bool>* off = nullptr; } dev[64];
+    bool acquire(int device, const void* owner, const std::atomic<bool>* off = nullptr)
+    {
+        if (device < 0 || device >= 64) return false;
+        std::lock_guard<std::mutex> g(mu);
+        Hold& h = dev[device];
+        if (h.refs != 0 && h.owner != owner) {
+            if (!(h.off && h.off->load(std::memory_order_relaxed))) return false;
+            h.refs = 0;                                    // (the old owner's later release() no longer matches and is ignored)
+        }
+        h.owner = owner;
+        h.off = off;
+        ++h.refs;
+        return true;
+    }
+    void release(int device, const void* owner)
+    {
+        if (device < 0 || device >= 64) return;
+        std::lock_guard<std::mutex> g(mu);
+        Hold& h = dev[device];
+        if (h.owner == owner && h.refs > 0 && --h.refs == 0) { h.owner = nullptr; h.off = nullptr; }
+    }
+};
+LpGate& lp_gate();                     // (the one instance: aidax_pool.cpp)
+
+// The device side of one loaded model: what the reference keeps in a DynamicModel (rt-neural-generic.h:115-129)
+// minus the per-stream members. A pool plays `cur`; aidax_pool_prepare_model builds the next one on the worker
+// thread and aidax_pool_commit_model swaps the two on the audio thread (plain struct assignment).
+struct ModelSlot {
+    bool has_model = false;
+    enum Kind { TABLE = 0, STACK = 1, CONV = 2, MFMA = 3, QUAD = 4 } kind = TABLE;
+    QuadDesc qdesc{};
+    StackDesc sdesc{};
+    MfmaDesc mdesc{};
+    ConvDesc cdesc{};
+    bool conv_mfma = false;          // conv stacks on the matrix cores (blocks of <= 256 frames), else k_conv
+    bool conv_ms = false;            // ... as bf16 term products (k_conv_ms: the stacks conv_ms_shape_ok admits; its own history layout)
+    bool conv_fused = false;         // ... with the DSP chain inside the same launch (AIDAX_CONV_FUSED=0: packed k_chain launches around it)
+    const KernelEntry* kernel = nullptr;
+    int cell = 0, input_size = 1, input_skip = 0, hidden = 0;
+    float in_gain = 1.f, out_gain = 1.f, model_sr = 48000.f;
+    uint32_t nn_stride = 0;
+    int pipe_capacity = 0;           // streams the 3-wave pipeline keeps resident at once (0 = never use it)
+    bool split_pays = false;         // the lean recurrent kernel keeps the occupancy of the one-wave kernel
+    float* d_wq4 = nullptr;          // k_lstm_q4's weight record (LSTM-32 snapshot models), next to the table kernels' d_wpack
+    float* d_wpack = nullptr;        // weights in the kernel's layout
+    float* d_nn = nullptr;           // recurrent state [n_streams][nn_stride]
+    float* d_ring = nullptr;         // k_mfma_lp: h of layer l-1 on its way to layer l, per stream group
+    uint32_t* d_counters = nullptr;  // k_mfma_lp: frames produced / consumed per (group, layer boundary)
+    mutable const void* lp_owner = nullptr;  // the pool whose hold on the device's LpGate this slot shares (d_ring != nullptr); given up on the launch path when the grid is refused
+    bool lp_fused = false;           // k_mfma_lp runs the DSP chain too (one-layer models, helper waves): one launch per block
+    uint32_t lp_round_streams = 0;   // k_mfma_ls on a pool larger than one resident grid: streams per launch (a pass is several launches over stream ranges); 0: one launch
+    mutable RelaxedFlag lp_refused;  // the runtime refused this model's chained grid (cooperative launch: not co-resident on this device): k_mfma serves it — this
+                                     // model only; another model of the pool, with a smaller grid, may still fit (set on the launch path, hence mutable)
+    int lp_split = 0;                // stacked models: k_mfma_ls serves the passes (contractions as bf16 term products of split operands): 6 or 9 products; 0: k_mfma_lp (fp32 MFMAs)
+    bool gru_gm = false;             // one-layer GRU: k_gru_gm (gate-major tiles, the whole run() in one launch) serves the passes
+    int lstm_gs = 0;                 // one-layer LSTM-40 / 64 on k_lstm_gs (k_gru_gs's structure): 6 or 9 term products; 0: not
+    int gru_gs = 0;                  // ... as k_gru_gs (recurrent product on the bf16 matrix pipe, operands split into three bf16 terms): 6 or 9 term products; 0: the fp32 kernel
+
+    float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
+    ModelRec rec() const { return model_rec(d_wpack, in_gain, out_gain, input_skip); }      // what a banked stream on this model reads of it
+    BankArch arch() const { return { cell, hidden, input_size, model_sr, has_model && kind == TABLE && kernel && kernel->fn_pipe_bank }; }
+};
+
+// The end markers of a pass, handed down to the launch that can carry them: the pipelined host path's "pass done" event, the blocking path's completion
+// word and the number to write. A launch that takes one clears it and raises its *_taken flag; the caller issues what was not taken behind the pass.
+struct PassEnd { hipEvent_t done = nullptr; uint32_t* word = nullptr; uint32_t seq = 0; bool done_taken = false, word_taken = false; };
+
+// The blocking host-buffer path's buffers (aidax_pool_process; alloc and release: aidax_pool_io.cpp)
+struct BlockingIo {
+    float* d_in = nullptr;           // staging for the host-buffer entry point
+    float* d_out = nullptr;
+    float* h_in = nullptr;           // pinned host staging (nullptr: blocks too large, pageable copies)
+    float* h_out = nullptr;
+    float* hd_in = nullptr;          // device view of h_in / h_out (zero-copy passes)
+    float* hd_out = nullptr;
+    bool zero_copy = false;
+    // completion word of a pass in pinned host memory: the stream writes the pass number behind its last launch and the
+    // caller of aidax_pool_process polls it — no interrupt, no wake-up of a blocked thread (small pools: the plugin case)
+    uint32_t* h_done = nullptr;
+    uint32_t* hd_done = nullptr;
+    uint32_t done_seq = 0;
+    bool spin_wait = false;
+    bool kernel_word = true;         // a one-workgroup pass (k_*_pipe / k_*_pipe4 of a one-stream pool) writes the completion word itself, behind its block:
+                                     // no packet follows the pass on its queue — 1.7 us of the LV2 instance's 23 us round trip at 64 frames
+                                     // (profiles/r06_host_pipeline.txt). AIDAX_KERNEL_WORD=0: the queue writes it (hipStreamWriteValue32), as in round 5
+    void alloc(size_t block_bytes, int device);      // (set-up side; reads AIDAX_ZEROCOPY, AIDAX_SPIN_WAIT, AIDAX_KERNEL_WORD)
+    void release();
+};
+
+// aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
+// block k and the download of the blocks in front of it run under the pass of block k (allocated by the first submit).
+// THREE sets since round 6: with two, submit(k) has to wait for collect(k - 2), which returns a cross-stream hop and a download
+// after pass k - 2 has ended; the upload of k and its own hop then end ~110 us after that — later than pass k - 1 (65 us for a
+// cfg2 block) does, and the GPU idles for the difference every block (88 us per block predicted, 83.8 measured in round 3).
+// A third set takes the host's round trip off the GPU's critical path: the pass is what is left.
+constexpr int kPipeSets = 3;
+struct Pipeline {
+    bool ready = false;
+    float* h_in[kPipeSets] = {}; float* h_out[kPipeSets] = {}; float* d_in[kPipeSets] = {}; float* d_out[kPipeSets] = {};
+    hipEvent_t ev_up[kPipeSets] = {}, ev_pass[kPipeSets] = {}, ev_down[kPipeSets] = {};
+    hipStream_t q_up = nullptr, q_down = nullptr;
+    uint32_t frames[kPipeSets] = {};
+    float* direct_out[kPipeSets] = {};      // the block's download went straight to this caller buffer (registered): collect() only waits
+    uint64_t submitted = 0, collected = 0;
+    void alloc(size_t cap);          // (the first submit: not a real-time call)
+    void release();
+};
+
+}  // namespace aidax
+using namespace aidax;               // (a private header of three sources that say the same)
+
+// A model on its way into (or out of) a pool. Built by aidax_pool_prepare_model on the worker thread; after
+// aidax_pool_commit_model the same object carries what the swap retired, for aidax_staged_free on the worker.
+struct aidax_staged {
+    int device = 0;
+    uint32_t n_streams = 0;
+    ModelSlot slot;
+    StreamState* d_pst = nullptr;    // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
+    hipEvent_t fence = nullptr;      // recorded by the commit: everything that may still touch the retired buffers precedes it
+    bool fenced = false;
+    enum Payload { MODEL, IR, BANK_SLOT } payload = MODEL;      // what is on its way: `slot`, `ir` (aidax_pool_prepare_ir / _slot) or `bank` (aidax_pool_prepare_model_slot)
+    int32_t ir_slot = AIDAX_IR_POOL; // IR: for the pool IR or for this bank slot
+    IrSlot ir;
+    uint32_t bank_slot = 0;
+    BankSlot bank;
+};
+
+struct aidax_pool {
+    int device = 0;
+    uint32_t n_streams = 0, max_frames = 0;
+    double host_sr = 48000.0;
+    float gain_coef = 0.f;
+    hipStream_t q = nullptr;         // the audio side's stream
+    hipStream_t wq = nullptr;        // the worker side's stream (prepare)
+    hipEvent_t ev_x = nullptr;       // edge between two streams that carry passes one after the other
+    hipEvent_t ev_adopt = nullptr;   // "everything this pool has issued so far": what a stream of ANOTHER pool waits for before it adopts one of ours
+    hipStream_t last_stream = nullptr;
+
+    StreamCtl* d_ctl = nullptr;
+    StreamState* d_st = nullptr;
+    BlockingIo io;                   // aidax_pool_process: staging, zero-copy views and the completion word
+    Pipeline pipe;                   // aidax_pool_submit / _collect (allocated by the first submit)
+    bool spin_collect = true;        // aidax_pool_collect polls the download's event instead of sleeping on it (AIDAX_SPIN_WAIT=0: off)
+    bool keep_warm = false;          // this pool holds a reference on its device's keep-warm thread (AIDAX_KEEP_WARM_US)
+    // k_mfma_lp: a word in pinned host memory that a workgroup bumps when a layer hand-over timed out. The pass that did
+    // so is wrong; whoever notices reports it, and the pool serves the model with k_mfma from then on (lp_off).
+    uint32_t* h_lp_fault = nullptr;
+    uint32_t* hd_lp_fault = nullptr;
+    mutable std::atomic<bool> lp_off{false};      // (mutable: set from the launch path, a const member function)
+    std::atomic<uint32_t> lp_faults{0};
+    mutable std::atomic<uint32_t> lp_refusals{0}; // chained grids the runtime refused (the text is in aidax_last_error(); kernel_name says k_mfma from then on)
+    bool take_lp_fault()
+    {
+        if (!h_lp_fault) return false;
+        // read-and-clear in ONE atomic step: workgroups bump the word with system-scope atomic adds while we look, and a
+        // give-up that landed between a read and a separate store of 0 would go unreported
+        if (__atomic_load_n(h_lp_fault, __ATOMIC_RELAXED) == 0) return false;
+        if (__atomic_exchange_n(h_lp_fault, 0u, __ATOMIC_ACQ_REL) == 0) return false;
+        lp_off.store(true, std::memory_order_relaxed);
+        lp_faults.fetch_add(1, std::memory_order_relaxed);
+        // the wrong block is in the IR history: clear it, so that it does not sound through the IR's tail (behind every pass issued so far)
+        if (ir.adopt()) {
+            if (last_stream && last_stream != q && hipEventRecord(ev_x, last_stream) == hipSuccess) (void)hipStreamWaitEvent(q, ev_x, 0);
+            last_stream = q;
+            ir.clear_all(q);
+        }
+        return true;
+    }
+
+    IrStage ir;                      // the cabinet IR stage behind every pass (aidax_ir_stage.h)
+    bool any_pass = false;           // the pool has issued a pass of n_frames > 0 (its first one has nothing for an IR change to fade from)
+    MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
+    GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
+    // aidax_pool_register_host: page-locked ranges of the caller's memory (copies to and from them need no staging)
+    struct HostRange { char* base; size_t bytes; };
+    std::vector<HostRange> host_ranges;
+    bool host_registered(const void* ptr, size_t bytes) const
+    {
+        const char* c = static_cast<const char*>(ptr);
+        for (const HostRange& r : host_ranges)
+            if (c >= r.base && c + bytes <= r.base + r.bytes) return true;
+        return false;
+    }
+
+    std::vector<aidax_controls> controls;
+    std::vector<uint8_t> loading;
+    std::vector<uint8_t> forced_off;                     // the hub parks a stream (raw copy, state does not move) without touching its controls
+    std::vector<StreamCtl> h_ctl;
+    DirtyRange ctl_dirty;                                // control records to upload
+    SnapshotRing ctl_ring;
+
+    ModelSlot cur;
+    ModelBankStage bank;             // the model bank (aidax_model_bank.h; nothing until the first aidax_pool_prepare_model_slot)
+    int tune = 0;                    // AIDAX_TUNE (measurement switches, see LaunchArgs)
+    int cus = 0;                     // compute units of the device (form selection)
+    int force_form = 0;              // AIDAX_KERNEL=wave|pipe|split|valu|mfma|quad overrides the heuristic (A/B testing)
+
+    // Form of a MODE_CHAIN pass of a TABLE slot: 0 one wave per stream, 1 three-wave pipeline (all streams resident at
+    // once: latency-bound regime), 2 split launches with packed chains (many streams: issue-bound regime), 3 four
+    // streams per workgroup with the cell on the matrix cores (k_lstm_q4: about four streams per CU or fewer)
+    int chain_form(const ModelSlot& m) const
+    {
+        if (m.kind != ModelSlot::TABLE && m.has_model) return 0;
+        if (m.has_model && m.d_wq4 && force_form == 7) return 3;      // opt-in only (AIDAX_KERNEL=q4): measured slower than the pipeline, see aidax_q4.hip
+        if (force_form == 1) return 0;
+        if (force_form == 2) return (m.has_model && m.kernel && m.kernel->fn_pipe) ? 1 : 0;
+        const bool packed_fits = chain_lds_bytes(max_frames) <= kChainLdsLimit;      // packed chains keep 8 blocks in LDS
+        if (force_form == 3) return (packed_fits && (!m.has_model || (m.kernel && m.kernel->fn_nn))) ? 2 : 0;
+        if (use_pipe(m)) return 1;
+        if (n_streams < 64 || !packed_fits) return 0;
+        return (!m.has_model || m.split_pays) ? 2 : 0;
+    }
+    // Models of the reference's table on the matrix-core kernels (many_streams_form); AIDAX_KERNEL=quad|mfma force one.
+    bool quad_for_table_model(int cell_kind, int hidden_units) const
+    {
+        if (force_form == 6) return true;
+        return force_form == 0 && many_streams_form(cell_kind, hidden_units, n_streams, cus, max_frames) == MANY_QUAD;
+    }
+    bool mfma_for_table_model(int cell_kind, int hidden_units) const
+    {
+        if (force_form == 5) return true;
+        return force_form == 0 && many_streams_form(cell_kind, hidden_units, n_streams, cus, max_frames) == MANY_MFMA;
+    }
+    bool use_pipe(const ModelSlot& m) const
+    {
+        if (!m.has_model || !m.kernel || !m.kernel->fn_pipe || m.kind != ModelSlot::TABLE) return false;
+        if (force_form == 1 || force_form == 3) return false;
+        if (force_form == 2) return true;
+        return static_cast<int>(n_streams) <= m.pipe_capacity;
+    }
+    // does a MODE_CHAIN pass of this slot consist of one launch (it may then read and write host memory in place)?
+    bool single_launch(const ModelSlot& m) const
+    {
+        if (&m == &cur && bank.in_force()) return true;
+        if (!m.has_model) return chain_form(m) != 2;
+        switch (m.kind) {
+        case ModelSlot::TABLE: return chain_form(m) != 2;
+        case ModelSlot::STACK: return true;
+        case ModelSlot::CONV: return !m.conv_mfma || m.conv_fused;
+        default: return false;
+        }
+    }
+
+    bool lp_in_use(const ModelSlot& m) const { return m.d_ring != nullptr && !m.lp_refused && !(m.mdesc.n_layers >= 2 && lp_off.load(std::memory_order_relaxed)); }
+
+    static size_t lds_bytes(const ModelSlot& m, uint32_t n_frames)
+    {
+        return (static_cast<size_t>((n_frames + 3) & ~3u) + static_cast<size_t>(m.hidden > 0 ? m.hidden + 4 : 4)) * sizeof(float);   // block + h row + spare slot
+    }
+
+    // Does a MODE_CHAIN pass of n frames go through the four-streams-per-workgroup pipeline (k_*_pipe4: 61.9 us per cfg2 block against
+    // k_lstm_pipe's 63.8, the small cells 9 - 19 % ahead, conditioned models 9 - 25 % at every cell up to 32: profiles/r06_cfg2_pipe4.txt, r06_pipe4_cells.txt)? Whole 16-frame tiles, at least one full
+    // workgroup of four streams (a conditioned model: any pool), every workgroup on a CU of its own; k_*_pipe serves every other pass on the same
+    // state (AIDAX_PIPE4=0, test build: all of them).
+    // (a plain model below one full workgroup: level at 256 frames, 0.6 - 1.0 us behind at 64 — the helper wave's longer prologue; a conditioned
+    // model is 11 - 20 % ahead also as a pool of ONE stream, the LV2 instance's: profiles/r06_pipe4_cells.txt. AIDAX_PIPE4_MIN, test build: the measurement's switch)
+    static uint32_t p4_min_streams(int input_size) { const char* e = AIDAX_HOOK_ENV("AIDAX_PIPE4_MIN"); return e ? (uint32_t)atoi(e) : input_size > 1 ? 1u : 4u; }
+    bool pipe4_serves(const ModelSlot& m, uint32_t n, int input_size) const
+    {
+        const bool off = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_PIPE4"); return e && e[0] == '0'; }();      // (read per call: tests switch forms within one process)
+        if (off || force_form != 0 || !m.kernel || !(input_size > 1 ? m.kernel->fn_pipe4c : m.kernel->fn_pipe4) || input_size < 1 || input_size > 3 || n == 0 || n % 16u || n_streams < p4_min_streams(input_size)) return false;
+        return cus > 0 && (n_streams + 3u) / 4u <= static_cast<uint32_t>(cus) && pipe4_lds_bytes(m.hidden, n, input_size) <= 160 * 1024;
+    }
+    void refresh_ctl(uint32_t s)
+    {
+        build_stream_ctl(controls[s], host_sr, cur.has_model, loading[s] != 0, gain_coef, cur.p_den(), &h_ctl[s]);
+        if (forced_off[s]) h_ctl[s].flags &= ~static_cast<uint32_t>(CTL_ENABLED);
+        ctl_dirty.mark(s, s);
+    }
+    void refresh_all()
+    {
+        // identical controls are the common case: design once, then copy
+        for (uint32_t s = 0; s < n_streams; ++s) {
+            if (s > 0 && std::memcmp(&controls[s], &controls[s - 1], sizeof(aidax_controls)) == 0 &&
+                loading[s] == loading[s - 1]) {
+                h_ctl[s] = h_ctl[s - 1];
+            } else {
+                build_stream_ctl(controls[s], host_sr, cur.has_model, loading[s] != 0, gain_coef, cur.p_den(), &h_ctl[s]);
+            }
+        }
+        for (uint32_t s = 0; s < n_streams; ++s)
+            if (forced_off[s]) h_ctl[s].flags &= ~static_cast<uint32_t>(CTL_ENABLED);
+        ctl_dirty.mark(0, n_streams - 1);
+    }
+    // the fields of a control record that depend on the model and on `loading`, without redesigning the filters
+    void patch_model_fields(uint32_t s)
+    {
+        StreamCtl& o = h_ctl[s];
+        const aidax_controls& c = controls[s];
+        o.master_target = loading[s] ? 0.f : db_to_coeff(c.master_db);                   // :490, :654
+        o.p_den = cur.p_den();
+        if (cur.has_model && !(c.net_bypass > 0.5f)) o.flags |= CTL_NET_ON;              // :631-632
+        else o.flags &= ~static_cast<uint32_t>(CTL_NET_ON);
+    }
+    // Upload the changed control records, stream-ordered with the pass that follows. The records leave from a
+    // ring of pinned snapshots, so the copy is asynchronous and a later set_controls cannot overtake it.
+    void flush_ctl(hipStream_t s) { ctl_ring.upload_dirty(d_ctl, h_ctl.data(), ctl_dirty, s); }
+    // Passes and control pokes are issued in program order by the audio side but may sit on two streams (the pool's
+    // own and one handed to aidax_pool_process_device): moving from one to the other puts an event edge between them.
+    void enter_stream(hipStream_t s)
+    {
+        if (last_stream && last_stream != s) {
+            HIP_TRY(hipEventRecord(ev_x, last_stream));
+            HIP_TRY(hipStreamWaitEvent(s, ev_x, 0));
+        }
+        last_stream = s;
+    }
+    // host side: wait for what the pool has issued on a caller's stream (its own stream is the caller's next wait)
+    void sync_issued() { if (last_stream && last_stream != q) HIP_TRY(hipStreamSynchronize(last_stream)); }
+    LaunchArgs args(const ModelSlot& m, StreamState* st, const float* in, float* out, uint32_t n_frames, int mode) const
+    {
+        LaunchArgs a{};
+        a.ctl = d_ctl; a.st = st; a.nn = m.d_nn;
+        a.in = in; a.out = out;
+        a.n_streams = n_streams; a.n_frames = n_frames; a.nn_stride = m.nn_stride;
+        a.mode = mode; a.input_size = m.input_size;
+        apply_model_rec(a, m.rec());
+        a.tune = tune;
+        return a;
+    }
+    // frames one launch of the extension kernels may carry (their LDS planes grow with n)
+    uint32_t ext_chunk() const { return max_frames < 256 ? max_frames : 256; }
+    uint32_t launch_chunk(const ModelSlot& m, uint32_t n) const
+    {
+        // (MFMA: k_mfma takes any length, but a 2048-frame warm-up launch would hold its CUs for ~10 ms next to the passes)
+        return (m.kind == ModelSlot::STACK || m.kind == ModelSlot::CONV || m.kind == ModelSlot::MFMA) ? std::min(ext_chunk(), n) : n;
+    }
+    // one pass (or warm-up, or bare-model run) of slot m in the form the pool chose for it; `end`: the pass's end markers, for a launch that can carry them (aidax_pool.cpp)
+    hipError_t launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s, PassEnd* end = nullptr) const;
+    // A fresh DynamicModel for stream s alone (:1035, :1053-1061), with START_WARMUP 2048 zeros through applyModel (:1077-1078): the launch
+    // arguments view the pool as one stream, which plays the model of `rec` (m's own, or a bank slot's weights, gains and skip)
+    void fresh_stream_model(const ModelSlot& m, uint32_t s, int start_mode, const ModelRec& rec, hipStream_t on) const
+    {
+        HIP_TRY(launch_reset_for_model(d_st + s, m.d_nn + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), on));
+        const uint32_t chunk = launch_chunk(m, kWarmupFrames);
+        for (uint32_t done = 0; start_mode == AIDAX_START_WARMUP && done < kWarmupFrames; done += chunk) {
+            LaunchArgs a = args(m, d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+            apply_model_rec(a, rec);
+            a.ctl += s; a.st += s; a.nn += static_cast<size_t>(s) * m.nn_stride;
+            a.n_streams = 1;
+            HIP_TRY(launch(m, a, on));
+        }
+    }
+    // an audio-side call that issues work on the pool's own stream, behind everything issued so far
+    template <class F> int on_own_stream(F&& f) { return guarded([&]() -> int { HIP_TRY(hipSetDevice(device)); enter_stream(q); return f(); }); }
+    void release()                   // (both callers delete the pool next: nothing is reset)
+    {
+        ir.release();
+        bank.release();
+        gate.release();
+        meter.release();
+        if (d_ctl) (void)hipFree(d_ctl);
+        if (d_st) (void)hipFree(d_st);
+        if (cur.d_nn) (void)hipFree(cur.d_nn);
+        if (cur.d_wpack) (void)hipFree(cur.d_wpack);
+        if (cur.d_wq4) (void)hipFree(cur.d_wq4);
+        if (cur.d_ring) (void)hipFree(cur.d_ring);
+        if (cur.d_counters) (void)hipFree(cur.d_counters);
+        if (cur.lp_owner) { lp_gate().release(device, cur.lp_owner); cur.lp_owner = nullptr; }
+        if (h_lp_fault)                                      // (measurement builds / AIDAX_TUNE bit 4096: the stamps behind the fault word)
+            if (const char* f = AIDAX_HOOK_ENV("AIDAX_LP_TRACE_FILE"))
+                if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(h_lp_fault + 16, 4, 1536, fp); std::fclose(fp); }
+        if (h_lp_fault) (void)hipHostFree(h_lp_fault);
+        for (const HostRange& r : host_ranges) (void)hipHostUnregister(r.base);
+        host_ranges.clear();
+        pipe.release();
+        io.release();
+        ctl_ring.release();
+        if (ev_x) (void)hipEventDestroy(ev_x);
+        if (ev_adopt) (void)hipEventDestroy(ev_adopt);
+        if (q) (void)hipStreamDestroy(q);
+        if (wq) (void)hipStreamDestroy(wq);
+    }
+};
+
+namespace aidax {
+// worker side (aidax_pool_model.cpp): what a staged object owns goes back; an empty staged object of pool p, with the fence its commit will record
+void staged_release(aidax_staged* s);
+using StagedPtr = std::unique_ptr<aidax_staged, void (*)(aidax_staged*)>;
+StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload);
+}  // namespace aidax

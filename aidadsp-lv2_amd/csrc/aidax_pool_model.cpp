@@ -1,0 +1,601 @@
+// aidax_pool_model.cpp — everything that builds or commits an aidax_staged (aidax_pool.h): a model, a model-bank slot or a cabinet IR on
+// its way into a pool — prepared on the worker thread, committed on the audio thread — and the entry points that ask which form and
+// kernel serve a model. Host logic only.
+#include <hip/hip_runtime_api.h>
+
+#include <cmath>
+
+#include "aidax_pool.h"
+
+namespace aidax {
+
+void staged_release(aidax_staged* s)
+{
+    if (!s) return;
+    (void)hipSetDevice(s->device);
+    if (s->fenced) (void)hipEventSynchronize(s->fence);         // passes that still read the retired buffers
+    if (s->slot.d_wpack) (void)hipFree(s->slot.d_wpack);
+    if (s->slot.d_wq4) (void)hipFree(s->slot.d_wq4);
+    if (s->slot.d_nn) (void)hipFree(s->slot.d_nn);
+    if (s->slot.d_ring) (void)hipFree(s->slot.d_ring);
+    if (s->slot.d_counters) (void)hipFree(s->slot.d_counters);
+    if (s->slot.lp_owner) lp_gate().release(s->device, s->slot.lp_owner);
+    if (s->d_pst) (void)hipFree(s->d_pst);
+    if (s->ir.d_frag) (void)hipFree(s->ir.d_frag);
+    if (s->bank.d_wpack) (void)hipFree(s->bank.d_wpack);
+    if (s->fence) (void)hipEventDestroy(s->fence);
+    delete s;
+}
+
+StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload)
+{
+    StagedPtr sg(new aidax_staged(), staged_release);
+    sg->device = p.device; sg->n_streams = p.n_streams; sg->payload = payload;
+    HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+    return sg;
+}
+
+namespace {
+
+// what prepare_impl uploads next to the slot: the weights in the chosen kernel's layout, k_lstm_q4's record where asked for; lp: the chained kernels serve the model if the LpGate allows
+struct Packed { std::vector<float> wp, wq4; bool lp = false; };
+
+// Which kernel form serves model m in pool p: fills the slot's host fields and packs the weights. No allocation, no launch (one
+// device-attribute query); what it sets of lp_split, lp_round_streams and lp_fused holds only if prepare_impl gets the chained kernel.
+int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed& pk)
+{
+    std::vector<float>& wp = pk.wp;
+    uint32_t state_floats = 0;
+    if (is_conv_model(*m)) {
+        ms.kind = ModelSlot::CONV;
+        wp = pack_conv(*m, &ms.cdesc, &state_floats);
+        ms.conv_mfma = p.force_form != 4 && convm_lds_bytes(ms.cdesc, p.ext_chunk()) <= 160 * 1024;
+        // the stacks k_conv_ms admits run there (the contraction as bf16 term products: BASELINE cfg4 60 -> see profiles/r05_cfg4_*); its
+        // per-layer histories live in the stream's state in ITS layout, so the choice holds for the life of the model in this pool
+        // (warm-up, bare-model modes and passes all run the one kernel). AIDAX_CONV_MS=0 (test build): k_conv_mfma, the fp32 partner.
+        const char* cms = AIDAX_HOOK_ENV("AIDAX_CONV_MS");
+        ms.conv_ms = ms.conv_mfma && ms.cdesc.ms_ok && !(cms && cms[0] == '0');
+        if (ms.conv_ms) state_floats = ms.cdesc.ms_state_floats;
+        // ... and of those, the stacks with a compiled geometry (conv_st_shape) take fused blocks of 64 / 128 / 256 frames through k_conv_st,
+        // the streaming form on the same state (AIDAX_CONV_ST=0, test build: k_conv_ms for every block)
+        const char* cst = AIDAX_HOOK_ENV("AIDAX_CONV_ST");
+        if (!ms.conv_ms || (cst && cst[0] == '0')) ms.cdesc.st_ok = 0;
+        // chain passes inside the conv launch while every workgroup of the pool is resident at once (their serial
+        // latency is then paid once per block; in a second round of workgroups it would be paid again, and the packed
+        // k_chain launches around the kernel are cheaper). AIDAX_CONV_FUSED=1 / 0 forces the form.
+        const char* fused = AIDAX_HOOK_ENV("AIDAX_CONV_FUSED");
+        ms.conv_fused = ms.conv_mfma && (fused ? fused[0] != '0'
+                                               : static_cast<int>(p.n_streams) <= (ms.conv_ms ? convs_resident_streams(p.device, ms.cdesc.st_ok - 1) : convm_resident_streams(ms.cdesc, p.ext_chunk(), p.device)));
+        if (ms.conv_mfma && p.max_frames > 256) ms.conv_fused = true;      // long blocks go through in time slices: the one-launch form only
+        if (!ms.conv_mfma && conv_lds_bytes(ms.cdesc, p.max_frames) > 160 * 1024)
+            return fail(AIDAX_ERR_ARG, "conv model: pool max_frames too large for the LDS activation planes");
+    } else if (m->n_rnn == 1 && find_kernel(m->cell, m->hidden) && p.quad_for_table_model(m->cell, m->hidden) &&
+               chain_lds_bytes(p.max_frames) <= kChainLdsLimit && quad_lds_bytes(m->hidden, p.max_frames) <= 160 * 1024) {
+        ms.kind = ModelSlot::QUAD;
+        wp = pack_quad(*m, &ms.qdesc.bias_off, &ms.qdesc.dense_off);
+        state_floats = static_cast<uint32_t>(m->cell == AIDAX_CELL_LSTM ? 2 * m->hidden : m->hidden);
+    } else if (mfma_form_fits(*m) && chain_lds_bytes(p.max_frames) <= kChainLdsLimit &&
+               (is_stack_model(*m) ? p.force_form != 4 : p.mfma_for_table_model(m->cell, m->hidden))) {
+        ms.kind = ModelSlot::MFMA;
+        wp = pack_mfma(*m, &ms.mdesc, &state_floats);
+    } else if (is_stack_model(*m)) {
+        ms.kind = ModelSlot::STACK;
+        wp = pack_stack(*m, &ms.sdesc, &state_floats);
+        if (stack_lds_bytes(ms.sdesc, p.max_frames) > 160 * 1024)
+            return fail(AIDAX_ERR_ARG, "stacked model: pool max_frames too large for the LDS block buffers");
+    } else {
+        ms.kind = ModelSlot::TABLE;
+        ms.kernel = find_kernel(m->cell, m->hidden);
+        wp = pack_weights(*m);
+        const int alt = (m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;   // a natural-order copy for k_nn
+        if (static_cast<int>(wp.size()) != ms.kernel->pack_regs * kWave + m->hidden + 1 + alt) return fail(AIDAX_ERR_STATE, "weight pack size mismatch");
+        state_floats = static_cast<uint32_t>(ms.kernel->state_floats);
+    }
+    ms.nn_stride = (state_floats + 3u) & ~3u;
+    ms.cell = m->cell;
+    ms.hidden = m->hidden;
+    ms.input_size = m->input_size;
+    ms.input_skip = m->input_skip;
+    ms.in_gain = m->input_gain;
+    ms.out_gain = m->output_gain;
+    ms.model_sr = m->samplerate;
+    ms.pipe_capacity = ms.kernel ? pipe_resident_streams(ms.kernel, p.max_frames, p.device) : 0;
+    ms.split_pays = ms.kernel ? split_form_pays(ms.kernel, p.max_frames) : false;
+    ms.has_model = true;
+
+    // Stacked model: one workgroup per (16 streams, layer), chained through a ring in global memory — where that adds
+    // parallelism, i.e. while every (group, layer) workgroup gets a CU of its own (2048 streams for two layers on 256
+    // CUs: 1.9x over one workgroup per group; beyond, where the CUs are full either way, a second round of workgroups
+    // costs what the resident weights save: 4096 streams 2.49 against 2.45 ms). AIDAX_MFMA_LP=1 / 0 forces it on / off.
+    const char* lp = AIDAX_HOOK_ENV("AIDAX_MFMA_LP");
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device));
+    const size_t lp_groups = (p.n_streams + kMfmaStreams - 1) / kMfmaStreams;
+    // (one-layer models of <= 48 units in the one-launch form: also in several rounds of workgroups — nothing waits for anything,
+    // and LSTM-40 at 8192 streams measures 521 us against 583 us for k_mfma; profiles/r03_cfg3_forms.txt)
+    const bool lp_rounds_ok = ms.kind == ModelSlot::MFMA && ms.mdesc.n_layers == 1 && ms.mdesc.hidden <= 48 && mfma_lp_fused_serves(ms.mdesc, p.max_frames);
+    // (a one-layer model has no hand-over and nothing to wait for: no hold on the device's gate needed)
+    const bool lp_chained = ms.mdesc.n_layers >= 2;
+    // Round 4: k_mfma_ls is fast enough to pay in SEVERAL rounds too — a pass over more streams than one resident grid holds goes
+    // out as one launch per range of streams (each a resident, cooperative grid; same ring, the counters are per group):
+    // LSTM-96 x 2 at 4096 streams 2 x 0.71 ms against 2.48 ms on k_mfma, at 16 384 streams 8 x 0.71 against 9.42 ms.
+    const char* sp_env = AIDAX_HOOK_ENV("AIDAX_LP_SPLIT");
+    // (a lone layer on k_mfma_ls: AIDAX_LS1=1 / 0 forces it on / off)
+    const char* ls1_env = AIDAX_HOOK_ENV("AIDAX_LS1");
+    const bool ls1 = !lp_chained && (ls1_env ? ls1_env[0] != '0' : lone_split_pays(m->cell, m->hidden, p.n_streams, cus, p.max_frames));
+    const bool ls_ok = ms.kind == ModelSlot::MFMA && (lp_chained || ls1) && mfma_ls_serves(ms.mdesc) && !(sp_env && sp_env[0] == '0') &&
+                       mfma_ls_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
+    const char* rg_env = AIDAX_HOOK_ENV("AIDAX_LP_ROUND_GROUPS");      // (tests: ranges of this many stream groups, so that a small pool goes out in several)
+    const size_t round_groups = rg_env && std::atoi(rg_env) > 0
+                                    ? static_cast<size_t>(std::atoi(rg_env))
+                                    : static_cast<size_t>(cus) / static_cast<size_t>(ms.mdesc.n_layers > 0 ? ms.mdesc.n_layers : 1) / 8 * 8;      // workgroup ids come in eights
+    // ... where k_mfma_ls's time per resident grid beats k_mfma's rate on a full chip (profiles/r04_ls_rounds_ab.txt): 64 units and
+    // more — LSTM-96 x 2 x1.65 / GRU-96 x 2 x1.64, 64 units x 2 x1.17..1.19, x 3 x1.10..1.16, GRU-80 x1.03; below 64 units k_mfma
+    // wins by x1.4..1.65, and LSTM-80 (the four-wave geometry) pays up to two grids' worth of streams only
+    const bool ranges_pay = rg_env || (ms.mdesc.hidden >= 64 && (ms.mdesc.hidden != 80 || ms.mdesc.L[0].cell != 0 || lp_groups <= static_cast<size_t>(cus)));
+    const bool ls_rounds = ls_ok && ranges_pay && round_groups >= (rg_env ? 1u : 8u) && lp_groups > round_groups && !(lp && lp[0] == '1');
+    // (the grid a chained launch asks for: workgroup ids come in eights, so the group count is rounded up — the padded workgroups return
+    // at once, but a cooperative launch counts them: 85 groups x 3 layers are 264 workgroups, not 255)
+    const size_t lp_blocks = (lp_groups + 7) / 8 * 8 * static_cast<size_t>(ms.mdesc.n_layers);
+    const bool lp_pays = lp ? lp[0] != '0' : (lp_rounds_ok || ls_rounds || (ls_ok && !lp_chained) || lp_blocks <= static_cast<size_t>(cus));
+    pk.lp = ms.kind == ModelSlot::MFMA && mfma_lp_serves(ms.mdesc) && lp_pays && mfma_lp_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
+    if (pk.lp) {
+        // stacked models whose split fragments fit the register file: the same hand-over with the contractions on the bf16 matrix
+        // pipe (k_mfma_ls; AIDAX_LP_SPLIT=0: the fp32 kernel, =9: every term product instead of six — A/B runs)
+        ms.lp_split = ls_ok ? (sp_env && sp_env[0] == '9' ? 9 : 6) : 0;
+        ms.lp_round_streams = ls_rounds ? static_cast<uint32_t>(round_groups) * kMfmaStreams : 0u;
+        const char* fu = AIDAX_HOOK_ENV("AIDAX_LP_FUSED");      // (=0: packed k_chain launches around the kernel, A/B runs)
+        ms.lp_fused = !(fu && fu[0] == '0') &&
+                      (ms.lp_split ? mfma_ls_fused_serves(ms.mdesc, p.max_frames) && mfma_ls_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024
+                                   : mfma_lp_fused_serves(ms.mdesc, p.max_frames) && mfma_lp_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024);
+    }
+    if (ms.kind == ModelSlot::MFMA) {
+        const char* gm = AIDAX_HOOK_ENV("AIDAX_GRU_GM");        // (=0: the four-rows-per-unit kernels; =f32: k_gru_gm with fp32 MFMAs — A/B runs)
+        ms.gru_gm = gru_gm_serves(ms.mdesc) && !(gm && gm[0] == '0') && gru_gm_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
+        const char* np = AIDAX_HOOK_ENV("AIDAX_GS_PRODUCTS");   // (=9: every term product of the split operands instead of six)
+        ms.lstm_gs = lstm_gs_serves(ms.mdesc) && lstm_gs_pays(m->cell, m->hidden, p.n_streams, cus) && lstm_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024
+                         ? (np && np[0] == '9' ? 9 : 6) : 0;
+        ms.gru_gs = gru_gs_serves(ms.mdesc) && !(gm && (gm[0] == 'f' || gm[0] == '0')) && gru_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024
+                        ? (np && np[0] == '9' ? 9 : 6) : 0;
+        if (ms.gru_gs) ms.gru_gm = true;                       // (80 units: the split kernel only — the flag says "one-launch gate-major form")
+        else if (!gru_gm_serves(ms.mdesc)) ms.gru_gm = false;
+    }
+    // AIDAX_KERNEL=q4 (A/B runs and tests only): LSTM-32 snapshot models, four streams per workgroup with the cell on the
+    // matrix cores; the table kernels' record stays for warm-ups and the bare-model modes
+    if (ms.kind == ModelSlot::TABLE && q4_serves(m->cell, m->hidden, m->input_size) && p.force_form == 7 && q4_lds_bytes(m->hidden, p.max_frames) <= 64 * 1024)
+        pk.wq4 = pack_q4(*m);
+    return AIDAX_OK;
+}
+
+// loadModelFromPath's device half (rt-neural-generic.cpp:1034-1079) into buffers of its own. Worker thread:
+// packs, allocates, uploads and warms up on the pool's worker stream and waits for it; touches nothing the
+// audio side uses except for reading each stream's PARAM targets (as work() reads them at :822-825).
+int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_staged** out)
+{
+    HIP_TRY(hipSetDevice(p.device));
+    StagedPtr sg = new_staged(p, aidax_staged::MODEL);
+    if (!m) {                                             // unload: an empty slot to swap in
+        *out = sg.release();
+        return AIDAX_OK;
+    }
+    if (!model_supported(*m)) return fail(AIDAX_ERR_ARCH, "Unable to identify a known model architecture! (no kernel)");
+    ModelSlot& ms = sg->slot;
+    Packed pk;                                            // (lives until the stream has been waited for below)
+    if (const int rc = choose_form(p, m, ms, pk)) return rc;
+    const std::vector<float>& wp = pk.wp;
+    HIP_TRY(hipMalloc(&ms.d_wpack, wp.size() * sizeof(float)));
+    HIP_TRY(hipMalloc(&ms.d_nn, static_cast<size_t>(p.n_streams) * ms.nn_stride * sizeof(float)));
+    HIP_TRY(hipMalloc(&sg->d_pst, sizeof(StreamState) * p.n_streams));
+    const bool lp_chained = ms.mdesc.n_layers >= 2;       // (only a hand-over between layers needs the hold on the device's gate)
+    if (pk.lp && !(lp_chained && p.lp_off.load()) && (!lp_chained || lp_gate().acquire(p.device, &p, &p.lp_off))) {
+        if (lp_chained) ms.lp_owner = &p;
+        const uint32_t ring_streams = ms.lp_round_streams ? ms.lp_round_streams : p.n_streams;
+        const size_t ring_bytes = ms.lp_split ? mfma_ls_ring_bytes(ms.mdesc, ring_streams) : mfma_lp_ring_bytes(ms.mdesc, p.n_streams);
+        HIP_TRY(hipMalloc(&ms.d_ring, ring_bytes));
+        HIP_TRY(hipMalloc(&ms.d_counters, mfma_lp_counter_bytes(ms.mdesc, p.n_streams)));
+        HIP_TRY(hipMemsetAsync(ms.d_counters, 0, mfma_lp_counter_bytes(ms.mdesc, p.n_streams), p.wq));
+    } else {
+        ms.lp_split = 0; ms.lp_round_streams = 0; ms.lp_fused = false;
+    }
+    HIP_TRY(hipMemcpyAsync(ms.d_wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
+    if (!pk.wq4.empty()) {
+        HIP_TRY(hipMalloc(&ms.d_wq4, pk.wq4.size() * sizeof(float)));
+        HIP_TRY(hipMemcpyAsync(ms.d_wq4, pk.wq4.data(), pk.wq4.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
+    }
+    // fresh DynamicModel per stream: reset() + param smoothers around the targets the playing model holds now
+    // (:822-825, :1035, :1053-1061) ...
+    HIP_TRY(launch_stage_params(p.d_st, sg->d_pst, p.n_streams, p.wq));
+    HIP_TRY(launch_reset_for_model(sg->d_pst, ms.d_nn, p.n_streams, ms.nn_stride, ms.p_den(), p.wq));
+    if (start_mode == AIDAX_START_WARMUP) {               // ... and 2048 zeros through applyModel (:1077-1078)
+        const uint32_t chunk = p.launch_chunk(ms, kWarmupFrames);
+        for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
+            LaunchArgs a = p.args(ms, sg->d_pst, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+            HIP_TRY(p.launch(ms, a, p.wq));
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(p.wq));                  // `wp` is pageable; the audio side must find the model complete
+    *out = sg.release();
+    return AIDAX_OK;
+}
+
+// work_response() (:859-893): swap, loading = false. Audio thread: host assignments plus one tiny kernel on the
+// pool's stream; no allocation, no free, no wait.
+int commit_impl(aidax_pool& p, aidax_staged* sg)
+{
+    if (sg->slot.has_model) HIP_TRY(launch_install_params(p.d_st, sg->d_pst, p.n_streams, p.q));
+    HIP_TRY(hipEventRecord(sg->fence, p.q));              // the retired buffers are free once this has passed
+    sg->fenced = true;
+    std::swap(p.cur, sg->slot);
+    const uint8_t loading = p.cur.has_model ? 0 : 1;      // :889 (unload: loading = true)
+    for (uint32_t s = 0; s < p.n_streams; ++s) {
+        p.loading[s] = loading;
+        p.patch_model_fields(s);
+    }
+    p.ctl_dirty.mark(0, p.n_streams - 1);
+    return AIDAX_OK;
+}
+
+}  // namespace
+}  // namespace aidax
+
+extern "C" {
+
+AIDAX_API int aidax_pool_prepare_model(aidax_pool* p, const aidax_model* m, int start_mode, aidax_staged** out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
+    return guarded([&]() { return prepare_impl(*p, m, start_mode, out); });
+}
+
+AIDAX_API int aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged)
+{
+    if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
+    if (staged->payload == aidax_staged::IR) return fail(AIDAX_ERR_ARG, "staged object holds an IR: commit it with aidax_pool_commit_ir");
+    if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged model was committed already");
+    if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged model belongs to another pool");
+    ModelBank* b = p->bank.adopt();
+    if (staged->payload == aidax_staged::BANK_SLOT) {
+        // a bank slot's content: host integers, then the swap and the fence behind everything that may still read the retired weights
+        if (!b) return fail(AIDAX_ERR_STATE, "the pool has no model bank");
+        if (const int rc = b->may_commit_slot(staged->bank_slot, staged->bank, p->cur.arch())) return rc;
+        return p->on_own_stream([&]() -> int {
+            HIP_TRY(hipEventRecord(staged->fence, p->q));
+            staged->fenced = true;
+            b->commit_slot(staged->bank_slot, staged->bank);
+            return AIDAX_OK;
+        });
+    }
+    if (const int rc = b ? b->may_commit_pool_model(staged->slot.arch()) : AIDAX_OK) return rc;
+    return p->on_own_stream([&] { return commit_impl(*p, staged); });
+}
+
+// Worker thread: the slot's weights in the pool model's layout, uploaded on the worker stream; the first call allocates the bank.
+AIDAX_API int aidax_pool_prepare_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m, aidax_staged** out)
+{
+    if (out) *out = nullptr;
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (slot >= static_cast<uint32_t>(AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be 0 .. 63");
+    const ModelSlot& cur = p->cur;
+    if (!cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model: the bank holds variants of the pool model");
+    const char* other_kernel = !m || (cur.kind == ModelSlot::TABLE && cur.kernel) ? nullptr : aidax_pool_kernel_name(p);
+    if (const int rc = m ? bank_may_stage(*m, cur.arch(), other_kernel, pipe_lds_bytes(cur.hidden, p->max_frames) <= 64 * 1024) : AIDAX_OK) return rc;
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        StagedPtr sg = new_staged(*p, aidax_staged::BANK_SLOT);
+        sg->bank_slot = slot;
+        const int alt = (m && m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;
+        p->bank.prepare(p->n_streams, m, m ? cur.kernel->pack_regs * kWave + m->hidden + 1 + alt : 0, sg->bank, p->wq);
+        *out = sg.release();
+        return AIDAX_OK;
+    });
+}
+
+// The set-up side's one-call forms: prepared content (rc: its prepare's result) committed at once, and what the swap retired (or, on
+// failure, the unused content) freed
+static int commit_and_free(aidax_pool* p, int rc, aidax_staged* sg, int (*commit)(aidax_pool*, aidax_staged*))
+{
+    if (rc == AIDAX_OK) rc = commit(p, sg);
+    aidax_staged_free(sg);
+    return rc;
+}
+
+AIDAX_API int aidax_pool_set_model_slot(aidax_pool* p, uint32_t slot, const aidax_model* m)
+{
+    aidax_staged* sg = nullptr;
+    const int rc = aidax_pool_prepare_model_slot(p, slot, m, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_model);
+}
+
+// Audio side, between passes: the stream becomes a fresh DynamicModel of the slot's model (:822-825, :1046-1079) — host records plus
+// the launches aidax_pool_reset_stream issues for the same purpose, on the pool's stream behind every pass issued so far.
+AIDAX_API int aidax_pool_assign_model(aidax_pool* p, int32_t stream, int32_t slot, int start_mode)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range (one stream per call)");
+    if (slot != AIDAX_MODEL_POOL && (slot < 0 || slot >= AIDAX_MODEL_SLOTS)) return fail(AIDAX_ERR_ARG, "model slot must be the pool model (-1) or 0 .. 63");
+    if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
+    ModelBank* b = p->bank.adopt();
+    if (slot >= 0 && (!b || !b->slot[slot].loaded)) return fail(AIDAX_ERR_STATE, "model bank slot " + std::to_string(slot) + " is empty");
+    if (!p->cur.has_model) return fail(AIDAX_ERR_STATE, "the pool has no model");
+    const uint32_t s = static_cast<uint32_t>(stream);
+    return p->on_own_stream([&]() -> int {
+        const ModelSlot& m = p->cur;
+        p->fresh_stream_model(m, s, start_mode, slot >= 0 ? ModelBank::rec_of(b->slot[slot]) : m.rec(), p->q);
+        if (b) b->assign_stream(s, slot, m.rec());          // (no bank: the stream was and stays on the pool model)
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_stream_model(const aidax_pool* p, uint32_t stream, int32_t* slot)
+{
+    if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const ModelBank* b = p->bank.adopt();
+    *slot = b ? b->assign[stream] : AIDAX_MODEL_POOL;
+    return AIDAX_OK;
+}
+
+AIDAX_API void aidax_staged_free(aidax_staged* staged) { staged_release(staged); }
+
+AIDAX_API int aidax_pool_set_model(aidax_pool* p, const aidax_model* m, int start_mode)
+{
+    aidax_staged* sg = nullptr;
+    const int rc = aidax_pool_prepare_model(p, m, start_mode, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_model);
+}
+
+// The cabinet IR, split between the threads like a model swap (IrStage::prepare on the worker, IrStage::commit on the audio thread).
+static int prepare_ir_impl(aidax_pool* p, int32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    *out = nullptr;
+    if (slot != AIDAX_IR_POOL && (slot < 0 || slot >= AIDAX_IR_SLOTS)) return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
+    if (taps) {
+        const uint32_t capacity = p->ir.capacity.load(std::memory_order_relaxed);
+        if (n_taps == 0 || n_taps > capacity)
+            return fail(AIDAX_ERR_ARG, "IR length must be 1 .. " + std::to_string(capacity) + " taps" + (capacity != kIrMaxTaps ? " (the pool's IR capacity)" : ""));
+        for (uint32_t k = 0; k < n_taps; ++k)
+            if (!std::isfinite(taps[k])) return fail(AIDAX_ERR_ARG, "IR tap " + std::to_string(k) + " is not finite");
+        if (samplerate != p->host_sr)
+            return fail(AIDAX_ERR_ARG, "IR sample rate " + std::to_string(samplerate) + " differs from the pool's " + std::to_string(p->host_sr) + " (no resampling)");
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        StagedPtr sg = new_staged(*p, aidax_staged::IR);
+        sg->ir_slot = slot;
+        p->ir.prepare(taps, n_taps, sg->ir);
+        *out = sg.release();
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_prepare_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out) { return prepare_ir_impl(p, AIDAX_IR_POOL, taps, n_taps, samplerate, out); }
+
+AIDAX_API int aidax_pool_prepare_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate, aidax_staged** out)
+{
+    if (slot >= static_cast<uint32_t>(AIDAX_IR_SLOTS)) {
+        if (out) *out = nullptr;
+        return fail(AIDAX_ERR_ARG, "IR slot must be 0 .. 63");
+    }
+    return prepare_ir_impl(p, static_cast<int32_t>(slot), taps, n_taps, samplerate, out);
+}
+
+AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
+{
+    if (!p || !staged) return fail(AIDAX_ERR_ARG, "null argument");
+    if (staged->payload != aidax_staged::IR) return fail(AIDAX_ERR_ARG, "staged object holds a model: commit it with aidax_pool_commit_model");
+    if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged IR was committed already");
+    if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged IR belongs to another pool");
+    return p->on_own_stream([&]() -> int {
+        p->ir.commit(staged->ir_slot, staged->ir, staged->fence, p->q);
+        staged->fenced = true;
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_set_ir(aidax_pool* p, const float* taps, uint32_t n_taps, double samplerate)
+{
+    aidax_staged* sg = nullptr;
+    const int rc = aidax_pool_prepare_ir(p, taps, n_taps, samplerate, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_ir);
+}
+
+AIDAX_API int aidax_pool_set_ir_slot(aidax_pool* p, uint32_t slot, const float* taps, uint32_t n_taps, double samplerate)
+{
+    aidax_staged* sg = nullptr;
+    const int rc = aidax_pool_prepare_ir_slot(p, slot, taps, n_taps, samplerate, &sg);
+    return commit_and_free(p, rc, sg, aidax_pool_commit_ir);
+}
+
+// Audio thread: host assignments only (the plan is rebuilt by the next pass).
+AIDAX_API int aidax_pool_assign_ir(aidax_pool* p, int32_t stream, int32_t slot)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    if (slot != AIDAX_IR_POOL && slot != AIDAX_IR_NONE && (slot < 0 || slot >= AIDAX_IR_SLOTS))
+        return fail(AIDAX_ERR_ARG, "IR slot must be the pool IR (-1), none (-2) or 0 .. 63");
+    IrPlan& plan = p->ir.plan;
+    if (stream == AIDAX_ALL_STREAMS) std::fill(plan.assign.begin(), plan.assign.end(), slot);
+    else plan.assign[stream] = slot;
+    plan.dirty = true;
+    return AIDAX_OK;
+}
+
+// Audio thread: a host record (the plan is rebuilt by the next pass that finds a change).
+AIDAX_API int aidax_pool_set_ir_fade(aidax_pool* p, uint32_t frames)
+{
+    if (frames > kIrMaxTaps) return fail(AIDAX_ERR_ARG, "IR fade length must be 0 .. 8192 frames");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    p->ir.plan.fade = frames;
+    return AIDAX_OK;
+}
+
+AIDAX_API uint32_t aidax_pool_ir_fade(const aidax_pool* p) { return p ? p->ir.plan.fade : 0; }
+
+// Audio thread: host assignments only. A stream at rest on A does not play its B side: the plan stands.
+AIDAX_API int aidax_pool_assign_ir_b(aidax_pool* p, int32_t stream, int32_t slot)
+{
+    if (slot != AIDAX_IR_POOL && slot != AIDAX_IR_NONE && (slot < 0 || slot >= AIDAX_IR_SLOTS))
+        return fail(AIDAX_ERR_ARG, "IR slot must be the pool IR (-1), none (-2) or 0 .. 63");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    IrPlan& plan = p->ir.plan;
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    for (uint32_t s = lo; s < hi; ++s) {
+        if (plan.assign_b[s] == slot) continue;
+        plan.assign_b[s] = slot;
+        if (plan.rest(s) != 0) plan.dirty = true;
+    }
+    return AIDAX_OK;
+}
+
+// Audio thread: host records (every stream's ramp starts from its own weight of the last frame issued).
+AIDAX_API int aidax_pool_set_ir_mix(aidax_pool* p, int32_t stream, float mix, uint32_t ramp_frames)
+{
+    if (!(mix >= 0.f && mix <= 1.f)) return fail(AIDAX_ERR_ARG, "IR mix must be a finite value in [0, 1]");
+    if (ramp_frames > kIrMaxRamp) return fail(AIDAX_ERR_ARG, "IR mix ramp must be 0 .. 16777216 frames");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    IrPlan& plan = p->ir.plan;
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    for (uint32_t s = lo; s < hi; ++s) plan.set_mix(s, mix, ramp_frames);
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_stream_ir_mix(const aidax_pool* p, uint32_t stream, int32_t* slot_b, float* mix_now, float* mix_target, uint32_t* frames_left)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const IrPlan& plan = p->ir.plan;
+    if (slot_b) *slot_b = plan.assign_b[stream];
+    if (mix_now) *mix_now = plan.ramp[stream].now;
+    if (mix_target) *mix_target = plan.ramp[stream].m1;
+    if (frames_left) *frames_left = plan.frames_left(stream);
+    return AIDAX_OK;
+}
+
+// Set-up side: a host record that the first prepare reads when it sizes the history ring (R >= capacity + max_frames); the kernels take
+// the ring's mask and row, and every IR's diagonal count, at run time.
+AIDAX_API int aidax_pool_set_ir_capacity(aidax_pool* p, uint32_t max_taps)
+{
+    if (max_taps < kIrMaxTaps || max_taps > AIDAX_IR_MAX_CAPACITY) return fail(AIDAX_ERR_ARG, "IR capacity must be 8192 .. 65536 taps");
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (p->ir.has_history())
+        return fail(AIDAX_ERR_STATE, "IR capacity is fixed once the first aidax_pool_prepare_ir / _ir_slot has allocated the history");
+    p->ir.capacity.store(max_taps, std::memory_order_relaxed);
+    return AIDAX_OK;
+}
+
+AIDAX_API uint32_t aidax_pool_ir_capacity(const aidax_pool* p) { return p ? p->ir.capacity.load(std::memory_order_relaxed) : 0; }
+
+AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t* slot)
+{
+    if (!p || !slot) return fail(AIDAX_ERR_ARG, "null argument");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    *slot = p->ir.plan.assign[stream];
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_many_streams_form(int cell, int hidden, uint32_t n_streams, int compute_units)
+{
+    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, 256));
+}
+AIDAX_API int aidax_many_streams_form_at(int cell, int hidden, uint32_t n_streams, int compute_units, uint32_t max_frames)
+{
+    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, max_frames));
+}
+
+AIDAX_API int aidax_model_conv_form(const aidax_model* m)
+{
+    if (!m || !is_conv_model(*m)) return 0;
+    ConvDesc d;
+    uint32_t state_floats = 0;
+    (void)pack_conv(*m, &d, &state_floats);
+    if (convm_lds_bytes(d, 256) > 160 * 1024) return 1;
+    return d.st_ok ? 4 : d.ms_ok ? 3 : 2;
+}
+
+AIDAX_API const char* aidax_pool_kernel_name(const aidax_pool* p)
+{
+    if (!(p && p->cur.has_model)) return "k_nomodel";
+    const ModelSlot& m = p->cur;
+    if (m.kind == ModelSlot::STACK) return "k_stack";
+    if (m.kind == ModelSlot::MFMA && m.lstm_gs) return "k_lstm_gs";
+    if (m.kind == ModelSlot::MFMA) return m.gru_gm ? (m.gru_gs ? "k_gru_gs" : "k_gru_gm") : !p->lp_in_use(m) ? "k_chain+k_mfma" : m.lp_split ? (m.mdesc.n_layers == 1 ? (m.lp_fused ? "k_mfma_ls1" : "k_chain+k_mfma_ls1") : m.lp_fused ? "k_mfma_ls" : "k_chain+k_mfma_ls") : m.lp_fused ? "k_mfma_lp" : "k_chain+k_mfma_lp";
+    if (m.kind == ModelSlot::QUAD) return "k_chain+k_quad";
+    if (m.kind == ModelSlot::CONV && m.conv_ms && m.conv_fused && m.cdesc.st_ok && p->max_frames >= 64) return "k_conv_st";      // (what a block of 64 / 128 / 256 frames runs; every other length: k_conv_ms)
+    if (m.kind == ModelSlot::CONV) return m.conv_ms ? (m.conv_fused ? "k_conv_ms" : "k_chain+k_conv_ms") : m.conv_fused ? "k_conv_mfma" : m.conv_mfma ? "k_chain+k_conv_mfma" : "k_conv";
+    if (p->bank.in_force()) return m.kernel->name_pipe_bank;      // a stream plays a bank slot: every pass is the bank kernel's
+    const int form = p->chain_form(m);
+    // (form 1: what a block of the pool's full length runs with the controls as they stand — k_*_pipe4 where it serves, k_*_pipe otherwise)
+    if (form == 1 && p->pipe4_serves(m, p->max_frames, m.input_size)) return m.kernel->name_pipe4;
+    return form == 3 ? "k_lstm_q4<32>" : form == 1 ? m.kernel->name_pipe : form == 2 ? m.kernel->name_split : m.kernel->name;
+}
+
+AIDAX_API int aidax_model_forward(const aidax_model* m, int device_id, const float* X, float* y, uint32_t n, int unit_gains)
+{
+    if (!m || !X || !y) return fail(AIDAX_ERR_ARG, "null argument");
+    aidax_pool* p = nullptr;
+    int rc = aidax_pool_create(1, 4, 48000.0, device_id, &p);
+    if (rc != AIDAX_OK) return rc;
+    rc = aidax_pool_set_model(p, m, AIDAX_START_RESET);
+    if (rc == AIDAX_OK) {
+        rc = guarded([&]() -> int {
+            float* d_x = nullptr;
+            float* d_y = nullptr;
+            const size_t xb = sizeof(float) * static_cast<size_t>(n) * m->input_size;
+            HIP_TRY(hipMalloc(&d_x, xb ? xb : 4));
+            HIP_TRY(hipMalloc(&d_y, sizeof(float) * (n ? n : 1)));
+            HIP_TRY(hipMemcpyAsync(d_x, X, xb, hipMemcpyHostToDevice, p->q));
+            hipError_t le = hipSuccess;
+            const uint32_t chunk = p->launch_chunk(p->cur, n ? n : 1);
+            for (uint32_t done = 0; done < n && le == hipSuccess; done += chunk) {
+                LaunchArgs a = p->args(p->cur, p->d_st, d_x + static_cast<size_t>(done) * m->input_size, d_y + done,
+                                       std::min(chunk, n - done), MODE_NN_ONLY);
+                if (unit_gains) { a.in_gain = 1.f; a.out_gain = 1.f; }
+                le = p->launch(p->cur, a, p->q);
+            }
+            if (le == hipSuccess) {
+                (void)hipMemcpyAsync(y, d_y, sizeof(float) * n, hipMemcpyDeviceToHost, p->q);
+            }
+            const hipError_t se = hipStreamSynchronize(p->q);
+            (void)hipFree(d_x);
+            (void)hipFree(d_y);
+            HIP_TRY(le);
+            HIP_TRY(se);
+            return AIDAX_OK;
+        });
+    }
+    aidax_pool_destroy(p);
+    return rc;
+}
+
+AIDAX_API int aidax_model_self_test(const aidax_model* m, int device_id, int32_t* n_errors, float* max_error, float* out_opt)
+{
+    if (!m || !n_errors || !max_error) return fail(AIDAX_ERR_ARG, "null argument");
+    const size_t n = m->golden_in.size();
+    if (n == 0) return fail(AIDAX_ERR_STATE, "model carries no input_batch/output_batch");
+    // params forced to 0, gains forced to 1 (rt-neural-generic.cpp:903-915)
+    std::vector<float> X(n * static_cast<size_t>(m->input_size), 0.f);
+    for (size_t t = 0; t < n; ++t) X[t * m->input_size] = m->golden_in[t];
+    std::vector<float> y(n);
+    const int rc = aidax_model_forward(m, device_id, X.data(), y.data(), static_cast<uint32_t>(n), 1);
+    if (rc != AIDAX_OK) return rc;
+    int32_t errs = 0;
+    float worst = 0.f;
+    for (size_t t = 0; t < n; ++t) {
+        const float e = std::fabs(y[t] - m->golden_out[t]);
+        if (e > worst) worst = e;
+        if (static_cast<double>(e) > 1.0e-5) ++errs;          // TEST_MODEL_THR, rt-neural-generic.h:182
+    }
+    *n_errors = errs;
+    *max_error = worst;
+    if (out_opt) std::memcpy(out_opt, y.data(), n * sizeof(float));
+    return AIDAX_OK;
+}
+
+}  // extern "C"
