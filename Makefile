@@ -21,9 +21,9 @@ CXXFLAGS := -O3 -std=c++17 -fPIC -ffp-contract=off -fvisibility=hidden -Wall -We
 # GRU-24 pipeline 88.5 -> 84.1 us, cfg3 478 -> 464 us, nothing slower by more than noise)
 HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS) -fno-slp-vectorize
 
-HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_pool_model.cpp $(SRC)/aidax_pool_io.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_ir_stage.cpp $(SRC)/aidax_model_bank.cpp $(SRC)/aidax_rate.cpp
+HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_pool_model.cpp $(SRC)/aidax_pool_io.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_ir_stage.cpp $(SRC)/aidax_model_bank.cpp $(SRC)/aidax_rate.cpp $(SRC)/aidax_mix_book.cpp
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
-KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp_p1.o $(OBJDIR)/aidax_mfmalp_p2.o $(OBJDIR)/aidax_mfmalp_p3.o $(OBJDIR)/aidax_mfmalp_p4.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o
+KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp_p1.o $(OBJDIR)/aidax_mfmalp_p2.o $(OBJDIR)/aidax_mfmalp_p3.o $(OBJDIR)/aidax_mfmalp_p4.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o $(OBJDIR)/aidax_mix.o
 HDRS      := $(wildcard $(SRC)/*.h) include/aidax.h
 
 LV2SO := $(PKG)/lv2/rt-neural-generic.so
@@ -116,6 +116,14 @@ build/asan/asan_gate_harness: $(ASAN_GATE_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_GATE_SRCS) -o $@
 asan_gate: build/asan/asan_gate_harness
 
+# ... and the mix buses' host half (MixBook, aidax_mix_stage.h: the sends, their ramps, the CSR plan, the advance per pass and per prefix): tests/asan_mix_harness.cpp, tests/test_asan_mix.py
+ASAN_MIX_SRCS := tests/asan_mix_harness.cpp $(SRC)/aidax_mix_book.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
+build/asan/asan_mix_harness: $(ASAN_MIX_SRCS) $(HDRS) $(SRC)/json_min.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_MIX_SRCS) -o $@
+asan_mix: build/asan/asan_mix_harness
+
 oracle:
 	$(MAKE) -s -C oracle all
 	$(MAKE) -s -C oracle _ref
@@ -124,4 +132,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix

@@ -19,6 +19,9 @@ IR_SLOTS = 64                     # AIDAX_IR_SLOTS: bank slots per pool, besides
 IR_POOL, IR_NONE = -1, -2         # a stream's IR: the pool IR (default), none, or a bank slot 0 .. IR_SLOTS - 1
 MODEL_SLOTS = 64                  # AIDAX_MODEL_SLOTS: model-bank slots per pool, besides the pool model
 MODEL_POOL = -1                   # a stream's model: the pool model (default) or a bank slot 0 .. MODEL_SLOTS - 1
+SENDS = 4                         # AIDAX_SENDS: sends per stream into the pool's mix buses
+BUS_NONE = -1                     # AIDAX_BUS_NONE: a send that goes nowhere (the default)
+MAX_BUSES = 4096                  # AIDAX_MAX_BUSES
 _fp = C.POINTER(C.c_float)
 
 
@@ -244,6 +247,16 @@ def lib() -> C.CDLL:
         L.aidax_pool_set_gate.argtypes = [vp, i32, C.POINTER(GateParams)]
         L.aidax_pool_stream_gate.argtypes = [vp, u32, C.POINTER(GateParams), C.POINTER(C.c_int)]
         L.aidax_pool_read_gate.argtypes = [vp, u32, u32, C.POINTER(GateState)]
+    if hasattr(L, "aidax_pool_set_buses"):         # (... or from before the mix buses)
+        L.aidax_pool_set_buses.argtypes = [vp, u32]
+        L.aidax_pool_buses.argtypes = [vp]
+        L.aidax_pool_buses.restype = u32
+        L.aidax_pool_set_send.argtypes = [vp, i32, u32, i32, C.c_float, u32]
+        L.aidax_pool_stream_send.argtypes = [vp, u32, u32, C.POINTER(i32), _fp, _fp, C.POINTER(u32)]
+        L.aidax_mix_gain.argtypes = [C.c_float, C.c_float, u32, u32, _fp]
+        L.aidax_pool_read_buses.argtypes = [vp, u32, u32, _fp, C.c_size_t, C.POINTER(u32)]
+        L.aidax_pool_buses_device.argtypes = [vp, C.POINTER(vp)]
+        L.aidax_pool_process_buses.argtypes = [vp, _fp, _fp, u32]
     _lib = L
     return L
 
@@ -286,6 +299,13 @@ def gate_design(params: GateParams, samplerate: float) -> GateRec:
     out = GateRec()
     _check(lib().aidax_gate_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
     return out
+
+
+def mix_gain(g0: float, g1: float, ramp_frames: int, k: int) -> float:
+    """aidax_mix_gain: the gain of frame k of a send's ramp g0 -> g1 over ramp_frames frames (pure, host only)"""
+    out = C.c_float(0)
+    _check(lib().aidax_mix_gain(g0, g1, ramp_frames, k, C.byref(out)))
+    return out.value
 
 
 def load_ir_wav(path: str):
@@ -608,6 +628,50 @@ class Pool:
             count = self.n_streams - first
         out = np.zeros(max(count, 0), GATE_STATE_DTYPE)
         _check(lib().aidax_pool_read_gate(self.h, first, count, out.ctypes.data_as(C.POINTER(GateState))))
+        return out
+
+    def set_buses(self, n_buses: int):
+        """aidax_pool_set_buses: the pool's mix buses (the first call with a count allocates: a set-up side call; 0: off)"""
+        _check(lib().aidax_pool_set_buses(self.h, n_buses))
+
+    @property
+    def buses(self) -> int:
+        return int(lib().aidax_pool_buses(self.h))
+
+    def set_send(self, stream: int, send: int, bus: int, gain: float = 1.0, ramp_frames: int = 0):
+        """aidax_pool_set_send: send `send` (0 .. SENDS - 1) of `stream` (ALL_STREAMS: of every stream) goes to `bus` (BUS_NONE: nowhere)
+        and its gain moves to `gain` over the stream's next `ramp_frames` frames (0: a jump at the block boundary)"""
+        _check(lib().aidax_pool_set_send(self.h, stream, send, bus, gain, ramp_frames))
+
+    def stream_send(self, stream: int, send: int):
+        """aidax_pool_stream_send: (bus, gain_now, gain_target, frames_left) behind the last pass issued"""
+        b, now, target, left = C.c_int32(0), C.c_float(0), C.c_float(0), C.c_uint32(0)
+        _check(lib().aidax_pool_stream_send(self.h, stream, send, C.byref(b), C.byref(now), C.byref(target), C.byref(left)))
+        return b.value, now.value, target.value, left.value
+
+    def read_buses(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """aidax_pool_read_buses: rows `first` .. of the last mixed pass's bus block as [count][n_frames] (default: all from `first` on),
+        behind every pass issued so far"""
+        if count is None:
+            count = self.buses - first
+        out = np.zeros((max(count, 0), self.max_frames), np.float32)
+        n = C.c_uint32(0)
+        _check(lib().aidax_pool_read_buses(self.h, first, count, out.ctypes.data_as(_fp), out.size, C.byref(n)))
+        return np.ascontiguousarray(out.reshape(-1)[:count * n.value].reshape(count, n.value))
+
+    @property
+    def buses_device(self) -> int:
+        """aidax_pool_buses_device: the device address of the bus block ([buses][n_frames] of the last pass mixed)"""
+        d = C.c_void_p()
+        _check(lib().aidax_pool_buses_device(self.h, C.byref(d)))
+        return d.value
+
+    def process_buses(self, x: np.ndarray) -> np.ndarray:
+        """aidax_pool_process_buses: one blocking pass that downloads the buses only, [buses][n_frames]"""
+        x = _f32(x)
+        assert x.ndim == 2 and x.shape[0] == self.n_streams
+        out = np.empty((self.buses, x.shape[1]), np.float32)
+        _check(lib().aidax_pool_process_buses(self.h, x.ctypes.data_as(_fp), out.ctypes.data_as(_fp), x.shape[1]))
         return out
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):

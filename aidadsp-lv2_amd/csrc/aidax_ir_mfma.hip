@@ -268,17 +268,8 @@ __global__ __launch_bounds__(256) void k_ir_mix(IrBlendArgs a)
     const uint32_t s = e.stream & ~kIrBlendDry;
     if (s >= a.n_streams) return;
     const uint32_t k = e.k + a.k_off + t;                              // (<= 2^24 + 2^25 + the block: no wrap)
-    float w = e.m1;
-    double ud = 1.0 - static_cast<double>(e.m1);
-    if (k + 1u < e.ramp) {
-        const double step = static_cast<double>(e.m1) - static_cast<double>(e.m0);
-        const double run = step * static_cast<double>(k + 1u);
-        const double part = run / static_cast<double>(e.ramp);
-        const double wd = static_cast<double>(e.m0) + part;
-        w = static_cast<float>(wd);
-        ud = 1.0 - wd;
-    }
-    const float u = static_cast<float>(ud);
+    const double wd = ramp_value(e.m0, e.m1, e.ramp, k);               // (behind the ramp's end: m1 itself)
+    const float w = static_cast<float>(wd), u = static_cast<float>(1.0 - wd);
     const size_t at = static_cast<size_t>(s) * a.n_frames + t;
     if (w == 0.f) return;                                              // A's bits, as they are
     const float yb = (e.stream & kIrBlendDry) ? a.ring[static_cast<size_t>(s) * a.ring_row + ((a.pos + t) & a.mask)] : a.side[at];

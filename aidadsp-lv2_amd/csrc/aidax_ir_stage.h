@@ -97,14 +97,10 @@ struct IrPlan {
         return r.m1 == 0.f ? 0 : r.m1 == 1.f ? 1 : -1;
     }
     int eff_key(uint32_t s) const { return rest(s) == 1 ? key_b(s) : key(s); }       // a stream at rest: its effective IR
-    // the weight of ramp frame k (aidax_kernels.h: k_ir_mix computes the same, operation by operation)
+    // the weight of ramp frame k (ramp_value, aidax_kernels.h: the statement k_ir_mix computes with)
     static float weight(const Ramp& r, uint32_t k)
     {
-        if (k + 1u >= r.len) return r.m1;
-        const double step = static_cast<double>(r.m1) - static_cast<double>(r.m0);
-        const double run = step * static_cast<double>(k + 1u);
-        const double part = run / static_cast<double>(r.len);
-        return static_cast<float>(static_cast<double>(r.m0) + part);
+        return static_cast<float>(ramp_value(r.m0, r.m1, r.len, k));
     }
     // aidax_pool_set_ir_mix for one stream: a ramp from the weight of the last frame issued; between equal weights it has ended already
     void set_mix(uint32_t s, float mix, uint32_t len);

@@ -146,6 +146,17 @@ hipError_t launch_ir_fade(const IrFadeArgs& a, hipStream_t q);
 constexpr uint32_t kIrBlendDry = 0x80000000u;
 constexpr uint32_t kIrMaxRamp = 1u << 24;
 constexpr uint32_t kIrMaxRampOffset = 1u << 25;
+// Frame k of a ramp v0 -> v1 over `ramp` frames, in fp64 with every operation rounded on its own (the sources are built without
+// contraction): the ONE statement of it, shared by k_ir_mix and IrPlan::weight (the weight of B) and by k_mix, MixBook and
+// aidax_mix_gain (a send's gain). k + 1 must not wrap.
+__host__ __device__ inline double ramp_value(float v0, float v1, uint32_t ramp, uint32_t k)
+{
+    if (k + 1u >= ramp) return static_cast<double>(v1);
+    const double step = static_cast<double>(v1) - static_cast<double>(v0);
+    const double run = step * static_cast<double>(k + 1u);
+    const double part = run / static_cast<double>(ramp);
+    return static_cast<double>(v0) + part;
+}
 struct IrBlendEntry {
     uint32_t stream;
     float m0, m1;
@@ -207,6 +218,28 @@ struct GateState {
 static_assert(sizeof(GateRec) == 32 && sizeof(GateState) == 8, "a stream's gate record is 32 bytes, its state 8");
 hipError_t launch_gate(const float* in, float* out, const GateRec* rec, GateState* state, const StreamCtl* ctl, uint32_t n_active, uint32_t n_frames,
                        hipStream_t q);
+
+// The mix buses behind a pool's last stage (aidax_mix.hip, k_mix): one launch gathers the rows of the block a pass returns, [n_streams]
+// [n_frames], into the pool's bus block, [n_buses][n_frames], by the rule of include/aidax.h ("Mix buses"). The plan is CSR: the entries
+// of bus b are entries[bus_start[b] .. bus_start[b + 1] - 1], in ascending (stream, send) order; frame t of the pass is ramp frame
+// k = entry.k + k_off + t of the entry's ramp g0 -> g1 over `ramp` frames (ramp_value; entry.k <= 2^24, k_off <= 2^25: the host
+// saturates it). An entry at or beyond n_streams (a prefix pass) is left out. max_entries: the longest bus's entries, which picks the
+// one-wave form (every bus of at most kMixGroup entries), the four-wave form (at most 4 kMixGroup) or the sixteen-wave form.
+constexpr uint32_t kMixGroup = 32;             // entries of one group sum
+constexpr uint32_t kMixMaxRampOffset = 1u << 25;
+struct MixEntry {
+    uint32_t stream;
+    float g0, g1;
+    uint32_t ramp, k;
+};
+struct MixArgs {
+    const uint32_t* bus_start;   // [n_buses + 1]
+    const MixEntry* entries;
+    const float* y;              // the block the pass returns: only read
+    float* out;                  // [n_buses][n_frames]
+    uint32_t n_buses, n_streams, n_frames, k_off;
+};
+hipError_t launch_mix(const MixArgs& a, uint32_t max_entries, hipStream_t q);
 
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 

@@ -338,7 +338,9 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         // ... and a metered pass behind k_meter's reading of the block it returns: the same rule, so that a pass that has ended for the host
         // (aidax_pool_process has returned, the submit path's download may start) has also been metered
         const bool meter_on = n_frames != 0 && p->meter.on;
-        if (ir_on || meter_on) end = nullptr;                          // (the markers are not handed down: nullptr to launch)
+        // ... and a pass with the mix buses on behind k_mix: a pass that has ended for the host has been mixed
+        const bool mix_on = n_frames != 0 && p->mix.on;
+        if (ir_on || meter_on || mix_on) end = nullptr;                // (the markers are not handed down: nullptr to launch)
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) p->meter.launch_in(d_in, n_active, n_frames, s);  // (ahead of the pass: it may work in place)
         a.in = p->gate.before_pass(d_in, p->d_ctl, n_active, n_frames, s);      // the gated block, where a gate is on
@@ -346,6 +348,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
+        if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s);   // the buses: a gather over the block the pass returns
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
@@ -536,6 +539,75 @@ AIDAX_API int aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count
     if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
     if (!p->gate.enabled()) return fail(AIDAX_ERR_STATE, "no gate was ever enabled (aidax_pool_set_gate)");
     return p->on_own_stream([&]() -> int { p->gate.read(first, count, out, p->q); return AIDAX_OK; });
+}
+
+// The mix buses (aidax_mix_stage.h). The first aidax_pool_set_buses with a count is the set-up side's (it allocates); everything else
+// changes or reads host records of the audio side, and the reads of the bus block wait like aidax_pool_read_meters.
+AIDAX_API int aidax_pool_set_buses(aidax_pool* p, uint32_t n_buses)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (n_buses > AIDAX_MAX_BUSES) return fail(AIDAX_ERR_ARG, "more than 4096 buses");
+    MixStage& m = p->mix;
+    if (n_buses == 0 || m.enabled()) {
+        if (n_buses != 0 && n_buses != m.book.n_buses) return fail(AIDAX_ERR_STATE, "the pool's bus count is fixed once set");
+        m.on = n_buses != 0;                                // (off before any on: nothing to change)
+        return AIDAX_OK;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        m.enable(p->n_streams, p->max_frames, n_buses, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API uint32_t aidax_pool_buses(const aidax_pool* p) { return p ? p->mix.book.n_buses : 0; }
+
+AIDAX_API int aidax_pool_set_send(aidax_pool* p, int32_t stream, uint32_t send, int32_t bus, float gain, uint32_t ramp_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
+        return fail(AIDAX_ERR_ARG, "stream out of range");
+    if (send >= AIDAX_SENDS) return fail(AIDAX_ERR_ARG, "send out of range");
+    float checked = 0.f;
+    if (const int rc = aidax_mix_gain(0.f, gain, ramp_frames, 0, &checked)) return rc;      // (the gain and the ramp length, by the one rule)
+    MixBook& b = p->mix.book;
+    if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
+    if (bus != AIDAX_BUS_NONE && (bus < 0 || static_cast<uint32_t>(bus) >= b.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
+    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
+    for (uint32_t s = lo; s < hi; ++s) b.set(s, send, bus, gain, ramp_frames);
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_stream_send(const aidax_pool* p, uint32_t stream, uint32_t send, int32_t* bus, float* gain_now, float* gain_target, uint32_t* frames_left)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    if (send >= AIDAX_SENDS) return fail(AIDAX_ERR_ARG, "send out of range");
+    const MixBook::Send x = p->mix.enabled() ? p->mix.book.at(stream, send) : MixBook::Send{};
+    if (bus) *bus = x.bus;
+    if (gain_now) *gain_now = MixBook::gain_now(x);
+    if (gain_target) *gain_target = x.g1;
+    if (frames_left) *frames_left = MixBook::frames_left(x);
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_read_buses(aidax_pool* p, uint32_t first, uint32_t count, float* out, size_t cap_floats, uint32_t* n_frames)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    MixStage& m = p->mix;
+    if (!m.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
+    if (count == 0 || first > m.book.n_buses || count > m.book.n_buses - first) return fail(AIDAX_ERR_ARG, "bus range out of the pool's buses");
+    if (static_cast<size_t>(count) * m.last_frames > cap_floats) return fail(AIDAX_ERR_ARG, "buffer too small for the rows at the last pass's n_frames");
+    if (n_frames) *n_frames = m.last_frames;
+    return p->on_own_stream([&]() -> int { m.read(first, count, out, p->q); return AIDAX_OK; });
+}
+
+AIDAX_API int aidax_pool_buses_device(aidax_pool* p, float** d_ptr)
+{
+    if (!p || !d_ptr) return fail(AIDAX_ERR_ARG, "null argument");
+    if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
+    *d_ptr = p->mix.d_bus;
+    return AIDAX_OK;
 }
 
 AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode) { return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr); }

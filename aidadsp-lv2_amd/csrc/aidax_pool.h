@@ -12,6 +12,7 @@
 #include "aidax_ir_stage.h"
 #include "aidax_model_bank.h"
 #include "aidax_stream_stages.h"
+#include "aidax_mix_stage.h"
 
 namespace aidax {
 
@@ -217,6 +218,7 @@ struct aidax_pool {
     bool any_pass = false;           // the pool has issued a pass of n_frames > 0 (its first one has nothing for an IR change to fade from)
     MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
     GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
+    MixStage mix;                    // the mix buses behind the last stage (aidax_mix_stage.h; nothing until the first aidax_pool_set_buses with a count)
     // aidax_pool_register_host: page-locked ranges of the caller's memory (copies to and from them need no staging)
     struct HostRange { char* base; size_t bytes; };
     std::vector<HostRange> host_ranges;
@@ -394,6 +396,7 @@ struct aidax_pool {
         ir.release();
         bank.release();
         gate.release();
+        mix.release();
         meter.release();
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);

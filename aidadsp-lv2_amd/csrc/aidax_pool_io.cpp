@@ -140,6 +140,35 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
     });
 }
 
+// The blocking call of a host that wants the buses only: the plain staged path of aidax_pool_process up to the pass, which runs into the
+// pool's own device block; then the bus block alone comes down, through the mix stage's pinned staging.
+AIDAX_API int aidax_pool_process_buses(aidax_pool* p, const float* in, float* bus_out, uint32_t n_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (n_frames > p->max_frames) return fail(AIDAX_ERR_ARG, "n_frames exceeds the pool's max_frames");
+    if (n_frames != 0 && (!in || !bus_out)) return fail(AIDAX_ERR_ARG, "null buffer");
+    if (!p->mix.on) return fail(AIDAX_ERR_STATE, "the pool's buses are off (aidax_pool_set_buses)");
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        const size_t bytes = sizeof(float) * p->n_streams * static_cast<size_t>(n_frames);
+        const size_t bus_bytes = sizeof(float) * p->mix.book.n_buses * static_cast<size_t>(n_frames);
+        BlockingIo& io = p->io;
+        const bool staged = io.h_in != nullptr;
+        if (bytes && staged) std::memcpy(io.h_in, in, bytes);
+        if (bytes) HIP_TRY(hipMemcpyAsync(io.d_in, staged ? io.h_in : in, bytes, hipMemcpyHostToDevice, p->q));
+        const int rc = pool_process_prefix(p, io.d_in, io.d_out, n_frames, p->q, p->n_streams);
+        if (rc != AIDAX_OK) return rc;
+        if (bus_bytes) HIP_TRY(hipMemcpyAsync(p->mix.h_bus, p->mix.d_bus, bus_bytes, hipMemcpyDeviceToHost, p->q));
+        HIP_TRY(hipStreamSynchronize(p->q));
+        if (p->take_lp_fault()) {                           // the pass is wrong: silence, and k_mfma from the next one on
+            if (bus_bytes) std::memset(bus_out, 0, bus_bytes);
+            return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
+        }
+        if (bus_bytes) std::memcpy(bus_out, p->mix.h_bus, bus_bytes);
+        return AIDAX_OK;
+    });
+}
+
 // ---- the pipelined host-buffer path. One caller thread (the audio side); at most two blocks between submit and collect.
 static int pool_submit_impl(aidax_pool* p, const float* in, float* out, uint32_t n_frames)
 {

@@ -605,15 +605,103 @@ AIDAX_API int  aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_ga
 AIDAX_API int  aidax_pool_stream_gate(const aidax_pool* p, uint32_t stream, aidax_gate_params* out, int* on);
 AIDAX_API int  aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count, aidax_gate_state* out);
 
+/* Mix buses: the streams of a pool summed into output buses where the blocks are (k_mix, aidax_mix.hip): two amps of one player, a
+ * stereo pair from two cabinets, monitor mixes, the rooms of a service. Opt-in: a pool that never calls aidax_pool_set_buses, or has
+ * its buses off, allocates and launches exactly what it did before these calls existed, bit for bit, and the buses only read the
+ * stream block: a pool's audio does not depend on them.
+ * Buses, sends and the bus block:
+ *  - A pool has B buses (aidax_pool_set_buses) and every stream AIDAX_SENDS = 4 sends. A send is (bus, gain); bus is 0 .. B - 1 or
+ *    AIDAX_BUS_NONE, the default.
+ *  - While the buses are on, every pass of n_frames > 0 ends with one launch of k_mix on the pass's stream, behind the last stage (the
+ *    IR stage, the meters): after it the pool's BUS BLOCK, [B][n_frames] floats, rows dense at that pass's n_frames like the stream
+ *    block's, holds the mix of the stream block that pass returned — exactly what the caller gets for each stream, whatever produced
+ *    it: a disabled stream's row is its raw input, and that is what is summed. A pass of 0 frames touches nothing.
+ *  - There is ONE bus block per pool: it is that of the last pass issued, on every path (the blocking calls, aidax_pool_submit* /
+ *    collect, aidax_pool_process_device on the pool's or a caller's stream, passes under aidax_rate_*, whose blocks are the pool-rate
+ *    ones). A host that keeps blocks in flight reads the buses of the last one it submitted; bus blocks per block in flight do not exist.
+ * The sum, normative (tests/mixhelp.py restates it in numpy; the kernel agrees with it bit for bit):
+ *  - The entries of bus b are the sends on b in ascending (stream, send index) order. A pass over the first n_active streams only (the
+ *    hub's prefix pass) leaves the entries of the other streams out, and their ramps do not move.
+ *  - Frame t of entry e contributes the term (float)(g_e[t] * y[stream_e][t]), one fp32 multiplication. A term whose gain is exactly 0
+ *    is left out whatever y holds: a muted send of a stream that plays NaN or Inf does not poison its bus.
+ *  - The entries are cut into groups of 32 consecutive ones by position in the bus's list. A group sum starts at +0.0f and adds its
+ *    terms in order; the bus sample starts at +0.0f and adds the group sums in group order. Every addition is one fp32 operation,
+ *    rounded to nearest; there is no fma anywhere. A bus of at most 32 entries is therefore the plain sequential sum, and a bus without
+ *    entries is +0.0f.
+ *  - A bus with one send at gain 1 carries the stream's bits, except that -0.0 becomes +0.0 (0 + -0 = +0) and a NaN's payload is the
+ *    hardware's.
+ * Gain ramps, by the IR blend's convention ("IR blend" above):
+ *  - g_now is the fp32 gain of the send's last issued frame on its bus: 0 for a send that never played, and for one that has just been
+ *    moved to another bus.
+ *  - aidax_pool_set_send(.., bus, gain, R): if `bus` is the bus the send played on in the last pass issued, a ramp from g0 = g_now to
+ *    g1 = gain whose frame k = 0 is the stream's next issued frame. If it is another bus, the send moves at the block boundary and ramps
+ *    from g0 = 0: a new send fades in. AIDAX_BUS_NONE removes the send at the block boundary, and its g_now is 0 from then on: to
+ *    remove a send without a click, ramp it to 0 first. Every call is judged against the state behind the last pass issued: of
+ *    several calls between two passes the last one wins, from the same g0.
+ *  - Ramp frame k has, in fp64 with every operation rounded on its own,
+ *        k + 1 <  R:  g = (float)((double)g0 + ((double)g1 - (double)g0) * (double)(k + 1) / (double)R)
+ *        k + 1 >= R:  g = g1                                                                    (R = 0: a jump at the block boundary)
+ *    and k counts the stream's issued frames, not passes: a ramp does not depend on how the host cuts the stream into blocks.
+ *  - Ramp positions are host integers, advanced by n_frames for the streams of every pass issued while the buses are on (not by a pass
+ *    of 0 frames, not while they are off). aidax_pool_reset_stream keeps the sends and a running ramp goes on.
+ *  - Each pass is mixed with the sends in force when it was issued. The plan (which entries each bus has, and their ramps) reaches the
+ *    device from a ring of snapshots ahead of the pass that follows an aidax_pool_set_send; a pass without a changed send uploads
+ *    nothing, running ramps or not.
+ * aidax_pool_set_buses      SET-UP side. The first call with n_buses > 0 (1 .. AIDAX_MAX_BUSES) allocates everything the feature
+ *                           ever needs — the bus block [n_buses][max_frames], zeroed, the plan for n_streams x AIDAX_SENDS entries, its
+ *                           snapshots, the pinned staging of the reads — switches the buses on, and may wait. The count is fixed from
+ *                           then on: a later call with the same count switches them on again, one with another non-zero count is
+ *                           AIDAX_ERR_STATE. 0 switches them off and keeps sends, ramps and allocation (before any other call: nothing
+ *                           to do); while off, no pass is mixed, the bus block stays as it was and ramps do not advance. Later calls are
+ *                           host records of the audio side. AIDAX_ERR_ARG for a null pool or a count beyond AIDAX_MAX_BUSES.
+ * aidax_pool_buses          the bus count (0 until it is set, and for a null pool), on or off.
+ * aidax_pool_set_send       AUDIO thread, between passes: send `send` of `stream` (AIDAX_ALL_STREAMS: of every stream, each from its own
+ *                           g_now) as above. Host records only: no allocation, no free, no wait. AIDAX_ERR_ARG for a null pool, a
+ *                           stream, send or bus out of range, a gain that is not finite or beyond AIDAX_MIX_MAX_GAIN = 16 in magnitude,
+ *                           ramp_frames > 2^24 (a refused call changes nothing); AIDAX_ERR_STATE before aidax_pool_set_buses.
+ * aidax_pool_stream_send    the state behind the last pass issued, as the next aidax_pool_set_send would find it (any pointer may be
+ *                           NULL): the send's bus, g_now, the ramp's target, and the frames still to be issued until g_now is the
+ *                           target (0: the ramp has ended; a jump has 1 until a frame is issued). Before aidax_pool_set_buses:
+ *                           AIDAX_BUS_NONE, 0, 0, 0.
+ * aidax_mix_gain            pure, host only, any thread, like aidax_gate_design: the gain of ramp frame k by the formula above.
+ *                           AIDAX_ERR_ARG for a null pointer and for what aidax_pool_set_send refuses of g0, g1 and ramp_frames.
+ * aidax_pool_read_buses     AUDIO side, and it waits, like aidax_pool_read_meters: rows first .. first + count - 1 of the last mixed pass's
+ *                           bus block, count x n_frames floats dense at that pass's n_frames (returned in *n_frames, which may be NULL;
+ *                           0 and nothing copied before the first mixed pass), behind every pass issued so far on whatever stream.
+ *                           AIDAX_ERR_ARG for a null pool or buffer, count == 0, first + count > the bus count or cap_floats too small
+ *                           (nothing is changed), AIDAX_ERR_STATE before aidax_pool_set_buses.
+ * aidax_pool_buses_device   the device address of the bus block, for hosts of aidax_pool_process_device: valid from
+ *                           aidax_pool_set_buses until the pool's end, written on the stream each pass ran on (a reader on another
+ *                           stream orders itself behind that pass, as it does for the stream block).
+ * aidax_pool_process_buses  the blocking host call that downloads only the buses: uploads `in` through the pool's staging as
+ *                           aidax_pool_process does for blocks beyond its in-place path, runs the pass into the pool's own device
+ *                           block, downloads [B][n_frames] into bus_out through pinned staging and waits for the pool's stream (no
+ *                           in-place host memory, no completion word). n_frames == 0 is the pre-run and writes nothing.
+ *                           AIDAX_ERR_STATE while the buses are off or were never set.
+ * Not covered: hub seats (aidax_hub never sets buses on its pool) and so the LV2 shell, meters on the buses, a bus block per block in
+ * flight, a pan law (the host sets two gains), more than four sends per stream. */
+#define AIDAX_SENDS 4
+#define AIDAX_BUS_NONE (-1)
+#define AIDAX_MAX_BUSES 4096
+#define AIDAX_MIX_MAX_GAIN 16.0f
+AIDAX_API int      aidax_pool_set_buses(aidax_pool* p, uint32_t n_buses);
+AIDAX_API uint32_t aidax_pool_buses(const aidax_pool* p);
+AIDAX_API int      aidax_pool_set_send(aidax_pool* p, int32_t stream, uint32_t send, int32_t bus, float gain, uint32_t ramp_frames);
+AIDAX_API int      aidax_pool_stream_send(const aidax_pool* p, uint32_t stream, uint32_t send, int32_t* bus, float* gain_now, float* gain_target, uint32_t* frames_left);
+AIDAX_API int      aidax_mix_gain(float g0, float g1, uint32_t ramp_frames, uint32_t k, float* gain);
+AIDAX_API int      aidax_pool_read_buses(aidax_pool* p, uint32_t first, uint32_t count, float* out, size_t cap_floats, uint32_t* n_frames);
+AIDAX_API int      aidax_pool_buses_device(aidax_pool* p, float** d_ptr);
+AIDAX_API int      aidax_pool_process_buses(aidax_pool* p, const float* in, float* bus_out, uint32_t n_frames);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side); aidax_gate_design is pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side); aidax_gate_design and aidax_mix_gain are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) and changed gate records (after a set_gate), go
+ * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses wait for the GPU (for the stream that carries the pass, never for the
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate) and a changed mix plan (after a set_send), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
