@@ -49,21 +49,21 @@ bool mfma_lp_fused_serves(const MfmaDesc& d, uint32_t max_frames);       // the 
 size_t mfma_lp_ring_bytes(const MfmaDesc& d, uint32_t n_streams);
 size_t mfma_lp_counter_bytes(const MfmaDesc& d, uint32_t n_streams);
 // `fault`: device view of a word in pinned host memory that a workgroup bumps when a hand-over wait timed out
-// k_gru_gm (aidax_mfmalp.hip): one-layer GRU on gate-major tiles, the whole run() in one launch (MODE_CHAIN, n_frames > 0)
+// k_gru_gm (aidax_tick.hip): one-layer GRU on gate-major tiles, the whole run() in one launch (MODE_CHAIN, n_frames > 0)
 bool gru_gm_serves(const MfmaDesc& d);
 size_t gru_gm_lds_bytes(const MfmaDesc& d, uint32_t n_frames);
 hipError_t launch_gru_gm_kernel(const LaunchArgs& a, const MfmaDesc& d, hipStream_t stream);
-// k_gru_gs (aidax_mfmalp.hip): k_gru_gm with the recurrent product as bf16 MFMAs of operands split exactly into three bf16
+// k_gru_gs (aidax_tick.hip): k_gru_gm with the recurrent product as bf16 MFMAs of operands split exactly into three bf16
 // terms; n_products: 6 (to fp32 rounding) or 9 (every term product)
 bool gru_gs_serves(const MfmaDesc& d);
 size_t gru_gs_lds_bytes(const MfmaDesc& d, uint32_t n_frames);
 hipError_t launch_gru_gs_kernel(const LaunchArgs& a, const MfmaDesc& d, int n_products, hipStream_t stream);
-// k_lstm_gs (aidax_mfmalp.hip): the same structure for one-layer LSTMs of 40 (run as 48) / 64 units (pack_mfma's LSTM record at gs_off)
+// k_lstm_gs (aidax_tick.hip): the same structure for one-layer LSTMs of 40 (run as 48) / 64 units (pack_mfma's LSTM record at gs_off)
 bool lstm_gs_serves(const MfmaDesc& d);
 size_t lstm_gs_lds_bytes(const MfmaDesc& d, uint32_t n_frames);
 hipError_t launch_lstm_gs_kernel(const LaunchArgs& a, const MfmaDesc& d, int n_products, hipStream_t stream);
 hipError_t launch_mfma_lp_kernel(const LaunchArgs& a, const MfmaDesc& d, float* ring, uint32_t* counters, uint32_t* fault, hipStream_t stream, bool fused = false);
-// k_mfma_ls (aidax_mfmalp.hip): k_mfma_lp's stacked models with the contractions as bf16 MFMAs of operands split exactly into
+// k_mfma_ls (aidax_mfmals.hip): k_mfma_lp's stacked models with the contractions as bf16 MFMAs of operands split exactly into
 // three bf16 terms (n_products: 6 or 9); same ring protocol, its own ring geometry (a frame is the h fragments)
 bool mfma_ls_serves(const MfmaDesc& d);
 size_t mfma_ls_lds_bytes(const MfmaDesc& d, uint32_t n_frames, bool fused = false);

@@ -39,7 +39,7 @@ struct RelaxedFlag {
 // k_mfma_lp needs every workgroup of its grid resident at once, which the pool can promise only for ONE grid on the
 // device: one pool per device holds the right to use the kernel (a pool's staged model shares its own pool's hold), the
 // others serve their stacked models with k_mfma. Process-wide; another process on the same GPU is beyond its reach
-// and ends in a reported give-up (aidax_mfmalp.hip).
+// and ends in a reported give-up (aidax_mfmalp.hip, aidax_mfmals.h).
 struct LpGate {
     std::mutex mu;
     // `off`: the owner's "I have stopped using the kernel" flag (a pool whose hand-over gave up serves its model with

@@ -2,7 +2,7 @@
 
 The sigmoid and tanh of the recurrent kernels exist in many hand-written copies (aidax_device.h: fast_sigmoid, sigmoid_pre,
 tanh_rat with its clamp at 7.9, tanh_exp / tanh_exp_pre, and the tanh-form sigmoid 0.5 tanh_rat(z / 2) + 0.5 of the one-wave
-LSTM's shared lane maps and of k_lstm_q4; aidax_mfmalp.hip deals the same operations out by hand between MFMA groups), and the
+LSTM's shared lane maps and of k_lstm_q4; aidax_tick.hip and aidax_mfmals.h deal the same operations out by hand between MFMA groups), and the
 random models of the parity tests keep every pre-activation within about +-3. Here the diagonal probe models of tests/probes.py
 (U = 0: each unit its own (w, b) per gate, an fp64 closed form — established as a reference, together with its conditioning, by
 tests/test_probes_reference.py) drive them to exactly 0 and 1, through the overflow of exp (|z| up to 200), down to |x| = 1e-6

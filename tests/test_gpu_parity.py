@@ -1429,7 +1429,7 @@ def test_gate_major_gru_kernel_ragged_blocks_controls_and_state_bits(hidden, isz
     ("gru", 40, 2, 1),       # 40 units run zero-padded to 48: the second k-step's upper half stays zero
 ])
 def test_split_stack_geometries_match_the_oracle(kind, hidden, n_rnn, isz, tmp_path):
-    """k_mfma_ls in every geometry ls_geo hands out (aidax_mfmalp.hip): ragged blocks incl. 0 and 1, 40 streams (the last group
+    """k_mfma_ls in every geometry ls_geo hands out (aidax_mfmals.h): ragged blocks incl. 0 and 1, 40 streams (the last group
     ragged), PARAM moves, against per-stream oracle plugins; the one-launch form on a 256-frame pool and the three-launch form
     on a 1024-frame pool."""
     path, spec = _model_file(tmp_path, f"ls_{kind}{hidden}x{n_rnn}", kind=kind, hidden=hidden, input_size=isz, seed=900 + hidden + n_rnn, n_rnn=n_rnn,
@@ -1467,7 +1467,7 @@ def test_split_stack_geometries_match_the_oracle(kind, hidden, n_rnn, isz, tmp_p
     ("lstm", 96, 1),       # wider than the reference's table
 ])
 def test_lone_layer_on_the_split_kernel_matches_the_oracle(kind, hidden, isz, tmp_path, monkeypatch):
-    """k_mfma_ls1 (aidax_mfmalp.hip): ONE layer on k_mfma_ls's body — first and last role at once, no ring. Forced (AIDAX_KERNEL=mfma,
+    """k_mfma_ls1 (aidax_mfmals.h): ONE layer on k_mfma_ls's body — first and last role at once, no ring. Forced (AIDAX_KERNEL=mfma,
     AIDAX_LS1=1) so that every geometry runs whatever the pool's table says: ragged blocks incl. 0 and 1, 40 streams (the last
     group ragged), PARAM moves, in_skip, against per-stream oracle plugins; the one-launch form on a 256-frame pool and the
     three-launch form on a 1024-frame pool."""
@@ -1544,7 +1544,7 @@ def test_gru80_on_the_split_gate_major_kernel_with_two_helper_waves(isz, nprod, 
 
 @pytest.mark.parametrize("hidden,isz,nprod", [(64, 1, 6), (64, 3, 9), (40, 2, 6), (80, 2, 6)])
 def test_one_layer_lstm_on_the_unit_major_split_kernel_matches_the_oracle(hidden, isz, nprod, tmp_path, monkeypatch):
-    """k_lstm_gs (aidax_mfmalp.hip): k_gru_gs's structure for one-layer LSTMs of 40 (run as 48) / 64 units — unit-major tiles, one
+    """k_lstm_gs (aidax_tick.hip): k_gru_gs's structure for one-layer LSTMs of 40 (run as 48) / 64 units — unit-major tiles, one
     main wave per 16 units, the DSP chain on helper waves, the whole run() in the launch. Forced (AIDAX_KERNEL=mfma, AIDAX_LSTM_GS=1):
     ragged blocks incl. 0 and 1 and blocks longer than a staging chunk, 40 streams (the last group ragged), PARAM moves, in_skip,
     EQ in circuit, against per-stream oracle plugins; copies of a stream stay bitwise identical."""
