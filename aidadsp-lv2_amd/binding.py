@@ -22,6 +22,8 @@ MODEL_POOL = -1                   # a stream's model: the pool model (default) o
 SENDS = 4                         # AIDAX_SENDS: sends per stream into the pool's mix buses
 BUS_NONE = -1                     # AIDAX_BUS_NONE: a send that goes nowhere (the default)
 MAX_BUSES = 4096                  # AIDAX_MAX_BUSES
+ALL_BUSES = -1                    # AIDAX_ALL_BUSES: every bus's limiter
+BUS_LOOKAHEAD_MAX, BUS_HOLD_MAX = 512, 4096      # AIDAX_BUS_LOOKAHEAD_MAX, AIDAX_BUS_HOLD_MAX: frames
 _fp = C.POINTER(C.c_float)
 
 
@@ -82,6 +84,26 @@ class GateState(C.Structure):
 
 
 GATE_STATE_DTYPE = np.dtype([("hold_left", "<u4"), ("atten", "<u4")])
+
+
+class BusLimitParams(C.Structure):
+    """aidax_bus_limit_params: a bus limiter as a user sets it (the ceiling in dB, times in ms)"""
+    _fields_ = [("ceiling_db", C.c_float), ("lookahead_ms", C.c_float), ("hold_ms", C.c_float)]
+
+
+class BusLimitRec(C.Structure):
+    """aidax_bus_limit_rec: the record k_bus_limit reads (16 bytes), what aidax_bus_limit_design makes of BusLimitParams at a sample rate"""
+    _fields_ = [("ceiling", C.c_float), ("lookahead", C.c_uint32), ("hold", C.c_uint32), ("on", C.c_uint32)]
+
+
+class BusMeter(C.Structure):
+    """aidax_bus_meter: one bus's record (48 bytes)"""
+    _fields_ = [("frames", C.c_uint64), ("passes", C.c_uint64), ("in_nonfinite", C.c_uint64), ("limited", C.c_uint64),
+                ("in_peak", C.c_float), ("out_peak", C.c_float), ("min_gain", C.c_float), ("reserved", C.c_float)]
+
+
+BUS_METER_DTYPE = np.dtype([("frames", "<u8"), ("passes", "<u8"), ("in_nonfinite", "<u8"), ("limited", "<u8"),
+                            ("in_peak", "<f4"), ("out_peak", "<f4"), ("min_gain", "<f4"), ("reserved", "<f4")])
 
 
 def lib_path() -> str:
@@ -257,6 +279,13 @@ def lib() -> C.CDLL:
         L.aidax_pool_read_buses.argtypes = [vp, u32, u32, _fp, C.c_size_t, C.POINTER(u32)]
         L.aidax_pool_buses_device.argtypes = [vp, C.POINTER(vp)]
         L.aidax_pool_process_buses.argtypes = [vp, _fp, _fp, u32]
+    if hasattr(L, "aidax_pool_set_bus_limiting"):  # (... or from before the bus limiters)
+        L.aidax_bus_limit_design.argtypes = [C.POINTER(BusLimitParams), C.c_double, C.POINTER(BusLimitRec)]
+        L.aidax_pool_set_bus_limiting.argtypes = [vp, C.c_int, u32, u32]
+        L.aidax_pool_bus_limiting.argtypes = [vp]
+        L.aidax_pool_set_bus_limiter.argtypes = [vp, i32, C.POINTER(BusLimitParams)]
+        L.aidax_pool_bus_limiter.argtypes = [vp, u32, C.POINTER(BusLimitParams), C.POINTER(C.c_int), C.POINTER(u32)]
+        L.aidax_pool_read_bus_meters.argtypes = [vp, u32, u32, C.POINTER(BusMeter), C.c_int]
     _lib = L
     return L
 
@@ -298,6 +327,13 @@ def gate_design(params: GateParams, samplerate: float) -> GateRec:
     """aidax_gate_design: the record of `params` at `samplerate` (pure, host only)"""
     out = GateRec()
     _check(lib().aidax_gate_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
+    return out
+
+
+def bus_limit_design(params: BusLimitParams, samplerate: float) -> BusLimitRec:
+    """aidax_bus_limit_design: the record of `params` at `samplerate` (pure, host only)"""
+    out = BusLimitRec()
+    _check(lib().aidax_bus_limit_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
     return out
 
 
@@ -672,6 +708,34 @@ class Pool:
         assert x.ndim == 2 and x.shape[0] == self.n_streams
         out = np.empty((self.buses, x.shape[1]), np.float32)
         _check(lib().aidax_pool_process_buses(self.h, x.ctypes.data_as(_fp), out.ctypes.data_as(_fp), x.shape[1]))
+        return out
+
+    def set_bus_limiting(self, on: bool, max_lookahead_frames: int = BUS_LOOKAHEAD_MAX, max_hold_frames: int = BUS_HOLD_MAX):
+        """aidax_pool_set_bus_limiting: the limiter and meter stage behind the buses on or off (the first enabling call allocates and
+        fixes the capacities: a set-up side call)"""
+        _check(lib().aidax_pool_set_bus_limiting(self.h, 1 if on else 0, max_lookahead_frames, max_hold_frames))
+
+    @property
+    def bus_limiting(self) -> bool:
+        return bool(lib().aidax_pool_bus_limiting(self.h))
+
+    def set_bus_limiter(self, params: Optional[BusLimitParams], bus: int = ALL_BUSES):
+        """aidax_pool_set_bus_limiter: the bus's (default: every bus's) limiter from the next pass on, None: off"""
+        _check(lib().aidax_pool_set_bus_limiter(self.h, bus, C.byref(params) if params is not None else None))
+
+    def bus_limiter(self, bus: int):
+        """aidax_pool_bus_limiter: (the bus's BusLimitParams as last set, whether its limiter is on, its latency in frames)"""
+        out, on, latency = BusLimitParams(), C.c_int(0), C.c_uint32(0)
+        _check(lib().aidax_pool_bus_limiter(self.h, bus, C.byref(out), C.byref(on), C.byref(latency)))
+        return out, bool(on.value), latency.value
+
+    def read_bus_meters(self, first: int = 0, count: Optional[int] = None, clear: bool = False) -> np.ndarray:
+        """aidax_pool_read_bus_meters: the records of `count` buses from `first` (default: all from `first` on) as a structured array
+        with aidax_bus_meter's field names, behind every pass issued so far; clear resets exactly those records behind the copy"""
+        if count is None:
+            count = self.buses - first
+        out = np.zeros(max(count, 0), BUS_METER_DTYPE)
+        _check(lib().aidax_pool_read_bus_meters(self.h, first, count, out.ctypes.data_as(C.POINTER(BusMeter)), 1 if clear else 0))
         return out
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):

@@ -271,4 +271,28 @@ AIDAX_API int aidax_gate_design(const aidax_gate_params* params, double samplera
     return AIDAX_OK;
 }
 
+// The record of a bus limiter (include/aidax.h, "Bus limiters"), in fp64: the ceiling as a level, the two times as frames.
+AIDAX_API int aidax_bus_limit_design(const aidax_bus_limit_params* params, double samplerate, aidax_bus_limit_rec* out)
+{
+    using aidax::fail;
+    if (!params || !out) return fail(AIDAX_ERR_ARG, "bus_limit_design: null argument");
+    const aidax_bus_limit_params& l = *params;
+    if (!std::isfinite(l.ceiling_db) || !std::isfinite(l.lookahead_ms) || !std::isfinite(l.hold_ms)) return fail(AIDAX_ERR_ARG, "bus_limit_design: every parameter must be finite");
+    if (!(samplerate > 0.0) || !std::isfinite(samplerate)) return fail(AIDAX_ERR_ARG, "bus_limit_design: samplerate must be positive");
+    if (!(l.ceiling_db >= -60.f && l.ceiling_db <= 12.f)) return fail(AIDAX_ERR_ARG, "bus_limit_design: ceiling_db must be in [-60, 12]");
+    if (l.lookahead_ms < 0.f || l.hold_ms < 0.f) return fail(AIDAX_ERR_ARG, "bus_limit_design: lookahead_ms and hold_ms must not be negative");
+    const double look = static_cast<double>(l.lookahead_ms) * samplerate / 1000.0, hold = static_cast<double>(l.hold_ms) * samplerate / 1000.0;
+    // (compared as fp64 ahead of the rounding: a time of any size is refused, never wrapped)
+    if (!(look < AIDAX_BUS_LOOKAHEAD_MAX + 1.0) || std::llround(look) < 1 || std::llround(look) > AIDAX_BUS_LOOKAHEAD_MAX)
+        return fail(AIDAX_ERR_ARG, "bus_limit_design: the look-ahead must be 1 .. 512 frames");
+    if (!(hold < AIDAX_BUS_HOLD_MAX + 1.0) || std::llround(hold) > AIDAX_BUS_HOLD_MAX) return fail(AIDAX_ERR_ARG, "bus_limit_design: the hold must be at most 4096 frames");
+    aidax_bus_limit_rec r;
+    r.ceiling = static_cast<float>(std::pow(10.0, static_cast<double>(l.ceiling_db) / 20.0));
+    r.lookahead = static_cast<uint32_t>(std::llround(look));
+    r.hold = static_cast<uint32_t>(std::llround(hold));
+    r.on = 1u;
+    *out = r;
+    return AIDAX_OK;
+}
+
 }  // extern "C"

@@ -241,6 +241,33 @@ struct MixArgs {
 };
 hipError_t launch_mix(const MixArgs& a, uint32_t max_entries, hipStream_t q);
 
+// The bus limiters behind k_mix (aidax_bus_limit.hip, k_bus_limit): one launch turns the raw bus block k_mix wrote, [n_buses][n_frames],
+// into the pool's bus block of the same shape by the per-frame rule of include/aidax.h ("Bus limiters"), a workgroup per bus. LimitRec is
+// aidax_bus_limit_rec and BusMeterRec aidax_bus_meter, field for field. Each bus has a row of mask + 1 floats in `ring`, the sanitised
+// samples of its past: absolute frame k lives in slot k & mask, `pos` is the absolute frame (modulo 2^32) of the pass's first one, and the
+// launch appends the pass's frames. The row holds at least 2 L + H - 1 frames of history next to the longest pass, for every record the
+// host admits (lookahead 1 .. kLimitMaxLookahead, hold 0 .. kLimitMaxHold). A bus whose record is off gets the raw bits.
+constexpr uint32_t kLimitUnit = 1u << 22;      // U: the gain position of "no reduction"
+constexpr uint32_t kLimitMaxLookahead = 512, kLimitMaxHold = 4096;
+struct LimitRec {
+    float ceiling;
+    uint32_t lookahead, hold, on;
+};
+struct BusMeterRec {
+    uint64_t frames, passes, in_nonfinite, limited;
+    float in_peak, out_peak, min_gain, reserved;
+};
+static_assert(sizeof(LimitRec) == 16 && sizeof(BusMeterRec) == 48, "a bus's limiter record is 16 bytes, its meter record 48");
+struct BusLimitArgs {
+    const float* raw;            // [n_buses][n_frames]: what k_mix wrote, only read
+    float* out;                  // [n_buses][n_frames]
+    float* ring;                 // [n_buses][mask + 1]
+    const LimitRec* rec;         // [n_buses]
+    BusMeterRec* meter;          // [n_buses]
+    uint32_t n_buses, n_frames, mask, pos;
+};
+hipError_t launch_bus_limit(const BusLimitArgs& a, hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

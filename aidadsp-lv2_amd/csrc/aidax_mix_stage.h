@@ -96,8 +96,9 @@ struct MixStage {
         *this = std::move(fresh);
     }
     // Behind the last stage of a pass of n_frames > 0: the plan, if a send has changed since the last one went up, then k_mix over the
-    // block the pass returns, then the sends move on (a pass that fails on its way here leaves them where they were)
-    void after_pass(const float* d_out, uint32_t n_active, uint32_t n_frames, hipStream_t s)
+    // block the pass returns, then the sends move on (a pass that fails on its way here leaves them where they were). `d_raw`: where k_mix
+    // writes instead of the bus block while the bus limiters are on (aidax_limit_stage.h: k_bus_limit then writes the bus block)
+    void after_pass(const float* d_out, uint32_t n_active, uint32_t n_frames, hipStream_t s, float* d_raw = nullptr)
     {
         if (book.dirty) {
             book.rebuild();
@@ -108,7 +109,7 @@ struct MixStage {
         a.bus_start = reinterpret_cast<const uint32_t*>(d_plan);
         a.entries = reinterpret_cast<const MixEntry*>(d_plan + book.entries_off());
         a.y = d_out;
-        a.out = d_bus;
+        a.out = d_raw ? d_raw : d_bus;
         a.n_buses = book.n_buses; a.n_streams = n_active; a.n_frames = n_frames; a.k_off = book.since_build;
         HIP_TRY(launch_mix(a, book.max_entries, s));
         book.advance(n_active, n_frames);

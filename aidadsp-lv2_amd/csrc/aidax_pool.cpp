@@ -348,7 +348,9 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
-        if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s);   // the buses: a gather over the block the pass returns
+        const bool limit_on = mix_on && p->limit.on;                   // the bus limiters: k_mix writes their raw side block, k_bus_limit the bus block
+        if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s, limit_on ? p->limit.d_raw : nullptr);      // the buses: a gather over the block the pass returns
+        if (limit_on) p->limit.after_mix(p->mix.d_bus, n_frames, s);
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
@@ -610,10 +612,79 @@ AIDAX_API int aidax_pool_buses_device(aidax_pool* p, float** d_ptr)
     return AIDAX_OK;
 }
 
+// The bus limiters and bus meters (aidax_limit_stage.h). The first aidax_pool_set_bus_limiting with on != 0 is the set-up side's (it
+// allocates); everything else changes or reads host records of the audio side, and the read of the meters waits like aidax_pool_read_meters.
+AIDAX_API int aidax_pool_set_bus_limiting(aidax_pool* p, int on, uint32_t max_lookahead_frames, uint32_t max_hold_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
+    LimitStage& l = p->limit;
+    if (!on) {
+        l.on = false;                                       // (off before any on: nothing to change)
+        return AIDAX_OK;
+    }
+    if (max_lookahead_frames < 1u || max_lookahead_frames > AIDAX_BUS_LOOKAHEAD_MAX || max_hold_frames > AIDAX_BUS_HOLD_MAX)
+        return fail(AIDAX_ERR_ARG, "the look-ahead capacity is 1 .. 512 frames, the hold capacity at most 4096");
+    if (l.enabled()) {
+        if (max_lookahead_frames != l.book.max_lookahead || max_hold_frames != l.book.max_hold) return fail(AIDAX_ERR_STATE, "the bus limiters' capacities are fixed once set");
+        l.on = true;
+        return AIDAX_OK;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        l.enable(p->mix.book.n_buses, p->max_frames, max_lookahead_frames, max_hold_frames, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_bus_limiting(const aidax_pool* p) { return p && p->limit.on ? 1 : 0; }
+
+AIDAX_API int aidax_pool_set_bus_limiter(aidax_pool* p, int32_t bus, const aidax_bus_limit_params* params)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    LimitStage& l = p->limit;
+    if (!l.enabled()) return fail(AIDAX_ERR_STATE, "bus limiting was never enabled (aidax_pool_set_bus_limiting)");
+    if (bus != AIDAX_ALL_BUSES && (bus < 0 || static_cast<uint32_t>(bus) >= l.book.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
+    aidax_bus_limit_rec designed{};
+    if (params)
+        if (const int rc = aidax_bus_limit_design(params, aidax_pool_samplerate(p), &designed)) return rc;
+    const uint32_t lo = bus == AIDAX_ALL_BUSES ? 0u : static_cast<uint32_t>(bus), hi = bus == AIDAX_ALL_BUSES ? l.book.n_buses : lo + 1u;
+    if (!l.book.set(lo, hi, params ? &designed : nullptr, params)) return fail(AIDAX_ERR_ARG, "the limiter's look-ahead or hold exceeds the capacities of aidax_pool_set_bus_limiting");
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_bus_limiter(const aidax_pool* p, uint32_t bus, aidax_bus_limit_params* out, int* on, uint32_t* latency_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (bus >= p->mix.book.n_buses) return fail(AIDAX_ERR_ARG, "bus out of range");
+    const LimitStage& l = p->limit;
+    const bool is_on = l.enabled() && l.book.h_rec[bus].on;
+    if (out) *out = is_on ? l.book.params[bus] : aidax_bus_limit_params{};
+    if (on) *on = is_on ? 1 : 0;
+    if (latency_frames) *latency_frames = l.enabled() ? l.book.latency(bus) : 0u;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_read_bus_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_bus_meter* out, int clear)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    LimitStage& l = p->limit;
+    if (!l.enabled()) return fail(AIDAX_ERR_STATE, "bus limiting was never enabled (aidax_pool_set_bus_limiting)");
+    if (count == 0 || first > l.book.n_buses || count > l.book.n_buses - first) return fail(AIDAX_ERR_ARG, "bus range out of the pool's buses");
+    return p->on_own_stream([&]() -> int { l.read(first, count, out, clear != 0, p->q); return AIDAX_OK; });
+}
+
 AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode) { return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr); }
 
 #ifdef AIDAX_TEST_HOOKS
 AIDAX_API int aidax_test_hip_calls(char* buf, uint32_t cap) { return read_hip_calls(buf, cap); }      // (test build only, not in include/aidax.h)
+// (test build only: aidax_pool_process_device over the first n_active streams — the hub's prefix pass, which no public call reaches on a pool
+// with buses: tests/test_gpu_bus_limit.py)
+AIDAX_API int aidax_test_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    return aidax::pool_process_prefix(p, d_in, d_out, n_frames, hip_stream, n_active);
+}
 // (test build only: one stream's whole record as the kernels left it — `pending`, and in `pad` the length of the post cascade that the last
 // k_*_pipe4 launch ran for the stream, 1 where it skipped a transparent EQ: tests/test_gpu_eq_transparent.py)
 AIDAX_API int aidax_test_stream_state(aidax_pool* p, uint32_t stream, void* out, uint32_t cap)

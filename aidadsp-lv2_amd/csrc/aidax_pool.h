@@ -13,6 +13,7 @@
 #include "aidax_model_bank.h"
 #include "aidax_stream_stages.h"
 #include "aidax_mix_stage.h"
+#include "aidax_limit_stage.h"
 
 namespace aidax {
 
@@ -219,6 +220,7 @@ struct aidax_pool {
     MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
     GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
     MixStage mix;                    // the mix buses behind the last stage (aidax_mix_stage.h; nothing until the first aidax_pool_set_buses with a count)
+    LimitStage limit;                // the bus limiters and bus meters behind k_mix (aidax_limit_stage.h; nothing until the first aidax_pool_set_bus_limiting(1, ..))
     // aidax_pool_register_host: page-locked ranges of the caller's memory (copies to and from them need no staging)
     struct HostRange { char* base; size_t bytes; };
     std::vector<HostRange> host_ranges;
@@ -397,6 +399,7 @@ struct aidax_pool {
         bank.release();
         gate.release();
         mix.release();
+        limit.release();
         meter.release();
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);

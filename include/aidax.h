@@ -678,7 +678,7 @@ AIDAX_API int  aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t coun
  *                           block, downloads [B][n_frames] into bus_out through pinned staging and waits for the pool's stream (no
  *                           in-place host memory, no completion word). n_frames == 0 is the pre-run and writes nothing.
  *                           AIDAX_ERR_STATE while the buses are off or were never set.
- * Not covered: hub seats (aidax_hub never sets buses on its pool) and so the LV2 shell, meters on the buses, a bus block per block in
+ * Not covered: hub seats (aidax_hub never sets buses on its pool) and so the LV2 shell, a bus block per block in
  * flight, a pan law (the host sets two gains), more than four sends per stream. */
 #define AIDAX_SENDS 4
 #define AIDAX_BUS_NONE (-1)
@@ -693,15 +693,92 @@ AIDAX_API int      aidax_pool_read_buses(aidax_pool* p, uint32_t first, uint32_t
 AIDAX_API int      aidax_pool_buses_device(aidax_pool* p, float** d_ptr);
 AIDAX_API int      aidax_pool_process_buses(aidax_pool* p, const float* in, float* bus_out, uint32_t n_frames);
 
+/* Bus limiters: the master section of the mix buses — a look-ahead brick-wall limiter and a meter on every bus, computed where the bus
+ * block is (k_bus_limit, aidax_bus_limit.hip). Opt-in: a pool that never calls aidax_pool_set_bus_limiting, or has the stage off,
+ * allocates and launches exactly what it did before these calls existed, bit for bit. While the stage and the buses are on, k_mix of
+ * every pass of n_frames > 0 writes a raw side block and one launch of k_bus_limit, behind it on the pass's stream, writes the pool's
+ * bus block: aidax_pool_read_buses, aidax_pool_buses_device and aidax_pool_process_buses then return the LIMITED block.
+ * The rule, normative (tests/limithelp.py restates it in numpy; the kernel agrees with it bit for bit). Each bus has a record
+ * (aidax_bus_limit_rec): C the ceiling (linear, fp32, > 0), L the look-ahead in frames (1 .. AIDAX_BUS_LOOKAHEAD_MAX), H the hold in
+ * frames (0 .. AIDAX_BUS_HOLD_MAX). U = 2^22, W = L + 1 + H. x[j] is the SANITISED raw bus sample of absolute frame j: what k_mix
+ * produced, with NaN and +-Inf replaced by +0.0f. Frames are counted from the stage's first enabling, and x[j] = 0 for j < 0.
+ *     q[j] = U                                               if |x[j]| <= C
+ *          = floor(((double)C / (double)|x[j]|) * 2^22)      otherwise (one rounded fp64 division, an exact scaling, floor)
+ *     h[m] = min(q[m - W + 1 .. m])                          (a sliding minimum over W frames)
+ *     s[n] = h[n - L + 1] + .. + h[n]                        (an integer, at most L U <= 2^31: any order of summation)
+ *     g[n] = (float)((double)s[n] / (double)(L U))           (one fp64 division, one rounding to fp32)
+ *     out[n] = x[n - L] * g[n]                               (one rounded fp32 multiplication)
+ * The bus is delayed by exactly L frames: the latency a host reports for it (aidax_pool_bus_limiter). The gain falls linearly over the L
+ * frames ahead of a peak, is held for H frames and rises linearly over L frames. Consequences:
+ *  - The ceiling holds without a clamp: every output is finite and |out[n]| <= C, since g[n] <= q[n - L] / U, that bound is exactly
+ *    representable and rounding is monotone.
+ *  - The output does not depend on how the host cuts the frames into blocks.
+ *  - A bus that never exceeds C comes out with its own bits, L frames late, and every g is exactly 1.
+ * A pass is evaluated with the record in force when it was issued, over the whole sample history, frames mixed under an older record
+ * included: a change of record, or of a limiter's on / off, takes effect at the block boundary and is NOT click-free, and a change of L
+ * also changes the delay. A bus whose limiter is OFF (the default) returns the raw k_mix bits undelayed, NaN included; its history is
+ * still kept. The history moves only with limited passes: not with a pass of 0 frames, not while the buses or the stage are off.
+ * The bus meter (aidax_bus_meter), folded by the same launch: every field is a maximum, a minimum or an integer count.
+ *  - frames, passes: of the limited passes since the last clear. in_nonfinite: raw samples that are NaN or +-Inf.
+ *  - in_peak: max |x| over the sanitised samples. out_peak: max |out|.
+ *  - limited: frames with s[n] < L U (the integer test: at L = 512, s = L U - 1 rounds to g == 1.0f). min_gain: min g, 1.0 after a clear.
+ *  - A bus whose limiter is off folds its in_peak into out_peak as well and leaves limited and min_gain alone.
+ * aidax_bus_limit_design      pure, host only, any thread: the record of `params` at `samplerate`, in fp64: ceiling = (float)pow(10,
+ *                             dB / 20) for -60 <= ceiling_db <= 12; lookahead and hold = ms * samplerate / 1000 rounded to nearest; on
+ *                             = 1. AIDAX_ERR_ARG for a null pointer, a non-finite field, a ceiling out of range, a negative time, a
+ *                             look-ahead below 1 or beyond 512 frames, a hold beyond 4096 frames, a samplerate that is not positive.
+ * aidax_pool_set_bus_limiting SET-UP side. The first call with on != 0 allocates everything the feature ever needs — the raw side block,
+ *                             a ring of sanitised samples per bus (zeroed), the records (every limiter off), the meter records
+ *                             (cleared), their snapshots and the pinned staging of the read — all or nothing, fixes the capacities
+ *                             (max_lookahead_frames 1 .. 512, max_hold_frames 0 .. 4096: no record beyond them is accepted), switches
+ *                             the stage on, and may wait. Later calls only flip a host record of the audio side: on != 0 with another
+ *                             capacity is AIDAX_ERR_STATE, on == 0 ignores the capacities. AIDAX_ERR_STATE before aidax_pool_set_buses,
+ *                             AIDAX_ERR_ARG for a null pool or a capacity out of range.
+ * aidax_pool_bus_limiting     1 while the stage is on, else 0 (0 for a null pool).
+ * aidax_pool_set_bus_limiter  AUDIO thread, between passes: `bus` (AIDAX_ALL_BUSES: every bus) is limited with `params`, designed at
+ *                             aidax_pool_samplerate, from the next pass on; params == NULL switches its limiter off. Host records only
+ *                             (they reach the device from a ring of snapshots ahead of the next limited pass): no allocation, no free, no
+ *                             wait. AIDAX_ERR_ARG for a null pool, a bus out of range, whatever aidax_bus_limit_design refuses and a
+ *                             record beyond the capacities (a refused call changes nothing); AIDAX_ERR_STATE before the stage's first
+ *                             enabling.
+ * aidax_pool_bus_limiter      the bus's host record (any pointer may be NULL): its parameters as last set (zeros while off), whether
+ *                             its limiter is on, and its latency in frames (L while on, else 0).
+ * aidax_pool_read_bus_meters  AUDIO side, and it waits and clears like aidax_pool_read_meters (a cleared record has min_gain = 1.0).
+ *                             AIDAX_ERR_ARG for a null argument, count == 0 or first + count > the bus count, AIDAX_ERR_STATE before the
+ *                             stage's first enabling.
+ * Not covered: hub seats and so the LV2 shell, resetting a bus's history, click-free parameter changes, a release longer than the
+ * look-ahead, linked (stereo) buses. */
+#define AIDAX_ALL_BUSES (-1)
+#define AIDAX_BUS_LOOKAHEAD_MAX 512
+#define AIDAX_BUS_HOLD_MAX 4096
+typedef struct { float ceiling_db, lookahead_ms, hold_ms; } aidax_bus_limit_params;
+typedef struct { float ceiling; uint32_t lookahead, hold, on; } aidax_bus_limit_rec;   /* 16 bytes */
+typedef struct {
+    uint64_t frames;           /* frames limited since the last clear                                 */
+    uint64_t passes;           /* limited passes since the last clear                                 */
+    uint64_t in_nonfinite;     /* raw bus samples that are NaN or +-Inf                               */
+    uint64_t limited;          /* frames with s[n] < L U                                              */
+    float    in_peak;          /* max |x| over the sanitised samples                                  */
+    float    out_peak;         /* max |out|                                                           */
+    float    min_gain;         /* min g, 1.0 after a clear                                            */
+    float    reserved;
+} aidax_bus_meter;             /* 48 bytes, no padding */
+AIDAX_API int      aidax_bus_limit_design(const aidax_bus_limit_params* params, double samplerate, aidax_bus_limit_rec* out);
+AIDAX_API int      aidax_pool_set_bus_limiting(aidax_pool* p, int on, uint32_t max_lookahead_frames, uint32_t max_hold_frames);
+AIDAX_API int      aidax_pool_bus_limiting(const aidax_pool* p);
+AIDAX_API int      aidax_pool_set_bus_limiter(aidax_pool* p, int32_t bus, const aidax_bus_limit_params* params);
+AIDAX_API int      aidax_pool_bus_limiter(const aidax_pool* p, uint32_t bus, aidax_bus_limit_params* out, int* on, uint32_t* latency_frames);
+AIDAX_API int      aidax_pool_read_bus_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_bus_meter* out, int clear);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, set_bus_limiting after its first enabling call, set_bus_limiter, read_bus_meters, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side); aidax_gate_design and aidax_mix_gain are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side) and the first aidax_pool_set_bus_limiting with on != 0 (it allocates; aidax_pool_bus_limiting and aidax_pool_bus_limiter read host records of the audio side); aidax_gate_design, aidax_mix_gain and aidax_bus_limit_design are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate) and a changed mix plan (after a set_send), go
+ * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses / aidax_pool_read_bus_meters wait for the GPU (for the stream that carries the pass, never for the
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate), a changed mix plan (after a set_send) and changed bus limiter records (after a set_bus_limiter), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
