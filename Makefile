@@ -126,6 +126,13 @@ build/asan/asan_limit_harness: $(ASAN_LIMIT_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_LIMIT_SRCS) -o $@
 asan_limit: build/asan/asan_limit_harness
 
+# ... and the pass-form decision (aidax_pass_form.h: resolve_pass, a header without HIP): tests/form_harness.cpp, tests/test_pass_form_host.py
+build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_pass_form.h $(SRC)/aidax_layout.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -I$(SRC) tests/form_harness.cpp -o $@
+asan_form: build/asan/form_harness
+
 oracle:
 	$(MAKE) -s -C oracle all
 	$(MAKE) -s -C oracle _ref
@@ -134,4 +141,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_form

@@ -49,9 +49,12 @@ void  build_stream_ctl(const aidax_controls& c, double host_samplerate, bool has
                        float gain_coef, float p_den, StreamCtl* out);
 
 // aidax_pool_process_device restricted to the first n_active streams (aidax_pool.cpp; used by the hub and the rate adapter). `end`: the
-// pass's end markers (aidax_pool.h), which only the pool's own host-buffer paths hand in
+// pass's end markers (aidax_pool.h), which only the pool's own host-buffer paths hand in; `form`: the pass's form where the caller has resolved it
+// already (aidax_pool::resolved_playing_form — the blocking path, which asks it whether the pass may run in place)
 struct PassEnd;
-int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active, PassEnd* end = nullptr);
+struct PassForm;
+int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active, PassEnd* end = nullptr,
+                        const PassForm* form = nullptr);
 
 // park / unpark a stream (behaves disabled while parked; its controls stay what they are) — aidax_pool.cpp, used by the hub
 int pool_park_stream(aidax_pool* p, uint32_t stream, bool parked);

@@ -4,28 +4,27 @@
 #include <hip/hip_runtime_api.h>
 
 #include "aidax_layout.h"
+#include "aidax_pass_form.h"
 
 namespace aidax {
 
+// One (cell, hidden) pair of the reference's table: its one-wave kernel, the optional forms (nullptr: the cell has none) and, in `has`,
+// which of them exist and what they are called — the part the pass-form decision reads (aidax_pass_form.h)
 struct KernelEntry {
     int cell, hidden;
     void (*fn)(LaunchArgs);           // one wavefront per stream (throughput form)
     void (*fn_pipe)(LaunchArgs);      // three wavefronts per stream (latency form)
     void (*fn_nn)(LaunchArgs);        // recurrent cell only, between the two packed chain launches (split form)
-    int pack_regs, state_floats;
-    const char* name;
-    const char* name_pipe;
-    const char* name_split;
-    void (*fn_pipe4)(LaunchArgs);     // four streams per workgroup, one helper wave (k_*_pipe4; nullptr: the cell has none)
-    const char* name_pipe4;
+    void (*fn_pipe4)(LaunchArgs);     // four streams per workgroup, one helper wave (k_*_pipe4)
     void (*fn_pipe4c)(LaunchArgs);    // the same for a conditioned model (PARAM1 / PARAM2 as inputs): the helper wave also runs the PARAM smoothers
-    void (*fn_pipe_bank)(LaunchArgs); // fn_pipe with every stream on the model of its own record (LaunchArgs::bank): the model bank's pass (nullptr: no fn_pipe)
-    const char* name_pipe_bank;
+    void (*fn_pipe_bank)(LaunchArgs); // fn_pipe with every stream on the model of its own record (LaunchArgs::bank): the model bank's pass
+    int pack_regs, state_floats;
+    CellKernels has;
 };
 
 const KernelEntry* find_kernel(int cell, int hidden);
 hipError_t launch_stream_kernel(const KernelEntry* e, const LaunchArgs& a, size_t lds_bytes, hipStream_t stream);
-hipError_t launch_split_kernels(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream);
+hipError_t launch_nn_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream);      // the split form's recurrent cell, between two launch_chain_pass (e == nullptr: no model, nothing)
 bool split_form_pays(const KernelEntry* e, uint32_t n_frames);
 size_t pipe_lds_bytes(int hidden, uint32_t n_frames);
 hipError_t launch_pipe_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream, hipEvent_t done = nullptr);

@@ -1862,34 +1862,52 @@ __global__ void k_adopt_dsp(StreamState* dst, const StreamState* src)
 }
 
 // ------------------------------------------------------------ host dispatch
-#define AIDAX_LSTM(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
-// ... with the four-streams-per-workgroup pipeline as well (BASELINE cfg2's cell)
-#define AIDAX_LSTM_P4(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", k_lstm_pipe4<H>, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true>, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
-// LSTM-64 / LSTM-80: the helper waves' share of the register file (pipe) resp. the Dense ring (split, H = 80) push the
-// 4H-row cell past 512 registers — those forms would spill, so they do not exist; the pool serves these cells
-// with k_quad / k_mfma, or the one-wave kernel when neither fits (pools with long blocks).
-#define AIDAX_LSTM_WIDE(H, NN) { 0, H, k_lstm<H>, nullptr, NN, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "-", "k_chain+k_nn<lstm" #H ">", nullptr, "-", nullptr, nullptr, "-" }
-#define AIDAX_GRU(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "-", nullptr, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
-#define AIDAX_LSTM_P4C(H) { 0, H, k_lstm<H>, k_lstm_pipe<H>, k_nn<LstmCell<H, false>>, LstmCell<H>::PACK, LstmCell<H>::STATE, "k_lstm<" #H ">", "k_lstm_pipe<" #H ">", "k_chain+k_nn<lstm" #H ">", nullptr, "k_lstm_pipe4<" #H ">", k_lstm_pipe4<H, true>, k_lstm_pipe_bank<H>, "k_lstm_pipe_bank<" #H ">" }
-#define AIDAX_GRU_P4C(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", nullptr, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true>, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
-#define AIDAX_GRU_P4(H)  { 1, H, k_gru<H>,  k_gru_pipe<H>,  k_nn<GruCell<H>>,  GruCell<H>::PACK,  GruCell<H>::STATE,  "k_gru<" #H ">", "k_gru_pipe<" #H ">", "k_chain+k_nn<gru" #H ">", k_gru_pipe4<H>, "k_gru_pipe4<" #H ">", k_gru_pipe4<H, true>, k_gru_pipe_bank<H>, "k_gru_pipe_bank<" #H ">" }
+// An entry states its cell, its width and which optional forms exist; a form that is not asked for is not instantiated.
+// (LSTM-64 / LSTM-80: the helper waves' share of the register file (pipe) resp. the Dense ring (split, H = 80) push the 4H-row cell past 512
+// registers — those forms would spill, so they do not exist; the pool serves these cells with k_quad / k_mfma, or the one-wave kernel when
+// neither fits (pools with long blocks).)
+enum : unsigned { HAS_PIPE = 1, HAS_NN = 2, HAS_P4 = 4, HAS_P4C = 8, HAS_BANK = 16,
+                  FORMS_3W = HAS_PIPE | HAS_NN | HAS_BANK,      // the three-wave pipeline, the split form and the bank's kernel
+                  FORMS_P4C = FORMS_3W | HAS_P4C,               // ... and k_*_pipe4 for conditioned models
+                  FORMS_P4 = FORMS_P4C | HAS_P4 };              // ... and for plain ones (BASELINE cfg2's cell)
+#define AIDAX_ENTRY_OF(K, Cell, ID, ...)                                                                                              \
+    template <int H, unsigned F, class NnCell = __VA_ARGS__>                                                                             \
+    static constexpr KernelEntry K##_entry(const char* name, const char* pipe, const char* split, const char* pipe4, const char* bank)          \
+    {                                                                                                                                    \
+        KernelEntry e{};                                                                                                                 \
+        e.cell = ID; e.hidden = H;                                                                                                       \
+        e.fn = k_##K<H>;                                                                                                              \
+        if constexpr ((F & HAS_PIPE) != 0) e.fn_pipe = k_##K##_pipe<H>;                                                               \
+        if constexpr ((F & HAS_NN) != 0) e.fn_nn = k_nn<NnCell>;                                                                         \
+        if constexpr ((F & HAS_P4) != 0) e.fn_pipe4 = k_##K##_pipe4<H>;                                                               \
+        if constexpr ((F & HAS_P4C) != 0) e.fn_pipe4c = k_##K##_pipe4<H, true>;                                                       \
+        if constexpr ((F & HAS_BANK) != 0) e.fn_pipe_bank = k_##K##_pipe_bank<H>;                                                     \
+        e.pack_regs = Cell<H>::PACK; e.state_floats = Cell<H>::STATE;                                                                    \
+        e.has = { (F & HAS_PIPE) != 0, (F & HAS_NN) != 0, (F & HAS_P4) != 0, (F & HAS_P4C) != 0, (F & HAS_BANK) != 0, name,              \
+                  F & HAS_PIPE ? pipe : "-", F & HAS_NN ? split : "-", F & (HAS_P4 | HAS_P4C) ? pipe4 : "-", F & HAS_BANK ? bank : "-" }; \
+        return e;                                                                                                                        \
+    }
+AIDAX_ENTRY_OF(lstm, LstmCell, 0, LstmCell<H, false>)      // (k_nn reads a natural-order copy of the LSTM weights)
+AIDAX_ENTRY_OF(gru, GruCell, 1, GruCell<H>)
+// the names, derived once: AIDAX_CELL(lstm, 32, FORMS_P4) is k_lstm<32>, k_lstm_pipe<32>, k_chain+k_nn<lstm32>, k_lstm_pipe4<32>, k_lstm_pipe_bank<32>
+#define AIDAX_CELL(cell, H, ...) cell##_entry<H, __VA_ARGS__>("k_" #cell "<" #H ">", "k_" #cell "_pipe<" #H ">", "k_chain+k_nn<" #cell #H ">", "k_" #cell "_pipe4<" #H ">", "k_" #cell "_pipe_bank<" #H ">")
 
-static const KernelEntry kTable[] = {
+static constexpr KernelEntry kTable[] = {
     // the 18 (cell, hidden) pairs of variant/generate_variant_hpp.py:4-6; input size is a run-time argument
     // (k_*_pipe4 where it measured ahead of k_*_pipe at a full pool of 1024 streams, profiles/r06_pipe4_cells.txt: LSTM-8 / 12 / 16 by 14 - 19 %,
     // GRU-8 / 12 / 16 by 9 - 14 %, LSTM-32 by 3 %; re-measured on the round's final kernel: GRU-24 by 6 %, LSTM-20 by 1 - 2 %; LSTM-24 and
     // GRU-20 / 32 measure 1 - 10 % behind and keep the three-wave pipeline.
     // A CONDITIONED model — PARAM1 / PARAM2 as inputs — runs k_*_pipe4<H, true> at every cell up to 32: 9 - 25 % ahead, same file)
 #ifdef AIDAX_P4_ALL_CELLS      // (measurement build, scratch/r06_pipe4_cells.py: the plain models of every cell up to 32 on k_*_pipe4)
-    AIDAX_LSTM_P4(8), AIDAX_LSTM_P4(12), AIDAX_LSTM_P4(16), AIDAX_LSTM_P4(20), AIDAX_LSTM_P4(24),
-    AIDAX_LSTM_P4(32), AIDAX_LSTM(40), AIDAX_LSTM_WIDE(64, k_nn<LstmCell<64>>), AIDAX_LSTM_WIDE(80, nullptr),
-    AIDAX_GRU_P4(8), AIDAX_GRU_P4(12), AIDAX_GRU_P4(16), AIDAX_GRU_P4(20), AIDAX_GRU_P4(24),
-    AIDAX_GRU_P4(32), AIDAX_GRU(40), AIDAX_GRU(64), AIDAX_GRU(80),
+    AIDAX_CELL(lstm, 8, FORMS_P4), AIDAX_CELL(lstm, 12, FORMS_P4), AIDAX_CELL(lstm, 16, FORMS_P4), AIDAX_CELL(lstm, 20, FORMS_P4), AIDAX_CELL(lstm, 24, FORMS_P4),
+    AIDAX_CELL(lstm, 32, FORMS_P4), AIDAX_CELL(lstm, 40, FORMS_3W), AIDAX_CELL(lstm, 64, HAS_NN, LstmCell<64>), AIDAX_CELL(lstm, 80, 0),
+    AIDAX_CELL(gru, 8, FORMS_P4), AIDAX_CELL(gru, 12, FORMS_P4), AIDAX_CELL(gru, 16, FORMS_P4), AIDAX_CELL(gru, 20, FORMS_P4), AIDAX_CELL(gru, 24, FORMS_P4),
+    AIDAX_CELL(gru, 32, FORMS_P4), AIDAX_CELL(gru, 40, FORMS_3W), AIDAX_CELL(gru, 64, FORMS_3W), AIDAX_CELL(gru, 80, FORMS_3W),
 #else
-    AIDAX_LSTM_P4(8), AIDAX_LSTM_P4(12), AIDAX_LSTM_P4(16), AIDAX_LSTM_P4(20), AIDAX_LSTM_P4C(24),
-    AIDAX_LSTM_P4(32), AIDAX_LSTM(40), AIDAX_LSTM_WIDE(64, k_nn<LstmCell<64>>), AIDAX_LSTM_WIDE(80, nullptr),
-    AIDAX_GRU_P4(8), AIDAX_GRU_P4(12), AIDAX_GRU_P4(16), AIDAX_GRU_P4C(20), AIDAX_GRU_P4(24),
-    AIDAX_GRU_P4C(32), AIDAX_GRU(40), AIDAX_GRU(64), AIDAX_GRU(80),
+    AIDAX_CELL(lstm, 8, FORMS_P4), AIDAX_CELL(lstm, 12, FORMS_P4), AIDAX_CELL(lstm, 16, FORMS_P4), AIDAX_CELL(lstm, 20, FORMS_P4), AIDAX_CELL(lstm, 24, FORMS_P4C),
+    AIDAX_CELL(lstm, 32, FORMS_P4), AIDAX_CELL(lstm, 40, FORMS_3W), AIDAX_CELL(lstm, 64, HAS_NN, LstmCell<64>), AIDAX_CELL(lstm, 80, 0),
+    AIDAX_CELL(gru, 8, FORMS_P4), AIDAX_CELL(gru, 12, FORMS_P4), AIDAX_CELL(gru, 16, FORMS_P4), AIDAX_CELL(gru, 20, FORMS_P4C), AIDAX_CELL(gru, 24, FORMS_P4),
+    AIDAX_CELL(gru, 32, FORMS_P4C), AIDAX_CELL(gru, 40, FORMS_3W), AIDAX_CELL(gru, 64, FORMS_3W), AIDAX_CELL(gru, 80, FORMS_3W),
 #endif
 };
 
@@ -1927,15 +1945,13 @@ hipError_t launch_chain_pass(bool pre, const LaunchArgs& a, hipStream_t stream)
     return hipGetLastError();
 }
 
-// Split form: pre chain (8 streams/wave) -> recurrent cell -> post chain, in place on `out`
-hipError_t launch_split_kernels(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream)
+// Split form: pre chain (8 streams/wave) -> recurrent cell -> post chain, in place on `out`: the cell
+hipError_t launch_nn_kernel(const KernelEntry* e, const LaunchArgs& a, hipStream_t stream)
 {
-    hipError_t err = launch_chain_pass(true, a, stream);
-    if (err != hipSuccess) return err;
-    if (e && !e->fn_nn) return hipErrorInvalidDeviceFunction;
-    if (e && a.n_frames != 0)
-        hipLaunchKernelGGL(e->fn_nn, dim3(a.n_streams), dim3(kWave), nn_lds_floats(e->hidden, (int)a.n_frames) * sizeof(float), stream, a);
-    return launch_chain_pass(false, a, stream);
+    if (!e) return hipSuccess;
+    if (!e->fn_nn) return hipErrorInvalidDeviceFunction;
+    hipLaunchKernelGGL(e->fn_nn, dim3(a.n_streams), dim3(kWave), nn_lds_floats(e->hidden, (int)a.n_frames) * sizeof(float), stream, a);
+    return hipGetLastError();
 }
 
 // Is the split form the better many-streams form for this cell? Yes when the lean recurrent kernel still

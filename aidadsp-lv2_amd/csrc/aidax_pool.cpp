@@ -189,133 +189,114 @@ static KeepWarm& keep_warm() { static KeepWarm k; return k; }
 
 }  // namespace aidax
 
-hipError_t aidax_pool::launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s, PassEnd* end) const
+// The executor of a PassForm (aidax_pass_form.h decides it): one arm per kernel family; the packed chains around a kernel that does not run
+// them itself, the time slices and stream ranges, the end markers and the refusal of a chained grid are what only the launch path can do.
+hipError_t aidax_pool::launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s, PassEnd* end, const PassForm* known) const
 {
-    // the split form of a MODE_CHAIN pass: packed chains in -> out, the model's kernel in place (none for a block of no frames), packed chains
-    auto between_chains = [&](auto&& model_launch) {
-        hipError_t e = launch_chain_pass(true, a, s);
-        if (e == hipSuccess && a.n_frames != 0) e = model_launch();
-        if (e == hipSuccess) e = launch_chain_pass(false, a, s);
-        return e;
-    };
-    if (m.has_model && m.kind == ModelSlot::MFMA) {
-        // split form around the matrix-core kernel: packed chains in -> out, applyModel in place, packed chains
-        // k_mfma_lp only for the passes themselves: warm-ups (worker stream, next to the passes) and the bare-model
-        // modes run on k_mfma, which leaves bit-identical state — two of those grids must never be in flight together
-        // A chained grid the runtime refuses (cooperative launch: it cannot be co-resident on this device — a partitioned
-        // GPU, a pool forced onto the kernel) is no error of the pass: the model is served by k_mfma from here on
-        auto refused = [&](hipError_t e) {
-            if (e != hipErrorCooperativeLaunchTooLarge) return false;
-            (void)hipGetLastError();
-            m.lp_refused = true;                          // this model's grid; a pool-wide lp_off is for give-ups (co-tenants)
-            // ... and this slot's share of the pool's hold on the device's gate goes back: a pool that cannot use the chained kernels
-            // must not keep every other pool of the device off them (advisor, round 5)
-            if (m.lp_owner) { lp_gate().release(device, m.lp_owner); m.lp_owner = nullptr; }
-            lp_refusals.fetch_add(1, std::memory_order_relaxed);
-            set_error("a chained grid cannot be co-resident on this device (cooperative launch refused): the model is served by k_mfma");
-            return true;
-        };
-        // k_mfma_ls over the pass's streams: one launch, or one per range of lp_round_streams streams (every range a resident grid)
-        auto launch_ls = [&](bool fused) {
-            if (!m.lp_round_streams || a.n_streams <= m.lp_round_streams)
-                return launch_mfma_ls_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, m.lp_split, s, fused);
-            for (uint32_t s0 = 0; s0 < a.n_streams; s0 += m.lp_round_streams) {
-                LaunchArgs b = a;
-                b.n_streams = std::min(m.lp_round_streams, a.n_streams - s0);
-                b.ctl = a.ctl + s0; b.st = a.st + s0; b.nn = a.nn + static_cast<size_t>(s0) * a.nn_stride;
-                if (a.in) b.in = a.in + static_cast<size_t>(s0) * a.n_frames;
-                b.out = a.out + static_cast<size_t>(s0) * a.n_frames;
-                const hipError_t e = launch_mfma_ls_kernel(b, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, m.lp_split, s, fused);
-                if (e != hipSuccess) return e;      // (a refusal can only come from the first range: the ranges are one size or smaller)
-            }
-            return hipSuccess;
-        };
-        auto model_kernel = [&]() {
-            if (lp_in_use(m) && a.mode == MODE_CHAIN) {
-                const hipError_t e = m.lp_split ? launch_ls(false) : launch_mfma_lp_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, s);
-                if (!refused(e)) return e;
-            }
-            return launch_mfma_kernel(a, m.mdesc, s);
-        };
-        if (a.mode != MODE_CHAIN) return model_kernel();
-        if (m.lstm_gs && a.n_frames != 0) return launch_lstm_gs_kernel(a, m.mdesc, m.lstm_gs, s);
-        if (m.gru_gm && a.n_frames != 0) return m.gru_gs ? launch_gru_gs_kernel(a, m.mdesc, m.gru_gs, s) : launch_gru_gm_kernel(a, m.mdesc, s);
-        if (m.lp_fused && lp_in_use(m) && a.n_frames != 0) {
-            const hipError_t e = m.lp_split ? launch_ls(true) : launch_mfma_lp_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, s, true);
-            if (!refused(e)) return e;
-        }
-        return between_chains(model_kernel);
-    }
-    if (m.has_model && m.kind == ModelSlot::QUAD) {
-        if (a.mode != MODE_CHAIN) return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s);
-        return between_chains([&] { return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s); });
-    }
-    if (m.has_model && m.kind == ModelSlot::STACK) return launch_stack_kernel(a, m.sdesc, s);
-    if (m.has_model && m.kind == ModelSlot::CONV && m.conv_mfma) {
-        auto conv_launch = [&](const LaunchArgs& b, bool fused) {
-            return m.conv_ms ? launch_conv_ms_kernel(b, m.cdesc, fused, s) : launch_conv_mfma_kernel(b, m.cdesc, fused, s);
-        };
-        if (a.mode != MODE_CHAIN) return conv_launch(a, false);
-        if (m.conv_fused) {
-            // the whole run() in one launch; a block longer than the kernel's 256 frames goes through in time slices,
-            // each the whole run() of its slice (the rows keep the block's pitch)
-            const uint32_t chunk = ext_chunk();
-            if (a.n_frames <= chunk) return conv_launch(a, true);
-            hipError_t e = hipSuccess;
-            for (uint32_t done = 0; done < a.n_frames && e == hipSuccess; done += chunk) {
-                LaunchArgs b = a;
-                b.in = a.in + done; b.out = a.out + done;
-                b.n_frames = std::min(chunk, a.n_frames - done);
-                b.row_stride = a.n_frames;
-                e = conv_launch(b, true);
-            }
-            return e;
-        }
-        return between_chains([&] { return conv_launch(a, false); });
-    }
-    if (m.has_model && m.kind == ModelSlot::CONV) return launch_conv_kernel(a, m.cdesc, s);
-    // A one-launch pass takes its end markers with it: the pipelined host path's "pass done" event rides on the dispatch (it saves the
-    // marker packet behind the kernel), and the blocking path's completion word is written by the one workgroup of a one-stream pool itself
-    auto take_end_markers = [&](LaunchArgs& b) -> hipEvent_t {
-        if (!end) return nullptr;
+    // A one-launch pass takes its end markers with it (PassForm::carries_event / carries_word)
+    auto take_end_markers = [&](const PassForm& f, LaunchArgs& b) -> hipEvent_t {
+        if (!end || !f.carries_event) return nullptr;
         hipEvent_t done = end->done;
         end->done = nullptr;
         end->done_taken = done != nullptr;
-        if (end->word && b.n_streams == 1 && b.n_frames != 0) {
+        if (end->word && f.carries_word) {
             b.done_word = end->word; b.done_seq = end->seq;
             end->word = nullptr;
             end->word_taken = true;
         }
         return done;
     };
-    if (a.bank) {
-        // the model bank in force (pool_process_prefix set the records): the whole pass is one launch of k_*_pipe_bank, whatever form
-        // the pool model alone would take
-        LaunchArgs b = a;
-        hipEvent_t done = take_end_markers(b);
-        return launch_pipe_bank_kernel(m.kernel, b, s, done);
+    // a block longer than the extension kernels' 256 frames: time slices, each the whole run() of its slice (the rows keep the block's pitch)
+    auto time_slices = [&](auto&& one) {
+        const uint32_t chunk = ext_chunk();
+        hipError_t e = hipSuccess;
+        for (uint32_t done = 0; done < a.n_frames && e == hipSuccess; done += chunk) {
+            LaunchArgs b = a;
+            b.in = a.in + done; b.out = a.out + done;
+            b.n_frames = std::min(chunk, a.n_frames - done);
+            b.row_stride = a.n_frames;
+            e = one(b);
+        }
+        return e;
+    };
+    // a pass over more streams than one resident grid of k_mfma_ls holds: one launch per range (every range a resident grid)
+    auto stream_ranges = [&](auto&& one) {
+        const uint32_t step = m.form.round_streams();
+        hipError_t e = hipSuccess;      // (a refusal can only come from the first range: the ranges are one size or smaller)
+        for (uint32_t s0 = 0; s0 < a.n_streams && e == hipSuccess; s0 += step) {
+            LaunchArgs b = a;
+            b.n_streams = std::min(step, a.n_streams - s0);
+            b.ctl = a.ctl + s0; b.st = a.st + s0; b.nn = a.nn + static_cast<size_t>(s0) * a.nn_stride;
+            if (a.in) b.in = a.in + static_cast<size_t>(s0) * a.n_frames;
+            b.out = a.out + static_cast<size_t>(s0) * a.n_frames;
+            e = one(b);
+        }
+        return e;
+    };
+    auto in_pieces = [&](const PassForm& f, auto&& one) {
+        return f.pieces == PassForm::TIME_SLICES ? time_slices(one) : f.pieces == PassForm::STREAM_RANGES ? stream_ranges(one) : one(a);
+    };
+    auto kernel = [&](const PassForm& f) -> hipError_t {
+        const bool whole_run = a.mode == MODE_CHAIN && !f.chains;      // the kernel runs the DSP chain too
+        const KernelEntry* table = m.has_model ? m.kernel : nullptr;
+        switch (f.kern) {
+        case PassKern::NoModel:
+        case PassKern::Wave: return launch_stream_kernel(table, a, lds_bytes(m, a.mode == MODE_CHAIN ? a.n_frames : 0), s);
+        case PassKern::Pipe: { LaunchArgs b = a; hipEvent_t done = take_end_markers(f, b); return launch_pipe_kernel(table, b, s, done); }
+        case PassKern::Pipe4: { LaunchArgs b = a; hipEvent_t done = take_end_markers(f, b); return launch_pipe4_kernel(table, b, s, done); }
+        // (the model bank in force — pool_process_prefix set the records)
+        case PassKern::PipeBank: { LaunchArgs b = a; hipEvent_t done = take_end_markers(f, b); return launch_pipe_bank_kernel(table, b, s, done); }
+        case PassKern::Q4: { LaunchArgs b = a; b.wpack = m.d_wq4; return launch_q4_kernel(m.hidden, b, s); }
+        case PassKern::Nn: return launch_nn_kernel(table, a, s);
+        case PassKern::Quad: return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s);
+        case PassKern::Mfma: return launch_mfma_kernel(a, m.mdesc, s);
+        case PassKern::MfmaLp: return launch_mfma_lp_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, s, whole_run);
+        case PassKern::MfmaLs:
+            return in_pieces(f, [&](const LaunchArgs& r) { return launch_mfma_ls_kernel(r, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, m.form.products(), s, whole_run); });
+        case PassKern::GruGm: return launch_gru_gm_kernel(a, m.mdesc, s);
+        case PassKern::GruGs: return launch_gru_gs_kernel(a, m.mdesc, m.form.products(), s);
+        case PassKern::LstmGs: return launch_lstm_gs_kernel(a, m.mdesc, m.form.products(), s);
+        case PassKern::Stack: return launch_stack_kernel(a, m.sdesc, s);
+        case PassKern::Conv: return launch_conv_kernel(a, m.cdesc, s);
+        case PassKern::ConvMfma: return in_pieces(f, [&](const LaunchArgs& r) { return launch_conv_mfma_kernel(r, m.cdesc, whole_run, s); });
+        case PassKern::ConvMs: return in_pieces(f, [&](const LaunchArgs& r) { return launch_conv_ms_kernel(r, m.cdesc, whole_run, s); });
+        }
+        return hipErrorInvalidValue;
+    };
+    // the packed chains in -> out ahead of a kernel that works in place between them (once per pass), and the kernel — none for a block of no frames
+    bool pre_issued = false;
+    auto issue = [&](const PassForm& f) {
+        hipError_t e = hipSuccess;
+        if (f.chains && !pre_issued) { e = launch_chain_pass(true, a, s); pre_issued = true; }
+        if (e == hipSuccess && !(f.chains && a.n_frames == 0)) e = kernel(f);
+        return e;
+    };
+    // (a form resolved by the caller stands unless it names a chained kernel that a give-up or a refusal has retired since)
+    const bool chained_known = known && (known->kern == PassKern::MfmaLp || known->kern == PassKern::MfmaLs);
+    PassForm f = known && !(chained_known && !lp_in_use(m)) ? *known : pass_form(m, a.mode, a.n_frames, a.n_streams, a.bank != nullptr);
+    hipError_t e = issue(f);
+    if (e == hipErrorCooperativeLaunchTooLarge && (f.kern == PassKern::MfmaLp || f.kern == PassKern::MfmaLs)) {
+        // A chained grid the runtime refuses (cooperative launch: it cannot be co-resident on this device — a partitioned GPU, a pool forced
+        // onto the kernel) is no error of the pass: the model is served by k_mfma from here on, and the form is resolved again
+        (void)hipGetLastError();
+        m.lp_refused = true;                          // this model's grid; a pool-wide lp_off is for give-ups (co-tenants)
+        // ... and this slot's share of the pool's hold on the device's gate goes back: a pool that cannot use the chained kernels
+        // must not keep every other pool of the device off them (advisor, round 5)
+        if (m.lp_owner) { lp_gate().release(device, m.lp_owner); m.lp_owner = nullptr; }
+        lp_refusals.fetch_add(1, std::memory_order_relaxed);
+        set_error("a chained grid cannot be co-resident on this device (cooperative launch refused): the model is served by k_mfma");
+        f = pass_form(m, a.mode, a.n_frames, a.n_streams, a.bank != nullptr);
+        e = issue(f);
     }
-    const int form = a.mode == MODE_CHAIN ? chain_form(m) : 0;
-    if (form == 3) {
-        LaunchArgs b = a;
-        b.wpack = m.d_wq4;
-        return launch_q4_kernel(m.hidden, b, s);
-    }
-    if (form == 1) {
-        LaunchArgs b = a;
-        hipEvent_t done = take_end_markers(b);
-        if (!pipe4_serves(m, a.n_frames, a.input_size)) return launch_pipe_kernel(m.kernel, b, s, done);
-        return launch_pipe4_kernel(m.kernel, b, s, done);
-    }
-    if (form == 2) return launch_split_kernels(m.has_model ? m.kernel : nullptr, a, s);
-    return launch_stream_kernel(m.has_model ? m.kernel : nullptr, a, lds_bytes(m, a.mode == MODE_CHAIN ? a.n_frames : 0), s);
+    if (e == hipSuccess && f.chains) e = launch_chain_pass(false, a, s);
+    return e;
 }
 
 namespace aidax {
 
 // aidax_pool_process_device over the first `n_active` streams only (rows of the others are neither read nor
 // written, their state does not move): the hub launches what can be attached, not the pool's capacity.
-int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active, PassEnd* end)
+int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t n_frames, void* hip_stream, uint32_t n_active, PassEnd* end, const PassForm* form)
 {
     if (n_frames > p->max_frames) return fail(AIDAX_ERR_ARG, "n_frames exceeds the pool's max_frames");
     if (n_frames != 0 && (!d_in || !d_out)) return fail(AIDAX_ERR_ARG, "null buffer");
@@ -326,9 +307,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         hipStream_t s = hip_stream ? static_cast<hipStream_t>(hip_stream) : p->q;
         p->enter_stream(s);
         p->flush_ctl(s);
-        // a give-up of an earlier pass that nobody has collected yet: no further k_mfma_lp launch (its counters are out
-        // of step); the word stays for whoever reports it (aidax_pool_sync, the hub)
-        if (p->h_lp_fault && *static_cast<volatile uint32_t*>(p->h_lp_fault) != 0) p->lp_off.store(true, std::memory_order_relaxed);
+        p->note_lp_give_up();                                          // (ahead of the form's resolution in launch)
         LaunchArgs a = p->args(p->cur, p->d_st, d_in, d_out, n_frames, MODE_CHAIN);
         a.n_streams = n_active;
         if (p->bank.in_force()) a.bank = p->bank.flush(s);           // the records this pass plays, ahead of it on its stream
@@ -344,7 +323,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) p->meter.launch_in(d_in, n_active, n_frames, s);  // (ahead of the pass: it may work in place)
         a.in = p->gate.before_pass(d_in, p->d_ctl, n_active, n_frames, s);      // the gated block, where a gate is on
-        HIP_TRY(p->launch(p->cur, a, s, end));
+        HIP_TRY(p->launch(p->cur, a, s, end, form));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
@@ -411,10 +390,10 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
         p->device = device_id;
         p->n_streams = n_streams;
         p->max_frames = max_frames;
+        p->packed_fits = chain_lds_bytes(max_frames) <= kChainLdsLimit;
         p->host_sr = host_samplerate;
         p->gain_coef = exp_smoother_coef(static_cast<float>(host_samplerate), 0.1f);
-        if (const char* f = AIDAX_HOOK_ENV("AIDAX_KERNEL"))
-            p->force_form = std::strcmp(f, "wave") == 0 ? 1 : std::strcmp(f, "pipe") == 0 ? 2 : std::strcmp(f, "split") == 0 ? 3 : std::strcmp(f, "valu") == 0 ? 4 : std::strcmp(f, "mfma") == 0 ? 5 : std::strcmp(f, "quad") == 0 ? 6 : std::strcmp(f, "q4") == 0 ? 7 : 0;
+        p->force = parse_force(AIDAX_HOOK_ENV("AIDAX_KERNEL"));
         if (const char* t = AIDAX_HOOK_ENV("AIDAX_TUNE")) p->tune = std::atoi(t);
         try {
             HIP_TRY(hipSetDevice(device_id));

@@ -1,6 +1,9 @@
-// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: forms, launches, create / destroy,
-// controls and stream state), aidax_pool_model.cpp (everything that builds or commits an aidax_staged) and aidax_pool_io.cpp (the
-// host-buffer entry points). Private to them. Issues HIP calls: include it last, like aidax_model_bank.h.
+// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: the form heuristics, launch — the
+// executor of a PassForm —, create / destroy, controls and stream state), aidax_pool_model.cpp (everything that builds or commits an
+// aidax_staged) and aidax_pool_io.cpp (the host-buffer entry points). Which kernels serve a pass is decided in ONE place, the HIP-free
+// aidax_pass_form.h: a slot carries the SlotForm that choose_form gave it, aidax_pool::pass_form gathers the facts (and reads the per-call
+// hooks), and launch, aidax_pool_kernel_name and aidax_pool_process all read the PassForm it returns. Private to the three sources.
+// Issues HIP calls: include it last, like aidax_model_bank.h.
 #pragma once
 
 #include <algorithm>
@@ -80,29 +83,19 @@ struct ModelSlot {
     StackDesc sdesc{};
     MfmaDesc mdesc{};
     ConvDesc cdesc{};
-    bool conv_mfma = false;          // conv stacks on the matrix cores (blocks of <= 256 frames), else k_conv
-    bool conv_ms = false;            // ... as bf16 term products (k_conv_ms: the stacks conv_ms_shape_ok admits; its own history layout)
-    bool conv_fused = false;         // ... with the DSP chain inside the same launch (AIDAX_CONV_FUSED=0: packed k_chain launches around it)
+    SlotForm form;                   // how the model's passes are served (aidax_pass_form.h; choose_form decides it, nothing changes it afterwards)
     const KernelEntry* kernel = nullptr;
     int cell = 0, input_size = 1, input_skip = 0, hidden = 0;
     float in_gain = 1.f, out_gain = 1.f, model_sr = 48000.f;
     uint32_t nn_stride = 0;
-    int pipe_capacity = 0;           // streams the 3-wave pipeline keeps resident at once (0 = never use it)
-    bool split_pays = false;         // the lean recurrent kernel keeps the occupancy of the one-wave kernel
     float* d_wq4 = nullptr;          // k_lstm_q4's weight record (LSTM-32 snapshot models), next to the table kernels' d_wpack
     float* d_wpack = nullptr;        // weights in the kernel's layout
     float* d_nn = nullptr;           // recurrent state [n_streams][nn_stride]
     float* d_ring = nullptr;         // k_mfma_lp: h of layer l-1 on its way to layer l, per stream group
     uint32_t* d_counters = nullptr;  // k_mfma_lp: frames produced / consumed per (group, layer boundary)
     mutable const void* lp_owner = nullptr;  // the pool whose hold on the device's LpGate this slot shares (d_ring != nullptr); given up on the launch path when the grid is refused
-    bool lp_fused = false;           // k_mfma_lp runs the DSP chain too (one-layer models, helper waves): one launch per block
-    uint32_t lp_round_streams = 0;   // k_mfma_ls on a pool larger than one resident grid: streams per launch (a pass is several launches over stream ranges); 0: one launch
     mutable RelaxedFlag lp_refused;  // the runtime refused this model's chained grid (cooperative launch: not co-resident on this device): k_mfma serves it — this
                                      // model only; another model of the pool, with a smaller grid, may still fit (set on the launch path, hence mutable)
-    int lp_split = 0;                // stacked models: k_mfma_ls serves the passes (contractions as bf16 term products of split operands): 6 or 9 products; 0: k_mfma_lp (fp32 MFMAs)
-    bool gru_gm = false;             // one-layer GRU: k_gru_gm (gate-major tiles, the whole run() in one launch) serves the passes
-    int lstm_gs = 0;                 // one-layer LSTM-40 / 64 on k_lstm_gs (k_gru_gs's structure): 6 or 9 term products; 0: not
-    int gru_gs = 0;                  // ... as k_gru_gs (recurrent product on the bf16 matrix pipe, operands split into three bf16 terms): 6 or 9 term products; 0: the fp32 kernel
 
     float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
     ModelRec rec() const { return model_rec(d_wpack, in_gain, out_gain, input_skip); }      // what a banked stream on this model reads of it
@@ -243,74 +236,41 @@ struct aidax_pool {
     ModelBankStage bank;             // the model bank (aidax_model_bank.h; nothing until the first aidax_pool_prepare_model_slot)
     int tune = 0;                    // AIDAX_TUNE (measurement switches, see LaunchArgs)
     int cus = 0;                     // compute units of the device (form selection)
-    int force_form = 0;              // AIDAX_KERNEL=wave|pipe|split|valu|mfma|quad overrides the heuristic (A/B testing)
+    bool packed_fits = false;        // the packed chains' eight rows of max_frames fit their LDS (chain_lds_bytes: set by aidax_pool_create)
+    Force force = Force::None;       // AIDAX_KERNEL (test build) overrides the heuristics (A/B testing)
 
-    // Form of a MODE_CHAIN pass of a TABLE slot: 0 one wave per stream, 1 three-wave pipeline (all streams resident at
-    // once: latency-bound regime), 2 split launches with packed chains (many streams: issue-bound regime), 3 four
-    // streams per workgroup with the cell on the matrix cores (k_lstm_q4: about four streams per CU or fewer)
-    int chain_form(const ModelSlot& m) const
-    {
-        if (m.kind != ModelSlot::TABLE && m.has_model) return 0;
-        if (m.has_model && m.d_wq4 && force_form == 7) return 3;      // opt-in only (AIDAX_KERNEL=q4): measured slower than the pipeline, see aidax_q4.hip
-        if (force_form == 1) return 0;
-        if (force_form == 2) return (m.has_model && m.kernel && m.kernel->fn_pipe) ? 1 : 0;
-        const bool packed_fits = chain_lds_bytes(max_frames) <= kChainLdsLimit;      // packed chains keep 8 blocks in LDS
-        if (force_form == 3) return (packed_fits && (!m.has_model || (m.kernel && m.kernel->fn_nn))) ? 2 : 0;
-        if (use_pipe(m)) return 1;
-        if (n_streams < 64 || !packed_fits) return 0;
-        return (!m.has_model || m.split_pays) ? 2 : 0;
-    }
-    // Models of the reference's table on the matrix-core kernels (many_streams_form); AIDAX_KERNEL=quad|mfma force one.
-    bool quad_for_table_model(int cell_kind, int hidden_units) const
-    {
-        if (force_form == 6) return true;
-        return force_form == 0 && many_streams_form(cell_kind, hidden_units, n_streams, cus, max_frames) == MANY_QUAD;
-    }
-    bool mfma_for_table_model(int cell_kind, int hidden_units) const
-    {
-        if (force_form == 5) return true;
-        return force_form == 0 && many_streams_form(cell_kind, hidden_units, n_streams, cus, max_frames) == MANY_MFMA;
-    }
-    bool use_pipe(const ModelSlot& m) const
-    {
-        if (!m.has_model || !m.kernel || !m.kernel->fn_pipe || m.kind != ModelSlot::TABLE) return false;
-        if (force_form == 1 || force_form == 3) return false;
-        if (force_form == 2) return true;
-        return static_cast<int>(n_streams) <= m.pipe_capacity;
-    }
-    // does a MODE_CHAIN pass of this slot consist of one launch (it may then read and write host memory in place)?
-    bool single_launch(const ModelSlot& m) const
-    {
-        if (&m == &cur && bank.in_force()) return true;
-        if (!m.has_model) return chain_form(m) != 2;
-        switch (m.kind) {
-        case ModelSlot::TABLE: return chain_form(m) != 2;
-        case ModelSlot::STACK: return true;
-        case ModelSlot::CONV: return !m.conv_mfma || m.conv_fused;
-        default: return false;
-        }
-    }
-
-    bool lp_in_use(const ModelSlot& m) const { return m.d_ring != nullptr && !m.lp_refused && !(m.mdesc.n_layers >= 2 && lp_off.load(std::memory_order_relaxed)); }
-
+    bool lp_in_use(const ModelSlot& m) const { return chained_usable(m.d_ring != nullptr && !m.lp_refused, m.mdesc.n_layers >= 2, lp_off.load(std::memory_order_relaxed)); }
     static size_t lds_bytes(const ModelSlot& m, uint32_t n_frames)
     {
         return (static_cast<size_t>((n_frames + 3) & ~3u) + static_cast<size_t>(m.hidden > 0 ? m.hidden + 4 : 4)) * sizeof(float);   // block + h row + spare slot
     }
 
-    // Does a MODE_CHAIN pass of n frames go through the four-streams-per-workgroup pipeline (k_*_pipe4: 61.9 us per cfg2 block against
-    // k_lstm_pipe's 63.8, the small cells 9 - 19 % ahead, conditioned models 9 - 25 % at every cell up to 32: profiles/r06_cfg2_pipe4.txt, r06_pipe4_cells.txt)? Whole 16-frame tiles, at least one full
-    // workgroup of four streams (a conditioned model: any pool), every workgroup on a CU of its own; k_*_pipe serves every other pass on the same
-    // state (AIDAX_PIPE4=0, test build: all of them).
-    // (a plain model below one full workgroup: level at 256 frames, 0.6 - 1.0 us behind at 64 — the helper wave's longer prologue; a conditioned
-    // model is 11 - 20 % ahead also as a pool of ONE stream, the LV2 instance's: profiles/r06_pipe4_cells.txt. AIDAX_PIPE4_MIN, test build: the measurement's switch)
-    static uint32_t p4_min_streams(int input_size) { const char* e = AIDAX_HOOK_ENV("AIDAX_PIPE4_MIN"); return e ? (uint32_t)atoi(e) : input_size > 1 ? 1u : 4u; }
-    bool pipe4_serves(const ModelSlot& m, uint32_t n, int input_size) const
+    // The form of one pass (or warm-up, or bare-model run) of slot m over n_pass_streams streams: the facts resolve_pass decides on. bank_pass:
+    // a pass of the playing slot with the model bank in force. (The two hooks are read per call: tests switch forms within one process.)
+    PassForm pass_form(const ModelSlot& m, int mode, uint32_t n_frames, uint32_t n_pass_streams, bool bank_pass) const
     {
-        const bool off = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_PIPE4"); return e && e[0] == '0'; }();      // (read per call: tests switch forms within one process)
-        if (off || force_form != 0 || !m.kernel || !(input_size > 1 ? m.kernel->fn_pipe4c : m.kernel->fn_pipe4) || input_size < 1 || input_size > 3 || n == 0 || n % 16u || n_streams < p4_min_streams(input_size)) return false;
-        return cus > 0 && (n_streams + 3u) / 4u <= static_cast<uint32_t>(cus) && pipe4_lds_bytes(m.hidden, n, input_size) <= 160 * 1024;
+        const char* p4 = AIDAX_HOOK_ENV("AIDAX_PIPE4");
+        const char* p4_min = AIDAX_HOOK_ENV("AIDAX_PIPE4_MIN");
+        const bool table = m.has_model && m.kernel;
+        PoolFacts pool{};
+        pool.n_streams = n_streams; pool.max_frames = max_frames; pool.cus = cus; pool.force = force;
+        pool.pipe4_off = p4 && p4[0] == '0'; pool.pipe4_min = p4_min ? atoi(p4_min) : -1;
+        pool.bank = bank_pass; pool.lp_off = lp_off.load(std::memory_order_relaxed); pool.packed_fits = packed_fits;
+        PassFacts pass{};
+        pass.slot = m.form; pass.has = table ? &m.kernel->has : nullptr;
+        pass.mode = mode; pass.n_frames = n_frames; pass.n_streams = n_pass_streams; pass.input_size = m.input_size;
+        pass.pipe4_lds_ok = table && pipe4_lds_bytes(m.hidden, n_frames, m.input_size) <= 160 * 1024;      // (a CU's LDS)
+        pass.ring_ready = m.d_ring != nullptr && !m.lp_refused; pass.hand_over = m.mdesc.n_layers >= 2;
+        pass.conv_st = m.cdesc.st_ok != 0;
+        return resolve_pass(pool, pass);
     }
+    // ... and of a MODE_CHAIN pass of the playing slot over the whole pool: what aidax_pool_kernel_name names (at max_frames) and aidax_pool_process asks
+    PassForm playing_form(uint32_t n_frames) const { return pass_form(cur, MODE_CHAIN, n_frames, n_streams, bank.in_force()); }
+    // A give-up of an earlier pass that nobody has collected yet: no further k_mfma_lp / k_mfma_ls launch of a stacked model (its counters are
+    // out of step); the word stays for whoever reports it (aidax_pool_sync, the hub). AHEAD of every resolution of a form that launch executes.
+    void note_lp_give_up() const { if (h_lp_fault && *static_cast<volatile uint32_t*>(h_lp_fault) != 0) lp_off.store(true, std::memory_order_relaxed); }
+    // ... so the form a caller resolves ahead of pool_process_prefix, to hand it in: the one launch would resolve itself
+    PassForm resolved_playing_form(uint32_t n_frames) const { note_lp_give_up(); return playing_form(n_frames); }
     void refresh_ctl(uint32_t s)
     {
         build_stream_ctl(controls[s], host_sr, cur.has_model, loading[s] != 0, gain_coef, cur.p_den(), &h_ctl[s]);
@@ -376,7 +336,7 @@ struct aidax_pool {
         return (m.kind == ModelSlot::STACK || m.kind == ModelSlot::CONV || m.kind == ModelSlot::MFMA) ? std::min(ext_chunk(), n) : n;
     }
     // one pass (or warm-up, or bare-model run) of slot m in the form the pool chose for it; `end`: the pass's end markers, for a launch that can carry them (aidax_pool.cpp)
-    hipError_t launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s, PassEnd* end = nullptr) const;
+    hipError_t launch(const ModelSlot& m, const LaunchArgs& a, hipStream_t s, PassEnd* end = nullptr, const PassForm* known = nullptr) const;
     // A fresh DynamicModel for stream s alone (:1035, :1053-1061), with START_WARMUP 2048 zeros through applyModel (:1077-1078): the launch
     // arguments view the pool as one stream, which plays the model of `rec` (m's own, or a bank slot's weights, gains and skip)
     void fresh_stream_model(const ModelSlot& m, uint32_t s, int start_mode, const ModelRec& rec, hipStream_t on) const

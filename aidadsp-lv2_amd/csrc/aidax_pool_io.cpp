@@ -107,10 +107,11 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
         if (bytes && staged) std::memcpy(io.h_in, in, bytes);
         if (io.zero_copy) {
             // small blocks (the one-instance plugin): the pass reads its input straight from pinned host memory;
-            // a one-launch pass also writes its output there, a multi-launch pass works in place on d_out
-            const bool direct = p->single_launch(p->cur);
+            // a pass whose form allows it also writes its output there, every other pass works in place on d_out
+            const PassForm form = p->resolved_playing_form(n_frames);      // (once: launch executes this one)
+            const bool direct = form.host_in_place;
             if (direct && io.spin_wait && io.kernel_word) { end.word = io.hd_done; end.seq = io.done_seq + 1; }
-            rc = pool_process_prefix(p, io.hd_in, direct ? io.hd_out : io.d_out, n_frames, p->q, p->n_streams, &end);
+            rc = pool_process_prefix(p, io.hd_in, direct ? io.hd_out : io.d_out, n_frames, p->q, p->n_streams, &end, &form);
             if (rc != AIDAX_OK) return rc;
             if (!direct && bytes) HIP_TRY(hipMemcpyAsync(io.h_out, io.d_out, bytes, hipMemcpyDeviceToHost, p->q));
         } else {

@@ -37,49 +37,57 @@ StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload)
 
 namespace {
 
-// what prepare_impl uploads next to the slot: the weights in the chosen kernel's layout, k_lstm_q4's record where asked for; lp: the chained kernels serve the model if the LpGate allows
-struct Packed { std::vector<float> wp, wq4; bool lp = false; };
+// what prepare_impl uploads and allocates next to the slot: the weights in the chosen kernel's layout, k_lstm_q4's record where asked for; lp: the
+// model gets a hand-over ring (and, stacked, a hold on the device's LpGate) — k_mfma_ls's for ring_streams streams where ls, else k_mfma_lp's
+struct Packed { std::vector<float> wp, wq4; bool lp = false, ls = false; uint32_t ring_streams = 0; };
 
-// Which kernel form serves model m in pool p: fills the slot's host fields and packs the weights. No allocation, no launch (one
-// device-attribute query); what it sets of lp_split, lp_round_streams and lp_fused holds only if prepare_impl gets the chained kernel.
+// Which kernel form serves model m in pool p: fills the slot's host fields, its SlotForm among them, and packs the weights. No allocation, no
+// launch (one device-attribute query). A chained form holds while the slot has its ring (PassFacts::ring_ready): prepare_impl may not get one.
 int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed& pk)
 {
     std::vector<float>& wp = pk.wp;
     uint32_t state_floats = 0;
+    // Models of the reference's table on the matrix-core kernels (many_streams_form); AIDAX_KERNEL=quad|mfma force one, every other forced form none
+    auto many = [&p](int cell, int hidden) {
+        return p.force == Force::Quad ? MANY_QUAD : p.force == Force::Mfma ? MANY_MFMA : p.force == Force::None ? many_streams_form(cell, hidden, p.n_streams, p.cus, p.max_frames) : MANY_NONE;
+    };
     if (is_conv_model(*m)) {
         ms.kind = ModelSlot::CONV;
         wp = pack_conv(*m, &ms.cdesc, &state_floats);
-        ms.conv_mfma = p.force_form != 4 && convm_lds_bytes(ms.cdesc, p.ext_chunk()) <= 160 * 1024;
+        const bool conv_mfma = p.force != Force::Valu && convm_lds_bytes(ms.cdesc, p.ext_chunk()) <= 160 * 1024;
         // the stacks k_conv_ms admits run there (the contraction as bf16 term products: BASELINE cfg4 60 -> see profiles/r05_cfg4_*); its
         // per-layer histories live in the stream's state in ITS layout, so the choice holds for the life of the model in this pool
         // (warm-up, bare-model modes and passes all run the one kernel). AIDAX_CONV_MS=0 (test build): k_conv_mfma, the fp32 partner.
         const char* cms = AIDAX_HOOK_ENV("AIDAX_CONV_MS");
-        ms.conv_ms = ms.conv_mfma && ms.cdesc.ms_ok && !(cms && cms[0] == '0');
-        if (ms.conv_ms) state_floats = ms.cdesc.ms_state_floats;
+        const bool conv_ms = conv_mfma && ms.cdesc.ms_ok && !(cms && cms[0] == '0');
+        if (conv_ms) state_floats = ms.cdesc.ms_state_floats;
         // ... and of those, the stacks with a compiled geometry (conv_st_shape) take fused blocks of 64 / 128 / 256 frames through k_conv_st,
         // the streaming form on the same state (AIDAX_CONV_ST=0, test build: k_conv_ms for every block)
         const char* cst = AIDAX_HOOK_ENV("AIDAX_CONV_ST");
-        if (!ms.conv_ms || (cst && cst[0] == '0')) ms.cdesc.st_ok = 0;
+        if (cst && cst[0] == '0') ms.cdesc.st_ok = 0;
         // chain passes inside the conv launch while every workgroup of the pool is resident at once (their serial
         // latency is then paid once per block; in a second round of workgroups it would be paid again, and the packed
         // k_chain launches around the kernel are cheaper). AIDAX_CONV_FUSED=1 / 0 forces the form.
         const char* fused = AIDAX_HOOK_ENV("AIDAX_CONV_FUSED");
-        ms.conv_fused = ms.conv_mfma && (fused ? fused[0] != '0'
-                                               : static_cast<int>(p.n_streams) <= (ms.conv_ms ? convs_resident_streams(p.device, ms.cdesc.st_ok - 1) : convm_resident_streams(ms.cdesc, p.ext_chunk(), p.device)));
-        if (ms.conv_mfma && p.max_frames > 256) ms.conv_fused = true;      // long blocks go through in time slices: the one-launch form only
-        if (!ms.conv_mfma && conv_lds_bytes(ms.cdesc, p.max_frames) > 160 * 1024)
+        const bool conv_fused = conv_mfma && (p.max_frames > 256      // long blocks go through in time slices: the one-launch form only
+                                              || (fused ? fused[0] != '0'
+                                                        : static_cast<int>(p.n_streams) <= (conv_ms ? convs_resident_streams(p.device, ms.cdesc.st_ok - 1) : convm_resident_streams(ms.cdesc, p.ext_chunk(), p.device))));
+        ms.form = conv_ms ? SlotForm::conv_ms(conv_fused) : conv_mfma ? SlotForm::conv_mfma(conv_fused) : SlotForm::conv();
+        if (!conv_mfma && conv_lds_bytes(ms.cdesc, p.max_frames) > 160 * 1024)
             return fail(AIDAX_ERR_ARG, "conv model: pool max_frames too large for the LDS activation planes");
-    } else if (m->n_rnn == 1 && find_kernel(m->cell, m->hidden) && p.quad_for_table_model(m->cell, m->hidden) &&
+    } else if (m->n_rnn == 1 && find_kernel(m->cell, m->hidden) && many(m->cell, m->hidden) == MANY_QUAD &&
                chain_lds_bytes(p.max_frames) <= kChainLdsLimit && quad_lds_bytes(m->hidden, p.max_frames) <= 160 * 1024) {
         ms.kind = ModelSlot::QUAD;
+        ms.form = SlotForm::quad();
         wp = pack_quad(*m, &ms.qdesc.bias_off, &ms.qdesc.dense_off);
         state_floats = static_cast<uint32_t>(m->cell == AIDAX_CELL_LSTM ? 2 * m->hidden : m->hidden);
     } else if (mfma_form_fits(*m) && chain_lds_bytes(p.max_frames) <= kChainLdsLimit &&
-               (is_stack_model(*m) ? p.force_form != 4 : p.mfma_for_table_model(m->cell, m->hidden))) {
+               (is_stack_model(*m) ? p.force != Force::Valu : many(m->cell, m->hidden) == MANY_MFMA)) {
         ms.kind = ModelSlot::MFMA;
         wp = pack_mfma(*m, &ms.mdesc, &state_floats);
     } else if (is_stack_model(*m)) {
         ms.kind = ModelSlot::STACK;
+        ms.form = SlotForm::stack();
         wp = pack_stack(*m, &ms.sdesc, &state_floats);
         if (stack_lds_bytes(ms.sdesc, p.max_frames) > 160 * 1024)
             return fail(AIDAX_ERR_ARG, "stacked model: pool max_frames too large for the LDS block buffers");
@@ -90,6 +98,10 @@ int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed
         const int alt = (m->cell == AIDAX_CELL_LSTM && lstm_has_alt_pack(m->hidden)) ? lstm_pack_regs(m->hidden, false) * kWave : 0;   // a natural-order copy for k_nn
         if (static_cast<int>(wp.size()) != ms.kernel->pack_regs * kWave + m->hidden + 1 + alt) return fail(AIDAX_ERR_STATE, "weight pack size mismatch");
         state_floats = static_cast<uint32_t>(ms.kernel->state_floats);
+        // AIDAX_KERNEL=q4 (A/B runs and tests only): LSTM-32 snapshot models, four streams per workgroup with the cell on the
+        // matrix cores; the table kernels' record stays for warm-ups and the bare-model modes
+        if (q4_serves(m->cell, m->hidden, m->input_size) && p.force == Force::Q4 && q4_lds_bytes(m->hidden, p.max_frames) <= 64 * 1024) pk.wq4 = pack_q4(*m);
+        ms.form = SlotForm::table(pipe_resident_streams(ms.kernel, p.max_frames, p.device), split_form_pays(ms.kernel, p.max_frames), !pk.wq4.empty());
     }
     ms.nn_stride = (state_floats + 3u) & ~3u;
     ms.cell = m->cell;
@@ -99,8 +111,6 @@ int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed
     ms.in_gain = m->input_gain;
     ms.out_gain = m->output_gain;
     ms.model_sr = m->samplerate;
-    ms.pipe_capacity = ms.kernel ? pipe_resident_streams(ms.kernel, p.max_frames, p.device) : 0;
-    ms.split_pays = ms.kernel ? split_form_pays(ms.kernel, p.max_frames) : false;
     ms.has_model = true;
 
     // Stacked model: one workgroup per (16 streams, layer), chained through a ring in global memory — where that adds
@@ -139,31 +149,30 @@ int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed
     const size_t lp_blocks = (lp_groups + 7) / 8 * 8 * static_cast<size_t>(ms.mdesc.n_layers);
     const bool lp_pays = lp ? lp[0] != '0' : (lp_rounds_ok || ls_rounds || (ls_ok && !lp_chained) || lp_blocks <= static_cast<size_t>(cus));
     pk.lp = ms.kind == ModelSlot::MFMA && mfma_lp_serves(ms.mdesc) && lp_pays && mfma_lp_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
-    if (pk.lp) {
-        // stacked models whose split fragments fit the register file: the same hand-over with the contractions on the bf16 matrix
-        // pipe (k_mfma_ls; AIDAX_LP_SPLIT=0: the fp32 kernel, =9: every term product instead of six — A/B runs)
-        ms.lp_split = ls_ok ? (sp_env && sp_env[0] == '9' ? 9 : 6) : 0;
-        ms.lp_round_streams = ls_rounds ? static_cast<uint32_t>(round_groups) * kMfmaStreams : 0u;
-        const char* fu = AIDAX_HOOK_ENV("AIDAX_LP_FUSED");      // (=0: packed k_chain launches around the kernel, A/B runs)
-        ms.lp_fused = !(fu && fu[0] == '0') &&
-                      (ms.lp_split ? mfma_ls_fused_serves(ms.mdesc, p.max_frames) && mfma_ls_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024
-                                   : mfma_lp_fused_serves(ms.mdesc, p.max_frames) && mfma_lp_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024);
-    }
     if (ms.kind == ModelSlot::MFMA) {
         const char* gm = AIDAX_HOOK_ENV("AIDAX_GRU_GM");        // (=0: the four-rows-per-unit kernels; =f32: k_gru_gm with fp32 MFMAs — A/B runs)
-        ms.gru_gm = gru_gm_serves(ms.mdesc) && !(gm && gm[0] == '0') && gru_gm_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
         const char* np = AIDAX_HOOK_ENV("AIDAX_GS_PRODUCTS");   // (=9: every term product of the split operands instead of six)
-        ms.lstm_gs = lstm_gs_serves(ms.mdesc) && lstm_gs_pays(m->cell, m->hidden, p.n_streams, cus) && lstm_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024
-                         ? (np && np[0] == '9' ? 9 : 6) : 0;
-        ms.gru_gs = gru_gs_serves(ms.mdesc) && !(gm && (gm[0] == 'f' || gm[0] == '0')) && gru_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024
-                        ? (np && np[0] == '9' ? 9 : 6) : 0;
-        if (ms.gru_gs) ms.gru_gm = true;                       // (80 units: the split kernel only — the flag says "one-launch gate-major form")
-        else if (!gru_gm_serves(ms.mdesc)) ms.gru_gm = false;
+        const int gs_products = np && np[0] == '9' ? 9 : 6;
+        // stacked models whose split fragments fit the register file: the same hand-over with the contractions on the bf16 matrix
+        // pipe (k_mfma_ls; AIDAX_LP_SPLIT=0: the fp32 kernel, =9: every term product instead of six — A/B runs)
+        pk.ls = pk.lp && ls_ok;
+        pk.ring_streams = pk.ls && ls_rounds ? static_cast<uint32_t>(round_groups) * kMfmaStreams : p.n_streams;
+        const char* fu = AIDAX_HOOK_ENV("AIDAX_LP_FUSED");      // (=0: packed k_chain launches around the kernel, A/B runs)
+        const bool fused = !(fu && fu[0] == '0') &&
+                           (pk.ls ? mfma_ls_fused_serves(ms.mdesc, p.max_frames) && mfma_ls_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024
+                                  : mfma_lp_fused_serves(ms.mdesc, p.max_frames) && mfma_lp_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024);
+        // one-layer models, the whole run() in one launch: k_lstm_gs; k_gru_gs (80 units: the split kernel only) ahead of the fp32 k_gru_gm
+        // (such a slot still gets the ring and counters of pk.lp, which no pass of its form can use — a one-layer GRU on k_gru_gs is one:
+        // allocation as it was, left for a change of its own)
+        if (lstm_gs_serves(ms.mdesc) && lstm_gs_pays(m->cell, m->hidden, p.n_streams, cus) && lstm_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
+            ms.form = SlotForm::lstm_gs(gs_products);
+        else if (gru_gs_serves(ms.mdesc) && !(gm && (gm[0] == 'f' || gm[0] == '0')) && gru_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
+            ms.form = SlotForm::gru_gs(gs_products);
+        else if (gru_gm_serves(ms.mdesc) && !(gm && gm[0] == '0') && gru_gm_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
+            ms.form = SlotForm::gru_gm();
+        else
+            ms.form = pk.ls ? SlotForm::ls(sp_env && sp_env[0] == '9' ? 9 : 6, fused, ls_rounds ? pk.ring_streams : 0u) : pk.lp ? SlotForm::lp(fused) : SlotForm::mfma();
     }
-    // AIDAX_KERNEL=q4 (A/B runs and tests only): LSTM-32 snapshot models, four streams per workgroup with the cell on the
-    // matrix cores; the table kernels' record stays for warm-ups and the bare-model modes
-    if (ms.kind == ModelSlot::TABLE && q4_serves(m->cell, m->hidden, m->input_size) && p.force_form == 7 && q4_lds_bytes(m->hidden, p.max_frames) <= 64 * 1024)
-        pk.wq4 = pack_q4(*m);
     return AIDAX_OK;
 }
 
@@ -189,13 +198,10 @@ int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_stag
     const bool lp_chained = ms.mdesc.n_layers >= 2;       // (only a hand-over between layers needs the hold on the device's gate)
     if (pk.lp && !(lp_chained && p.lp_off.load()) && (!lp_chained || lp_gate().acquire(p.device, &p, &p.lp_off))) {
         if (lp_chained) ms.lp_owner = &p;
-        const uint32_t ring_streams = ms.lp_round_streams ? ms.lp_round_streams : p.n_streams;
-        const size_t ring_bytes = ms.lp_split ? mfma_ls_ring_bytes(ms.mdesc, ring_streams) : mfma_lp_ring_bytes(ms.mdesc, p.n_streams);
+        const size_t ring_bytes = pk.ls ? mfma_ls_ring_bytes(ms.mdesc, pk.ring_streams) : mfma_lp_ring_bytes(ms.mdesc, p.n_streams);
         HIP_TRY(hipMalloc(&ms.d_ring, ring_bytes));
         HIP_TRY(hipMalloc(&ms.d_counters, mfma_lp_counter_bytes(ms.mdesc, p.n_streams)));
         HIP_TRY(hipMemsetAsync(ms.d_counters, 0, mfma_lp_counter_bytes(ms.mdesc, p.n_streams), p.wq));
-    } else {
-        ms.lp_split = 0; ms.lp_round_streams = 0; ms.lp_fused = false;
     }
     HIP_TRY(hipMemcpyAsync(ms.d_wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
     if (!pk.wq4.empty()) {
@@ -519,22 +525,8 @@ AIDAX_API int aidax_model_conv_form(const aidax_model* m)
     return d.st_ok ? 4 : d.ms_ok ? 3 : 2;
 }
 
-AIDAX_API const char* aidax_pool_kernel_name(const aidax_pool* p)
-{
-    if (!(p && p->cur.has_model)) return "k_nomodel";
-    const ModelSlot& m = p->cur;
-    if (m.kind == ModelSlot::STACK) return "k_stack";
-    if (m.kind == ModelSlot::MFMA && m.lstm_gs) return "k_lstm_gs";
-    if (m.kind == ModelSlot::MFMA) return m.gru_gm ? (m.gru_gs ? "k_gru_gs" : "k_gru_gm") : !p->lp_in_use(m) ? "k_chain+k_mfma" : m.lp_split ? (m.mdesc.n_layers == 1 ? (m.lp_fused ? "k_mfma_ls1" : "k_chain+k_mfma_ls1") : m.lp_fused ? "k_mfma_ls" : "k_chain+k_mfma_ls") : m.lp_fused ? "k_mfma_lp" : "k_chain+k_mfma_lp";
-    if (m.kind == ModelSlot::QUAD) return "k_chain+k_quad";
-    if (m.kind == ModelSlot::CONV && m.conv_ms && m.conv_fused && m.cdesc.st_ok && p->max_frames >= 64) return "k_conv_st";      // (what a block of 64 / 128 / 256 frames runs; every other length: k_conv_ms)
-    if (m.kind == ModelSlot::CONV) return m.conv_ms ? (m.conv_fused ? "k_conv_ms" : "k_chain+k_conv_ms") : m.conv_fused ? "k_conv_mfma" : m.conv_mfma ? "k_chain+k_conv_mfma" : "k_conv";
-    if (p->bank.in_force()) return m.kernel->name_pipe_bank;      // a stream plays a bank slot: every pass is the bank kernel's
-    const int form = p->chain_form(m);
-    // (form 1: what a block of the pool's full length runs with the controls as they stand — k_*_pipe4 where it serves, k_*_pipe otherwise)
-    if (form == 1 && p->pipe4_serves(m, p->max_frames, m.input_size)) return m.kernel->name_pipe4;
-    return form == 3 ? "k_lstm_q4<32>" : form == 1 ? m.kernel->name_pipe : form == 2 ? m.kernel->name_split : m.kernel->name;
-}
+// What a MODE_CHAIN pass of the pool's full block length runs, with the controls, the bank and the chained kernels' flags as they stand
+AIDAX_API const char* aidax_pool_kernel_name(const aidax_pool* p) { return p ? p->playing_form(p->max_frames).name : "k_nomodel"; }
 
 AIDAX_API int aidax_model_forward(const aidax_model* m, int device_id, const float* X, float* y, uint32_t n, int unit_gains)
 {
