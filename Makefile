@@ -23,7 +23,7 @@ HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS) -fno-slp-vectorize
 
 HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_pool_model.cpp $(SRC)/aidax_pool_io.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_ir_stage.cpp $(SRC)/aidax_model_bank.cpp $(SRC)/aidax_rate.cpp $(SRC)/aidax_mix_book.cpp
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
-KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp.o $(OBJDIR)/aidax_tick.o $(OBJDIR)/aidax_mfmals.o $(OBJDIR)/aidax_mfmals2.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o $(OBJDIR)/aidax_mix.o $(OBJDIR)/aidax_bus_limit.o
+KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp.o $(OBJDIR)/aidax_tick.o $(OBJDIR)/aidax_mfmals.o $(OBJDIR)/aidax_mfmals2.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o $(OBJDIR)/aidax_mix.o $(OBJDIR)/aidax_bus_limit.o $(OBJDIR)/aidax_bus_reverb.o
 HDRS      := $(wildcard $(SRC)/*.h) include/aidax.h
 
 LV2SO := $(PKG)/lv2/rt-neural-generic.so
@@ -126,6 +126,14 @@ build/asan/asan_limit_harness: $(ASAN_LIMIT_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_LIMIT_SRCS) -o $@
 asan_limit: build/asan/asan_limit_harness
 
+# ... and the bus reverbs' host half (ReverbBook, aidax_reverb_stage.h: the records, the capacity, the dirty range, the position, the epochs and their refresh): tests/asan_reverb_harness.cpp, tests/test_asan_reverb.py
+ASAN_REVERB_SRCS := tests/asan_reverb_harness.cpp $(SRC)/aidax_model.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_dsp_host.cpp
+build/asan/asan_reverb_harness: $(ASAN_REVERB_SRCS) $(HDRS) $(SRC)/json_min.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_REVERB_SRCS) -o $@
+asan_reverb: build/asan/asan_reverb_harness
+
 # ... and the pass-form decision (aidax_pass_form.h: resolve_pass, a header without HIP): tests/form_harness.cpp, tests/test_pass_form_host.py
 build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_pass_form.h $(SRC)/aidax_layout.h
 	@mkdir -p build/asan
@@ -141,4 +149,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_form
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_form

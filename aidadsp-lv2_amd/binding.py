@@ -24,6 +24,7 @@ BUS_NONE = -1                     # AIDAX_BUS_NONE: a send that goes nowhere (th
 MAX_BUSES = 4096                  # AIDAX_MAX_BUSES
 ALL_BUSES = -1                    # AIDAX_ALL_BUSES: every bus's limiter
 BUS_LOOKAHEAD_MAX, BUS_HOLD_MAX = 512, 4096      # AIDAX_BUS_LOOKAHEAD_MAX, AIDAX_BUS_HOLD_MAX: frames
+BUS_REVERB_LINES, BUS_REVERB_MIN_DELAY, BUS_REVERB_MAX_DELAY = 8, 64, 32768      # AIDAX_BUS_REVERB_*: lines per bus, frames
 _fp = C.POINTER(C.c_float)
 
 
@@ -100,6 +101,17 @@ class BusMeter(C.Structure):
     """aidax_bus_meter: one bus's record (48 bytes)"""
     _fields_ = [("frames", C.c_uint64), ("passes", C.c_uint64), ("in_nonfinite", C.c_uint64), ("limited", C.c_uint64),
                 ("in_peak", C.c_float), ("out_peak", C.c_float), ("min_gain", C.c_float), ("reserved", C.c_float)]
+
+
+class BusReverbParams(C.Structure):
+    """aidax_bus_reverb_params: a bus reverb as a user sets it (decay time in s, room size, damping, levels, one of four delay tables)"""
+    _fields_ = [("rt60_s", C.c_float), ("size", C.c_float), ("damping", C.c_float), ("wet", C.c_float), ("dry", C.c_float), ("variant", C.c_uint32)]
+
+
+class BusReverbRec(C.Structure):
+    """aidax_bus_reverb_rec: the record k_bus_reverb reads (96 bytes), what aidax_bus_reverb_design makes of BusReverbParams at a sample rate"""
+    _fields_ = [("m", C.c_uint32 * 8), ("gq", C.c_float * 8), ("a", C.c_float), ("wet", C.c_float), ("dry", C.c_float),
+                ("on", C.c_uint32), ("epoch", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
 BUS_METER_DTYPE = np.dtype([("frames", "<u8"), ("passes", "<u8"), ("in_nonfinite", "<u8"), ("limited", "<u8"),
@@ -286,6 +298,14 @@ def lib() -> C.CDLL:
         L.aidax_pool_set_bus_limiter.argtypes = [vp, i32, C.POINTER(BusLimitParams)]
         L.aidax_pool_bus_limiter.argtypes = [vp, u32, C.POINTER(BusLimitParams), C.POINTER(C.c_int), C.POINTER(u32)]
         L.aidax_pool_read_bus_meters.argtypes = [vp, u32, u32, C.POINTER(BusMeter), C.c_int]
+    if hasattr(L, "aidax_pool_set_bus_reverbs"):  # (... or from before the bus reverbs)
+        L.aidax_bus_reverb_design.argtypes = [C.POINTER(BusReverbParams), C.c_double, C.POINTER(BusReverbRec)]
+        L.aidax_pool_set_bus_reverbs.argtypes = [vp, C.c_int, u32]
+        L.aidax_pool_bus_reverbs.argtypes = [vp]
+        L.aidax_pool_set_bus_reverb.argtypes = [vp, i32, C.POINTER(BusReverbParams)]
+        L.aidax_pool_set_bus_reverb_rec.argtypes = [vp, i32, C.POINTER(BusReverbRec)]
+        L.aidax_pool_bus_reverb.argtypes = [vp, u32, C.POINTER(BusReverbParams), C.POINTER(BusReverbRec), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+        L.aidax_pool_reset_bus_reverb.argtypes = [vp, i32]
     _lib = L
     return L
 
@@ -327,6 +347,13 @@ def gate_design(params: GateParams, samplerate: float) -> GateRec:
     """aidax_gate_design: the record of `params` at `samplerate` (pure, host only)"""
     out = GateRec()
     _check(lib().aidax_gate_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
+    return out
+
+
+def bus_reverb_design(params: BusReverbParams, samplerate: float) -> BusReverbRec:
+    """aidax_bus_reverb_design: the record of `params` at `samplerate` (pure, host only)"""
+    out = BusReverbRec()
+    _check(lib().aidax_bus_reverb_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
     return out
 
 
@@ -737,6 +764,33 @@ class Pool:
         out = np.zeros(max(count, 0), BUS_METER_DTYPE)
         _check(lib().aidax_pool_read_bus_meters(self.h, first, count, out.ctypes.data_as(C.POINTER(BusMeter)), 1 if clear else 0))
         return out
+
+    def set_bus_reverbs(self, on: bool, max_delay_frames: int = 4096):
+        """aidax_pool_set_bus_reverbs: the reverb stage between the buses and their limiters on or off (the first enabling call
+        allocates and fixes the delay capacity: a set-up side call)"""
+        _check(lib().aidax_pool_set_bus_reverbs(self.h, 1 if on else 0, max_delay_frames))
+
+    @property
+    def bus_reverbs(self) -> bool:
+        return bool(lib().aidax_pool_bus_reverbs(self.h))
+
+    def set_bus_reverb(self, params: Optional[BusReverbParams], bus: int = ALL_BUSES):
+        """aidax_pool_set_bus_reverb: the bus's (default: every bus's) reverb from the next pass on, None: off"""
+        _check(lib().aidax_pool_set_bus_reverb(self.h, bus, C.byref(params) if params is not None else None))
+
+    def set_bus_reverb_rec(self, rec: Optional[BusReverbRec], bus: int = ALL_BUSES):
+        """aidax_pool_set_bus_reverb_rec: the same with a record of the caller's own, None: off"""
+        _check(lib().aidax_pool_set_bus_reverb_rec(self.h, bus, C.byref(rec) if rec is not None else None))
+
+    def bus_reverb(self, bus: int):
+        """aidax_pool_bus_reverb: (the bus's BusReverbParams as last set, its BusReverbRec, whether its reverb is on, frames since its epoch)"""
+        out, rec, on, since = BusReverbParams(), BusReverbRec(), C.c_int(0), C.c_uint64(0)
+        _check(lib().aidax_pool_bus_reverb(self.h, bus, C.byref(out), C.byref(rec), C.byref(on), C.byref(since)))
+        return out, rec, bool(on.value), since.value
+
+    def reset_bus_reverb(self, bus: int = ALL_BUSES):
+        """aidax_pool_reset_bus_reverb: the bus's (default: every bus's) memories are cut at the next pass's first frame"""
+        _check(lib().aidax_pool_reset_bus_reverb(self.h, bus))
 
     def set_controls(self, c: Controls, stream: int = ALL_STREAMS):
         _check(lib().aidax_pool_set_controls(self.h, stream, C.byref(c)))

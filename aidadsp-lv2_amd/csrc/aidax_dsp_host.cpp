@@ -295,4 +295,43 @@ AIDAX_API int aidax_bus_limit_design(const aidax_bus_limit_params* params, doubl
     return AIDAX_OK;
 }
 
+// The record of a bus reverb (include/aidax.h, "Bus reverbs"), in fp64: eight delays out of the variant's table, scaled by size and rate
+// and made odd and distinct, each line's gain for the decay time over its own length, the damping as the FIR's coefficient.
+AIDAX_API int aidax_bus_reverb_design(const aidax_bus_reverb_params* params, double samplerate, aidax_bus_reverb_rec* out)
+{
+    using aidax::fail;
+    static const double base[4][AIDAX_BUS_REVERB_LINES] = {
+        { 1423, 1637, 1871, 2087, 2311, 2539, 2767, 2999 },
+        { 1493, 1693, 1913, 2129, 2357, 2591, 2803, 2971 },
+        { 1447, 1663, 1889, 2113, 2339, 2557, 2789, 2963 },
+        { 1481, 1709, 1931, 2141, 2371, 2579, 2819, 2953 },
+    };
+    if (!params || !out) return fail(AIDAX_ERR_ARG, "bus_reverb_design: null argument");
+    const aidax_bus_reverb_params& v = *params;
+    if (!(samplerate > 0.0) || !std::isfinite(samplerate)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: samplerate must be positive");
+    if (!(v.rt60_s >= 0.1f && v.rt60_s <= 20.f)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: rt60_s must be in [0.1, 20]");
+    if (!(v.size >= 0.05f && v.size <= 2.f)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: size must be in [0.05, 2]");
+    if (!(v.damping >= 0.f && v.damping <= 1.f)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: damping must be in [0, 1]");
+    if (!(std::fabs(v.wet) <= 4.f) || !(std::fabs(v.dry) <= 4.f)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: wet and dry must be finite and at most 4 in magnitude");
+    if (v.variant > 3u) return fail(AIDAX_ERR_ARG, "bus_reverb_design: variant must be 0 .. 3");
+    aidax_bus_reverb_rec r{};
+    for (uint32_t i = 0; i < AIDAX_BUS_REVERB_LINES; ++i) {
+        const double f = std::floor(base[v.variant][i] * static_cast<double>(v.size) * samplerate / 48000.0 + 0.5);
+        // (compared as fp64 ahead of the conversion: a delay of any size is refused, never wrapped)
+        if (!(f <= AIDAX_BUS_REVERB_MAX_DELAY)) return fail(AIDAX_ERR_ARG, "bus_reverb_design: a delay exceeds 32768 frames at this size and samplerate");
+        uint32_t m = std::max<uint32_t>(AIDAX_BUS_REVERB_MIN_DELAY, static_cast<uint32_t>(f)) | 1u;
+        for (uint32_t k = 0; k < i;)
+            if (r.m[k] == m) { m += 2u; k = 0; } else ++k;
+        if (m > AIDAX_BUS_REVERB_MAX_DELAY) return fail(AIDAX_ERR_ARG, "bus_reverb_design: a delay exceeds 32768 frames at this size and samplerate");
+        r.m[i] = m;
+        r.gq[i] = static_cast<float>(std::pow(10.0, -3.0 * static_cast<double>(m) / (static_cast<double>(v.rt60_s) * samplerate)) / std::sqrt(8.0));
+    }
+    r.a = static_cast<float>(static_cast<double>(v.damping) * 0.5);
+    r.wet = v.wet;
+    r.dry = v.dry;
+    r.on = 1u;
+    *out = r;
+    return AIDAX_OK;
+}
+
 }  // extern "C"

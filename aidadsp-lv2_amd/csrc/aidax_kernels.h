@@ -267,6 +267,28 @@ struct BusLimitArgs {
 };
 hipError_t launch_bus_limit(const BusLimitArgs& a, hipStream_t q);
 
+// The bus reverbs between k_mix and k_bus_limit (aidax_bus_reverb.hip, k_bus_reverb): one launch reverberates, in place, the block k_mix
+// wrote, [n_buses][n_frames], by the per-frame rule of include/aidax.h ("Bus reverbs"), a workgroup per bus. ReverbRec is
+// aidax_bus_reverb_rec, field for field. Each bus has eight rows of mask + 1 floats in `ring`, one per delay line: d_i of absolute frame k
+// lives in slot k & mask of row i, `pos` is the absolute frame (modulo 2^32) of the pass's first one, and a slot whose frame lies before
+// the record's epoch (compared modulo 2^32) reads as 0. A row holds max_delay + 1 frames of history next to the longest pass. A bus whose
+// record is off is not touched.
+constexpr uint32_t kReverbLines = 8, kReverbMinDelay = 64, kReverbMaxDelay = 32768;
+struct ReverbRec {
+    uint32_t m[kReverbLines];
+    float gq[kReverbLines];
+    float a, wet, dry;
+    uint32_t on, epoch, reserved[3];
+};
+static_assert(sizeof(ReverbRec) == 96, "a bus's reverb record is 96 bytes");
+struct BusReverbArgs {
+    float* block;                // [n_buses][n_frames]: what k_mix wrote, reverberated in place
+    float* ring;                 // [n_buses][8][mask + 1]
+    const ReverbRec* rec;        // [n_buses]
+    uint32_t n_buses, n_frames, mask, pos, max_delay;
+};
+hipError_t launch_bus_reverb(const BusReverbArgs& a, hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

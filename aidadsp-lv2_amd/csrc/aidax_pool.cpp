@@ -329,6 +329,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
         const bool limit_on = mix_on && p->limit.on;                   // the bus limiters: k_mix writes their raw side block, k_bus_limit the bus block
         if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s, limit_on ? p->limit.d_raw : nullptr);      // the buses: a gather over the block the pass returns
+        if (mix_on && p->reverb.on) p->reverb.after_mix(limit_on ? p->limit.d_raw : p->mix.d_bus, n_frames, s);      // the bus reverbs, in place on the block k_mix wrote
         if (limit_on) p->limit.after_mix(p->mix.d_bus, n_frames, s);
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
@@ -651,6 +652,89 @@ AIDAX_API int aidax_pool_read_bus_meters(aidax_pool* p, uint32_t first, uint32_t
     if (!l.enabled()) return fail(AIDAX_ERR_STATE, "bus limiting was never enabled (aidax_pool_set_bus_limiting)");
     if (count == 0 || first > l.book.n_buses || count > l.book.n_buses - first) return fail(AIDAX_ERR_ARG, "bus range out of the pool's buses");
     return p->on_own_stream([&]() -> int { l.read(first, count, out, clear != 0, p->q); return AIDAX_OK; });
+}
+
+// The bus reverbs (aidax_reverb_stage.h). The first aidax_pool_set_bus_reverbs with on != 0 is the set-up side's (it allocates);
+// everything else changes or reads host records of the audio side.
+AIDAX_API int aidax_pool_set_bus_reverbs(aidax_pool* p, int on, uint32_t max_delay_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
+    ReverbStage& r = p->reverb;
+    if (!on) {
+        r.on = false;                                       // (off before any on: nothing to change)
+        return AIDAX_OK;
+    }
+    if (max_delay_frames < AIDAX_BUS_REVERB_MIN_DELAY || max_delay_frames > AIDAX_BUS_REVERB_MAX_DELAY)
+        return fail(AIDAX_ERR_ARG, "the bus reverbs' delay capacity is 64 .. 32768 frames");
+    if (r.enabled()) {
+        if (max_delay_frames != r.book.max_delay) return fail(AIDAX_ERR_STATE, "the bus reverbs' delay capacity is fixed once set");
+        r.on = true;
+        return AIDAX_OK;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        r.enable(p->mix.book.n_buses, p->max_frames, max_delay_frames, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_bus_reverbs(const aidax_pool* p) { return p && p->reverb.on ? 1 : 0; }
+
+// the range of buses a call names, or an error
+static int reverb_buses(aidax_pool* p, int32_t bus, uint32_t* lo, uint32_t* hi)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    const ReverbStage& r = p->reverb;
+    if (!r.enabled()) return fail(AIDAX_ERR_STATE, "the bus reverbs were never enabled (aidax_pool_set_bus_reverbs)");
+    if (bus != AIDAX_ALL_BUSES && (bus < 0 || static_cast<uint32_t>(bus) >= r.book.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
+    *lo = bus == AIDAX_ALL_BUSES ? 0u : static_cast<uint32_t>(bus);
+    *hi = bus == AIDAX_ALL_BUSES ? r.book.n_buses : *lo + 1u;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_set_bus_reverb(aidax_pool* p, int32_t bus, const aidax_bus_reverb_params* params)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = reverb_buses(p, bus, &lo, &hi)) return rc;
+    aidax_bus_reverb_rec designed{};
+    if (params)
+        if (const int rc = aidax_bus_reverb_design(params, aidax_pool_samplerate(p), &designed)) return rc;
+    if (!p->reverb.book.set(lo, hi, params ? &designed : nullptr, params)) return fail(AIDAX_ERR_ARG, "a delay of the reverb exceeds the capacity of aidax_pool_set_bus_reverbs");
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_set_bus_reverb_rec(aidax_pool* p, int32_t bus, const aidax_bus_reverb_rec* rec)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = reverb_buses(p, bus, &lo, &hi)) return rc;
+    if (rec && !ReverbBook::valid(*rec)) return fail(AIDAX_ERR_ARG, "bus reverb record: delays 64 .. 32768, 0 <= gq < 1/sqrt(8), 0 <= a <= 0.5, wet and dry finite and at most 4 in magnitude");
+    if (!p->reverb.book.set(lo, hi, rec, nullptr)) return fail(AIDAX_ERR_ARG, "a delay of the reverb exceeds the capacity of aidax_pool_set_bus_reverbs");
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_bus_reverb(const aidax_pool* p, uint32_t bus, aidax_bus_reverb_params* params, aidax_bus_reverb_rec* rec, int* on, uint64_t* frames_since_epoch)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (bus >= p->mix.book.n_buses) return fail(AIDAX_ERR_ARG, "bus out of range");
+    const ReverbStage& r = p->reverb;
+    const bool is_on = r.enabled() && r.book.h_rec[bus].on;
+    if (params) *params = is_on ? r.book.params[bus] : aidax_bus_reverb_params{};
+    if (rec) {
+        *rec = aidax_bus_reverb_rec{};
+        if (is_on) std::memcpy(rec, &r.book.h_rec[bus], sizeof *rec);
+    }
+    if (on) *on = is_on ? 1 : 0;
+    if (frames_since_epoch) *frames_since_epoch = is_on ? r.book.since_epoch(bus) : 0u;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_reset_bus_reverb(aidax_pool* p, int32_t bus)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = reverb_buses(p, bus, &lo, &hi)) return rc;
+    p->reverb.book.reset(lo, hi);
+    return AIDAX_OK;
 }
 
 AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode) { return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr); }

@@ -17,6 +17,7 @@
 #include "aidax_stream_stages.h"
 #include "aidax_mix_stage.h"
 #include "aidax_limit_stage.h"
+#include "aidax_reverb_stage.h"
 
 namespace aidax {
 
@@ -213,6 +214,7 @@ struct aidax_pool {
     MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
     GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
     MixStage mix;                    // the mix buses behind the last stage (aidax_mix_stage.h; nothing until the first aidax_pool_set_buses with a count)
+    ReverbStage reverb;              // the bus reverbs between k_mix and k_bus_limit (aidax_reverb_stage.h; nothing until the first aidax_pool_set_bus_reverbs(1, ..))
     LimitStage limit;                // the bus limiters and bus meters behind k_mix (aidax_limit_stage.h; nothing until the first aidax_pool_set_bus_limiting(1, ..))
     // aidax_pool_register_host: page-locked ranges of the caller's memory (copies to and from them need no staging)
     struct HostRange { char* base; size_t bytes; };
@@ -360,6 +362,7 @@ struct aidax_pool {
         gate.release();
         mix.release();
         limit.release();
+        reverb.release();
         meter.release();
         if (d_ctl) (void)hipFree(d_ctl);
         if (d_st) (void)hipFree(d_st);

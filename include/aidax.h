@@ -770,15 +770,103 @@ AIDAX_API int      aidax_pool_set_bus_limiter(aidax_pool* p, int32_t bus, const 
 AIDAX_API int      aidax_pool_bus_limiter(const aidax_pool* p, uint32_t bus, aidax_bus_limit_params* out, int* on, uint32_t* latency_frames);
 AIDAX_API int      aidax_pool_read_bus_meters(aidax_pool* p, uint32_t first, uint32_t count, aidax_bus_meter* out, int clear);
 
+/* Bus reverbs: a room on every mix bus — a feedback delay network of eight delay lines with an orthogonal feedback matrix, computed
+ * where the bus block is (k_bus_reverb, aidax_bus_reverb.hip), behind k_mix and ahead of k_bus_limit. Opt-in: a pool that never calls
+ * aidax_pool_set_bus_reverbs, or has the stage off, allocates and launches exactly what it did before these calls existed, bit for bit.
+ * While the stage and the buses are on, one launch of k_bus_reverb behind k_mix of every pass of n_frames > 0 works in place on the
+ * block k_mix wrote (the limiters' raw side block while they are on, else the pool's bus block): the limiters and their meters, and
+ * aidax_pool_read_buses, aidax_pool_buses_device and aidax_pool_process_buses, then see the REVERBERATED block. A bus whose reverb is
+ * OFF (the default) keeps the bits k_mix wrote, NaN included.
+ * The rule, normative (tests/reverbhelp.py restates it in numpy; the kernel agrees with it bit for bit). Each bus has a record
+ * (aidax_bus_reverb_rec): eight delays m[i] in frames (AIDAX_BUS_REVERB_MIN_DELAY = 64 <= m[i] <= the pool's delay capacity), eight
+ * feedback gains gq[i] (fp32, 0 <= gq[i] < 1/sqrt(8)), a damping a (fp32, 0 <= a <= 0.5), wet and dry (fp32, finite, magnitude <= 4),
+ * on, and an epoch, a frame position modulo 2^32. x[n] is the SANITISED raw bus sample of absolute frame n: what k_mix produced, with
+ * NaN and +-Inf replaced by +0.0f and then clamped to +-2^64. d_i[j] is line i's memory at absolute frame j; it is 0 for every frame
+ * before the record's epoch. Every operation below is ONE fp32 operation rounded to nearest; there is no fma anywhere. Per frame n, for
+ * i = 0 .. 7:
+ *     s_i = d_i[n - m_i]        t_i = d_i[n - m_i - 1]                      (the taps)
+ *     f_i = s_i + a * (t_i - s_i)                                           (the damping: a 2-tap FIR of magnitude <= 1 at every frequency;
+ *                                                                            deliberately not a one-pole, which would chain the frames)
+ *     h   = the unnormalised Hadamard butterfly of f in three stages with strides 1, 2 and 4: in each stage the element whose stride
+ *           bit is clear becomes lo + hi and its partner lo - hi (the factor 1/sqrt(8) is inside gq)
+ *     d_i[n] = x[n] + gq_i * h_i                                            (the write)
+ *     w   = ((s_0 - s_1) + (s_2 - s_3)) + ((s_4 - s_5) + (s_6 - s_7))       (the wet sum)
+ *     out[n] = dry * x[n] + wet * w
+ * Why the state stays finite: write g_i = sqrt(8) gq_i < 1 and g_max for the largest. The butterfly is sqrt(8) times an orthogonal
+ * matrix, so the feedback path of a frame is an orthogonal mix, scaled per line by g_i <= g_max, of FIR outputs no larger than the
+ * larger of their two taps: round the loop every component of the signal loses at least the factor g_max at every frequency, and by
+ * the small-gain argument the energy the lines hold is bounded by that of the input over 1 - g_max. The input is clamped to 2^64, so
+ * the lines stay some sixty binary orders below the fp32 range; each rounding moves a value by at most 2^-24 of itself, which a loop
+ * gain of 1 - 1e-5 or less (every designed record: rt60 <= 20 s) absorbs.
+ * Independence: frame n reads nothing younger than n - min m_i, so the frames n .. n + K - 1 are independent of one another for
+ * K <= min m_i. The rule depends neither on how a pass is cut into chunks nor on how the host cuts the signal into blocks.
+ * The memories move only with reverberated passes: not with a pass of 0 frames, not while the buses or the stage are off (frames
+ * mixed meanwhile never enter the lines). The epoch is set to the next pass's first frame — the tail is cut, and the change is NOT
+ * click-free — when a bus's reverb goes on, when any m[i] changes, and by aidax_pool_reset_bus_reverb. A change of only gq, a, wet or
+ * dry keeps the memories and acts at the block boundary.
+ * Position wrap: the stage stays right beyond 2^32 issued frames. The device compares positions modulo 2^32, so the host moves an epoch
+ * that has fallen 2^30 frames behind forward to the longest admitted delay + 1 behind the position (any epoch older than that gives
+ * the same result): one record upload every few hours.
+ * aidax_bus_reverb_design     pure, host only, any thread: the record of `params` at `samplerate`, in fp64. rt60_s 0.1 .. 20, size
+ *                             0.05 .. 2, damping 0 .. 1, wet and dry finite with magnitude <= 4, variant 0 .. 3. m_i = max(64,
+ *                             floor(base[variant][i] * size * samplerate / 48000 + 0.5)) | 1, then + 2 while equal to an earlier
+ *                             line's; base is four fixed tables of eight lengths between 1400 and 3000 frames (variant 0: 1423, 1637,
+ *                             1871, 2087, 2311, 2539, 2767, 2999), and two buses with different variants make a decorrelated stereo
+ *                             pair. gq_i = (float)(pow(10, -3 m_i / (rt60_s * samplerate)) / sqrt(8)), a = (float)(damping * 0.5),
+ *                             on = 1, epoch = 0 (the pool sets it). AIDAX_ERR_ARG for a null pointer, anything outside the ranges (a NaN
+ *                             is), a samplerate that is not positive, a delay beyond AIDAX_BUS_REVERB_MAX_DELAY; `out` is untouched then.
+ * aidax_pool_set_bus_reverbs  SET-UP side. The first call with on != 0 allocates everything the feature ever needs — eight ring rows
+ *                             per bus (zeroed), the records (every reverb off) and their snapshots — all or nothing, fixes the delay
+ *                             capacity (max_delay_frames 64 .. 32768: no record with a longer delay is accepted; a ring row is the
+ *                             smallest power of two >= capacity + 1 + max_frames floats), switches the stage on, and may wait. Later
+ *                             calls only flip a host record of the audio side: on != 0 with another capacity is AIDAX_ERR_STATE, on
+ *                             == 0 ignores it. AIDAX_ERR_STATE before aidax_pool_set_buses, AIDAX_ERR_ARG for a null pool or a capacity
+ *                             out of range.
+ * aidax_pool_bus_reverbs      1 while the stage is on, else 0 (0 for a null pool).
+ * aidax_pool_set_bus_reverb   AUDIO thread, between passes: `bus` (AIDAX_ALL_BUSES: every bus) is reverberated with `params`, designed
+ *                             at aidax_pool_samplerate, from the next pass on; params == NULL switches its reverb off. Host records
+ *                             only (they reach the device from a ring of snapshots ahead of the next reverberated pass): no allocation,
+ *                             no free, no wait. AIDAX_ERR_ARG for a null pool, a bus out of range, whatever aidax_bus_reverb_design
+ *                             refuses and a delay beyond the capacity (a refused call changes nothing); AIDAX_ERR_STATE before the
+ *                             stage's first enabling.
+ * aidax_pool_set_bus_reverb_rec  the same with a record of the caller's own (a host's own tuning); its `on` and `epoch` are ignored.
+ *                             AIDAX_ERR_ARG also for a record outside the conditions above; rec == NULL switches the reverb off.
+ * aidax_pool_bus_reverb       the bus's host record (any pointer may be NULL): its parameters as last set (zeros while off or set by a
+ *                             record), its record (zeros while off), whether its reverb is on, and the reverberated frames issued
+ *                             since its epoch (0 while off).
+ * aidax_pool_reset_bus_reverb AUDIO thread, between passes: the memories of `bus` (AIDAX_ALL_BUSES: every bus) are cut at the next
+ *                             pass's first frame (its epoch is set). Host records only. Errors as aidax_pool_set_bus_reverb's.
+ * Not covered: hub seats and so the LV2 shell, click-free changes, a wet-only return to another bus, modulation of the delays, a
+ * meter of its own (the limiter's bus meter sees the reverberated block). */
+#define AIDAX_BUS_REVERB_LINES 8
+#define AIDAX_BUS_REVERB_MIN_DELAY 64
+#define AIDAX_BUS_REVERB_MAX_DELAY 32768
+typedef struct { float rt60_s, size, damping, wet, dry; uint32_t variant; } aidax_bus_reverb_params;
+typedef struct {
+    uint32_t m[AIDAX_BUS_REVERB_LINES];    /* the delays in frames                                 */
+    float    gq[AIDAX_BUS_REVERB_LINES];   /* the feedback gains, 1/sqrt(8) included               */
+    float    a, wet, dry;
+    uint32_t on;
+    uint32_t epoch;                        /* the pool's: every d_i is 0 before this frame         */
+    uint32_t reserved[3];
+} aidax_bus_reverb_rec;                    /* 96 bytes, no padding */
+AIDAX_API int      aidax_bus_reverb_design(const aidax_bus_reverb_params* params, double samplerate, aidax_bus_reverb_rec* out);
+AIDAX_API int      aidax_pool_set_bus_reverbs(aidax_pool* p, int on, uint32_t max_delay_frames);
+AIDAX_API int      aidax_pool_bus_reverbs(const aidax_pool* p);
+AIDAX_API int      aidax_pool_set_bus_reverb(aidax_pool* p, int32_t bus, const aidax_bus_reverb_params* params);
+AIDAX_API int      aidax_pool_set_bus_reverb_rec(aidax_pool* p, int32_t bus, const aidax_bus_reverb_rec* rec);
+AIDAX_API int      aidax_pool_bus_reverb(const aidax_pool* p, uint32_t bus, aidax_bus_reverb_params* params, aidax_bus_reverb_rec* rec, int* on, uint64_t* frames_since_epoch);
+AIDAX_API int      aidax_pool_reset_bus_reverb(aidax_pool* p, int32_t bus);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, set_bus_limiting after its first enabling call, set_bus_limiter, read_bus_meters, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, set_bus_limiting after its first enabling call, set_bus_limiter, read_bus_meters, set_bus_reverbs after its first enabling call, set_bus_reverb, set_bus_reverb_rec, reset_bus_reverb, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side) and the first aidax_pool_set_bus_limiting with on != 0 (it allocates; aidax_pool_bus_limiting and aidax_pool_bus_limiter read host records of the audio side); aidax_gate_design, aidax_mix_gain and aidax_bus_limit_design are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side) and the first aidax_pool_set_bus_limiting with on != 0 (it allocates; aidax_pool_bus_limiting and aidax_pool_bus_limiter read host records of the audio side) and the first aidax_pool_set_bus_reverbs with on != 0 (it allocates; aidax_pool_bus_reverbs and aidax_pool_bus_reverb read host records of the audio side); aidax_gate_design, aidax_mix_gain, aidax_bus_limit_design and aidax_bus_reverb_design are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
  * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses / aidax_pool_read_bus_meters wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate), a changed mix plan (after a set_send) and changed bus limiter records (after a set_bus_limiter), go
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate), a changed mix plan (after a set_send) changed bus limiter records (after a set_bus_limiter) and changed bus reverb records (after a set_bus_reverb, a set_bus_reverb_rec or a reset_bus_reverb, and once in 2^30 frames when an epoch is moved forward), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
