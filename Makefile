@@ -134,6 +134,14 @@ build/asan/asan_reverb_harness: $(ASAN_REVERB_SRCS) $(HDRS) $(SRC)/json_min.h
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ $(ASAN_REVERB_SRCS) -o $@
 asan_reverb: build/asan/asan_reverb_harness
 
+# ... and the owning types (aidax_hip_host.h: DevBuf, PinnedBuf, Event, Stream; SnapshotRing and GateStage::enable built from them) over a
+# stub runtime that the harness itself defines, so no HIP library is linked: tests/asan_own_harness.cpp, tests/test_asan_own.py
+build/asan/asan_own_harness: tests/asan_own_harness.cpp $(HDRS)
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ tests/asan_own_harness.cpp -o $@
+asan_own: build/asan/asan_own_harness
+
 # ... and the pass-form decision (aidax_pass_form.h: resolve_pass, a header without HIP): tests/form_harness.cpp, tests/test_pass_form_host.py
 build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_pass_form.h $(SRC)/aidax_layout.h
 	@mkdir -p build/asan
@@ -149,4 +157,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_form
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_own asan_form

@@ -1,6 +1,8 @@
 // aidax_hip_host.h — what every host source that issues HIP calls for a pool shares: the error plumbing (HIP_TRY throws HipFail, guarded
-// turns it into AIDAX_ERR_DEVICE) and, in the test build, the call counting behind aidax_test_hip_calls. Include it last: its macros
-// rename the calls of the source that follow it (aidax_snapshot_ring.h, aidax_model_bank.h, aidax_stream_stages.h and aidax_pool.h include it and are counted: they go last too).
+// turns it into AIDAX_ERR_DEVICE), the owners of device memory, pinned memory, events and streams (DevBuf, PinnedBuf, Event, Stream: the
+// ONE place that frees them) and, in the test build, the call counting behind aidax_test_hip_calls. Include it last: its macros rename the
+// calls of the source that follow it, the owners' among them (aidax_snapshot_ring.h, aidax_model_bank.h, aidax_stream_stages.h and
+// aidax_pool.h include it and are counted: they go last too).
 #pragma once
 
 #include <hip/hip_runtime_api.h>
@@ -92,6 +94,152 @@ inline void hip_check(hipError_t e, const char* what)
     }
 }
 #define HIP_TRY(x) aidax::hip_check((x), #x)
+
+// Who owns what on the device: a hipMalloc block (DevBuf), a pinned host block (PinnedBuf), an event without timing (Event) and a stream
+// (Stream). Move-only; an empty one issues no HIP call when it is reset or destroyed (the call-count tests depend on it); alloc / create
+// throw HipFail and leave the owner as it was. Kernel arguments and launchers take get() (a Stream converts). A struct's members are destroyed in reverse
+// declaration order: one that declares its Streams first frees every block ahead of its streams.
+template <class T>
+class DevBuf {
+    T* p_ = nullptr;
+
+  public:
+    DevBuf() = default;
+    DevBuf(DevBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    DevBuf& operator=(DevBuf&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    // A block whose pointer travelled through a host-only record (IrSlot, BankSlot: the books swap them and the sanitizer harnesses fill
+    // them with made-up addresses, so they stay plain) comes back under an owner where the record's life ends
+    static DevBuf adopt(T* p) { DevBuf b; b.p_ = p; return b; }
+    void alloc(size_t count)
+    {
+        T* p = nullptr;
+        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count));
+        reset();
+        p_ = p;
+    }
+    T* get() const { return p_; }
+    T* release() { T* p = p_; p_ = nullptr; return p; }      // (into such a record)
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset()
+    {
+        if (p_) (void)hipFree(p_);
+        p_ = nullptr;
+    }
+};
+
+template <class T>
+class PinnedBuf {
+    T* p_ = nullptr;
+
+  public:
+    PinnedBuf() = default;
+    PinnedBuf(PinnedBuf&& o) noexcept : p_(o.p_) { o.p_ = nullptr; }
+    PinnedBuf& operator=(PinnedBuf&& o) noexcept
+    {
+        if (this != &o) { reset(); p_ = o.p_; o.p_ = nullptr; }
+        return *this;
+    }
+    ~PinnedBuf() { reset(); }
+    void alloc(size_t count)
+    {
+        T* p = nullptr;
+        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p), sizeof(T) * count, hipHostMallocDefault));
+        reset();
+        p_ = p;
+    }
+    T* get() const { return p_; }
+    T* device() const                                        // the block as the device addresses it (zero-copy passes, the fault and completion words)
+    {
+        T* d = nullptr;
+        HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&d), p_, 0));
+        return d;
+    }
+    explicit operator bool() const { return p_ != nullptr; }
+    void reset()
+    {
+        if (p_) (void)hipHostFree(p_);
+        p_ = nullptr;
+    }
+};
+
+class Event {
+    hipEvent_t e_ = nullptr;
+
+  public:
+    Event() = default;
+    Event(Event&& o) noexcept : e_(o.e_) { o.e_ = nullptr; }
+    Event& operator=(Event&& o) noexcept
+    {
+        if (this != &o) { reset(); e_ = o.e_; o.e_ = nullptr; }
+        return *this;
+    }
+    ~Event() { reset(); }
+    void create()
+    {
+        hipEvent_t e = nullptr;
+        HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+        reset();
+        e_ = e;
+    }
+    hipEvent_t get() const { return e_; }
+    explicit operator bool() const { return e_ != nullptr; }
+    void reset()
+    {
+        if (e_) (void)hipEventDestroy(e_);
+        e_ = nullptr;
+    }
+};
+
+class Stream {
+    hipStream_t s_ = nullptr;
+
+  public:
+    Stream() = default;
+    Stream(Stream&& o) noexcept : s_(o.s_) { o.s_ = nullptr; }
+    Stream& operator=(Stream&& o) noexcept
+    {
+        if (this != &o) { reset(); s_ = o.s_; o.s_ = nullptr; }
+        return *this;
+    }
+    ~Stream() { reset(); }
+    void create()                                            // non-blocking, default priority
+    {
+        hipStream_t s = nullptr;
+        HIP_TRY(hipStreamCreateWithFlags(&s, hipStreamNonBlocking));
+        reset();
+        s_ = s;
+    }
+    void create(int priority)
+    {
+        hipStream_t s = nullptr;
+        HIP_TRY(hipStreamCreateWithPriority(&s, hipStreamNonBlocking, priority));
+        reset();
+        s_ = s;
+    }
+    operator hipStream_t() const { return s_; }              // (a stream is named at every call that issues work: it reads as the handle)
+    void reset()
+    {
+        if (s_) (void)hipStreamDestroy(s_);
+        s_ = nullptr;
+    }
+};
+
+// A stage's read: `bytes` from d to its pinned staging h behind everything on q, `clear_behind` (the clear of what was copied, or nothing)
+// behind the copy, the wait, then out of the staging (zero bytes: the wait alone)
+template <class Clear>
+void read_back(void* out, void* h, const void* d, size_t bytes, hipStream_t q, Clear&& clear_behind)
+{
+    if (bytes) HIP_TRY(hipMemcpyAsync(h, d, bytes, hipMemcpyDeviceToHost, q));
+    clear_behind();
+    HIP_TRY(hipStreamSynchronize(q));
+    if (bytes) std::memcpy(out, h, bytes);
+}
+inline void read_back(void* out, void* h, const void* d, size_t bytes, hipStream_t q) { read_back(out, h, d, bytes, q, [] {}); }
 
 template <class F>
 int guarded(F&& f)

@@ -36,6 +36,14 @@ struct aidax_model {
 
 namespace aidax {
 
+// the smallest power of two that is at least `need` (the rows of the history rings: a position wraps with a mask)
+inline uint32_t pow2_at_least(uint32_t need)
+{
+    uint32_t row = 1u;
+    while (row < need) row <<= 1;
+    return row;
+}
+
 void set_error(const std::string& msg);
 int  fail(int code, const std::string& msg);
 

@@ -151,7 +151,7 @@ struct IrStage {
         max_frames_ = max_frames; cus_ = cus; wq_ = worker;
         plan.init(n_streams);
     }
-    void release();
+    ~IrStage();                                              // (aidax_ir_stage.cpp: the history and the fragments go back)
     // the longest IR the stage takes (aidax_pool_set_ir_capacity, set-up side: fixed once the first prepare has sized the history with it)
     std::atomic<uint32_t> capacity{kIrMaxTaps};
     bool has_history() const { return pub_.load(std::memory_order_acquire) != nullptr; }

@@ -40,10 +40,7 @@ struct LimitBook {
     // (2 L + H - 1 frames) next to a pass of max_frames
     static uint32_t ring_row(uint32_t lookahead_cap, uint32_t hold_cap, uint32_t max_frames)
     {
-        const uint32_t need = 2u * lookahead_cap + hold_cap - 1u + max_frames;
-        uint32_t row = 1u;
-        while (row < need) row <<= 1;
-        return row;
+        return pow2_at_least(2u * lookahead_cap + hold_cap - 1u + max_frames);
     }
     bool fits(const aidax_bus_limit_rec& r) const { return r.lookahead >= 1u && r.lookahead <= max_lookahead && r.hold <= max_hold; }
     // Buses [lo, hi) get the designed record and its parameters, or (designed == nullptr) their limiters go off. false, and nothing
@@ -68,45 +65,35 @@ struct LimitBook {
 // bus block. HIP failures leave as HipFail.
 struct LimitStage {
     LimitBook book;
-    float* d_raw = nullptr;          // the raw bus block k_mix writes while the stage is on: [n_buses][max_frames]; nullptr: never enabled
-    float* d_ring = nullptr;         // [n_buses][ring_row]: the sanitised samples of every bus's past
-    LimitRec* d_rec = nullptr;       // [n_buses]
-    BusMeterRec* d_meter = nullptr;  // [n_buses]
-    BusMeterRec* h_meter = nullptr;  // pinned: [n_buses] staging of the read, then [n_buses] cleared records (what a clear copies up)
+    DevBuf<float> d_raw;             // the raw bus block k_mix writes while the stage is on: [n_buses][max_frames]; empty: never enabled
+    DevBuf<float> d_ring;            // [n_buses][ring_row]: the sanitised samples of every bus's past
+    DevBuf<LimitRec> d_rec;          // [n_buses]
+    DevBuf<BusMeterRec> d_meter;     // [n_buses]
+    PinnedBuf<BusMeterRec> h_meter;  // [n_buses] staging of the read, then [n_buses] cleared records (what a clear copies up)
     SnapshotRing ring;
     uint32_t ring_row = 0;
     bool on = false;
 
-    bool enabled() const { return d_raw != nullptr; }
+    bool enabled() const { return static_cast<bool>(d_raw); }
     // the side block, the rings (zeroed), the records (all off), the meter records (cleared), the snapshots and the pinned staging; all or nothing
     void enable(uint32_t n_buses, uint32_t max_frames, uint32_t lookahead_cap, uint32_t hold_cap, hipStream_t q)
     {
         const size_t n = n_buses;
         LimitStage fresh;
         fresh.ring_row = LimitBook::ring_row(lookahead_cap, hold_cap, max_frames);
-        const size_t ring_bytes = sizeof(float) * n * fresh.ring_row;
-        auto build = [&]() -> hipError_t {
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.d_raw), sizeof(float) * n * max_frames);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_ring), ring_bytes);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_rec), sizeof(LimitRec) * n);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_meter), sizeof(BusMeterRec) * n);
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&fresh.h_meter), sizeof(BusMeterRec) * 2u * n, hipHostMallocDefault);
-            if (e != hipSuccess) return e;
-            for (size_t b = 0; b < n; ++b) { fresh.h_meter[n + b] = BusMeterRec{}; fresh.h_meter[n + b].min_gain = 1.f; }
-            e = hipMemsetAsync(fresh.d_ring, 0, ring_bytes, q);
-            if (e == hipSuccess) e = hipMemsetAsync(fresh.d_rec, 0, sizeof(LimitRec) * n, q);
-            if (e == hipSuccess) e = hipMemcpyAsync(fresh.d_meter, fresh.h_meter + n, sizeof(BusMeterRec) * n, hipMemcpyHostToDevice, q);
-            if (e == hipSuccess) e = hipStreamSynchronize(q);      // (a pass on a caller's stream must find them cleared)
-            return e;
-        };
-        try {
-            HIP_TRY(build());
-            fresh.ring.alloc(sizeof(LimitRec) * n);
-            fresh.book.init(n_buses, lookahead_cap, hold_cap);
-        } catch (...) {
-            fresh.release();
-            throw;
-        }
+        fresh.d_raw.alloc(n * max_frames);
+        fresh.d_ring.alloc(n * fresh.ring_row);
+        fresh.d_rec.alloc(n);
+        fresh.d_meter.alloc(n);
+        fresh.h_meter.alloc(2u * n);
+        BusMeterRec* cleared = fresh.h_meter.get() + n;
+        for (size_t b = 0; b < n; ++b) { cleared[b] = BusMeterRec{}; cleared[b].min_gain = 1.f; }
+        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * n * fresh.ring_row, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(LimitRec) * n, q));
+        HIP_TRY(hipMemcpyAsync(fresh.d_meter.get(), cleared, sizeof(BusMeterRec) * n, hipMemcpyHostToDevice, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them cleared)
+        fresh.ring.alloc(sizeof(LimitRec) * n);
+        fresh.book.init(n_buses, lookahead_cap, hold_cap);
         fresh.on = true;
         *this = std::move(fresh);
     }
@@ -114,9 +101,9 @@ struct LimitStage {
     // into the pool's bus block, then the ring position moves on (a pass that fails on its way here leaves it where it was)
     void after_mix(float* d_bus, uint32_t n_frames, hipStream_t s)
     {
-        ring.upload_dirty(d_rec, book.h_rec.data(), book.dirty, s);
+        ring.upload_dirty(d_rec.get(), book.h_rec.data(), book.dirty, s);
         BusLimitArgs a{};
-        a.raw = d_raw; a.out = d_bus; a.ring = d_ring; a.rec = d_rec; a.meter = d_meter;
+        a.raw = d_raw.get(); a.out = d_bus; a.ring = d_ring.get(); a.rec = d_rec.get(); a.meter = d_meter.get();
         a.n_buses = book.n_buses; a.n_frames = n_frames; a.mask = ring_row - 1u; a.pos = book.pos;
         HIP_TRY(launch_bus_limit(a, s));
         book.advance(n_frames);
@@ -125,19 +112,8 @@ struct LimitStage {
     void read(uint32_t first, uint32_t count, aidax_bus_meter* out, bool clear, hipStream_t q)
     {
         const size_t bytes = sizeof(BusMeterRec) * count;
-        HIP_TRY(hipMemcpyAsync(h_meter + first, d_meter + first, bytes, hipMemcpyDeviceToHost, q));
-        if (clear) HIP_TRY(hipMemcpyAsync(d_meter + first, h_meter + book.n_buses + first, bytes, hipMemcpyHostToDevice, q));
-        HIP_TRY(hipStreamSynchronize(q));
-        std::memcpy(out, h_meter + first, bytes);
-    }
-    void release()
-    {
-        if (d_raw) (void)hipFree(d_raw);
-        if (d_ring) (void)hipFree(d_ring);
-        if (d_rec) (void)hipFree(d_rec);
-        if (d_meter) (void)hipFree(d_meter);
-        if (h_meter) (void)hipHostFree(h_meter);
-        ring.release();
+        read_back(out, h_meter.get() + first, d_meter.get() + first, bytes, q,
+                  [&] { if (clear) HIP_TRY(hipMemcpyAsync(d_meter.get() + first, h_meter.get() + book.n_buses + first, bytes, hipMemcpyHostToDevice, q)); });
     }
 };
 

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <utility>
 #include <vector>
 
 #include "aidax_snapshot_ring.h"
@@ -63,35 +64,26 @@ struct MixBook {
 // of the audio side, and a pass issued while it is set ends with k_mix over the block it returns. HIP failures leave as HipFail.
 struct MixStage {
     MixBook book;
-    float* d_bus = nullptr;          // the bus block: [n_buses][max_frames] floats, rows dense at the last mixed pass's n_frames; nullptr: never enabled
-    uint8_t* d_plan = nullptr;       // bus_start and entries (MixBook::serialise)
-    float* h_bus = nullptr;          // pinned staging of the reads, the bus block's size
+    DevBuf<float> d_bus;             // the bus block: [n_buses][max_frames] floats, rows dense at the last mixed pass's n_frames; empty: never enabled
+    DevBuf<uint8_t> d_plan;          // bus_start and entries (MixBook::serialise)
+    PinnedBuf<float> h_bus;          // pinned staging of the reads, the bus block's size
     SnapshotRing ring;
     bool on = false;
     uint32_t last_frames = 0;        // n_frames of the last pass mixed (0: none yet)
 
-    bool enabled() const { return d_bus != nullptr; }
+    bool enabled() const { return static_cast<bool>(d_bus); }
     // the bus block (zeroed), the plan, its snapshots and the pinned staging of the reads; all or nothing
     void enable(uint32_t n_streams, uint32_t max_frames, uint32_t n_buses, hipStream_t q)
     {
         MixStage fresh;
-        const size_t block = sizeof(float) * n_buses * static_cast<size_t>(max_frames);
-        try {
-            fresh.book.init(n_streams, n_buses);
-            auto build = [&]() -> hipError_t {
-                hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.d_bus), block);
-                if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_plan), fresh.book.plan_bytes());
-                if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&fresh.h_bus), block, hipHostMallocDefault);
-                if (e == hipSuccess) e = hipMemsetAsync(fresh.d_bus, 0, block, q);
-                if (e == hipSuccess) e = hipStreamSynchronize(q);      // (a pass on a caller's stream must find it zeroed)
-                return e;
-            };
-            HIP_TRY(build());
-            fresh.ring.alloc(fresh.book.plan_bytes());
-        } catch (...) {
-            fresh.release();
-            throw;
-        }
+        const size_t block = n_buses * static_cast<size_t>(max_frames);
+        fresh.book.init(n_streams, n_buses);
+        fresh.d_bus.alloc(block);
+        fresh.d_plan.alloc(fresh.book.plan_bytes());
+        fresh.h_bus.alloc(block);
+        HIP_TRY(hipMemsetAsync(fresh.d_bus.get(), 0, sizeof(float) * block, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find it zeroed)
+        fresh.ring.alloc(fresh.book.plan_bytes());
         fresh.on = true;
         *this = std::move(fresh);
     }
@@ -103,13 +95,13 @@ struct MixStage {
         if (book.dirty) {
             book.rebuild();
             const size_t bytes = book.serialise(ring.take());
-            ring.send(d_plan, 0, bytes, s);
+            ring.send(d_plan.get(), 0, bytes, s);
         }
         MixArgs a{};
-        a.bus_start = reinterpret_cast<const uint32_t*>(d_plan);
-        a.entries = reinterpret_cast<const MixEntry*>(d_plan + book.entries_off());
+        a.bus_start = reinterpret_cast<const uint32_t*>(d_plan.get());
+        a.entries = reinterpret_cast<const MixEntry*>(d_plan.get() + book.entries_off());
         a.y = d_out;
-        a.out = d_raw ? d_raw : d_bus;
+        a.out = d_raw ? d_raw : d_bus.get();
         a.n_buses = book.n_buses; a.n_streams = n_active; a.n_frames = n_frames; a.k_off = book.since_build;
         HIP_TRY(launch_mix(a, book.max_entries, s));
         book.advance(n_active, n_frames);
@@ -118,17 +110,8 @@ struct MixStage {
     // rows [first, first + count) of the last mixed pass's bus block, count * last_frames floats, behind everything on q (waits)
     void read(uint32_t first, uint32_t count, float* out, hipStream_t q)
     {
-        const size_t at = static_cast<size_t>(first) * last_frames, bytes = sizeof(float) * count * static_cast<size_t>(last_frames);
-        if (bytes) HIP_TRY(hipMemcpyAsync(h_bus + at, d_bus + at, bytes, hipMemcpyDeviceToHost, q));
-        HIP_TRY(hipStreamSynchronize(q));
-        if (bytes) std::memcpy(out, h_bus + at, bytes);
-    }
-    void release()
-    {
-        if (d_bus) (void)hipFree(d_bus);
-        if (d_plan) (void)hipFree(d_plan);
-        if (h_bus) (void)hipHostFree(h_bus);
-        ring.release();
+        const size_t at = static_cast<size_t>(first) * last_frames;
+        read_back(out, h_bus.get() + at, d_bus.get() + at, sizeof(float) * count * static_cast<size_t>(last_frames), q);
     }
 };
 

@@ -58,10 +58,10 @@ struct ModelBank {
 class ModelBankStage {
     struct Shared {
         ModelBank host;
-        ModelRec* d_rec = nullptr;
+        DevBuf<ModelRec> d_rec;
         SnapshotRing ring;
         explicit Shared(uint32_t n) : host(n) {}
-        ~Shared() { if (d_rec) (void)hipFree(d_rec); ring.release(); }
+        ~Shared() { for (BankSlot& k : host.slot) DevBuf<float>::adopt(k.d_wpack); }      // (the slots' weights: BankSlot is a record of the host half)
     };
     std::atomic<Shared*> pub_{nullptr};
 
@@ -78,13 +78,15 @@ class ModelBankStage {
             wpack = pack_weights(*m);
             if (wpack.size() != pack_floats) throw std::runtime_error("weight pack size mismatch");
             k = bank_slot_of(*m);
-            HIP_TRY(hipMalloc(&k.d_wpack, wpack.size() * sizeof(float)));
+            DevBuf<float> w;
+            w.alloc(wpack.size());
+            k.d_wpack = w.release();                      // (the staged object's from here: staged_release)
             HIP_TRY(hipMemcpyAsync(k.d_wpack, wpack.data(), wpack.size() * sizeof(float), hipMemcpyHostToDevice, wq));
         }
         if (!adopt()) {
             auto nb = std::make_unique<Shared>(n_streams);
-            HIP_TRY(hipMalloc(&nb->d_rec, sizeof(ModelRec) * n_streams));
-            HIP_TRY(hipMemsetAsync(nb->d_rec, 0, sizeof(ModelRec) * n_streams, wq));
+            nb->d_rec.alloc(n_streams);
+            HIP_TRY(hipMemsetAsync(nb->d_rec.get(), 0, sizeof(ModelRec) * n_streams, wq));
             nb->ring.alloc(sizeof(ModelRec) * n_streams);
             HIP_TRY(hipStreamSynchronize(wq));
             pub_.store(nb.release(), std::memory_order_release);
@@ -95,15 +97,10 @@ class ModelBankStage {
     const ModelRec* flush(hipStream_t s)
     {
         Shared* b = pub_.load(std::memory_order_acquire);
-        b->ring.upload_dirty(b->d_rec, b->host.rec.data(), b->host.dirty, s);
-        return b->d_rec;
+        b->ring.upload_dirty(b->d_rec.get(), b->host.rec.data(), b->host.dirty, s);
+        return b->d_rec.get();
     }
-    void release()
-    {
-        std::unique_ptr<Shared> b(pub_.exchange(nullptr));
-        for (int k = 0; b && k < AIDAX_MODEL_SLOTS; ++k)
-            if (b->host.slot[k].d_wpack) (void)hipFree(b->host.slot[k].d_wpack);
-    }
+    ~ModelBankStage() { delete pub_.exchange(nullptr); }
 };
 
 }  // namespace aidax

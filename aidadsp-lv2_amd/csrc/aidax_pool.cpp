@@ -246,13 +246,13 @@ hipError_t aidax_pool::launch(const ModelSlot& m, const LaunchArgs& a, hipStream
         case PassKern::Pipe4: { LaunchArgs b = a; hipEvent_t done = take_end_markers(f, b); return launch_pipe4_kernel(table, b, s, done); }
         // (the model bank in force — pool_process_prefix set the records)
         case PassKern::PipeBank: { LaunchArgs b = a; hipEvent_t done = take_end_markers(f, b); return launch_pipe_bank_kernel(table, b, s, done); }
-        case PassKern::Q4: { LaunchArgs b = a; b.wpack = m.d_wq4; return launch_q4_kernel(m.hidden, b, s); }
+        case PassKern::Q4: { LaunchArgs b = a; b.wpack = m.d_wq4.get(); return launch_q4_kernel(m.hidden, b, s); }
         case PassKern::Nn: return launch_nn_kernel(table, a, s);
         case PassKern::Quad: return launch_quad_kernel(m.cell, m.hidden, a, m.qdesc, s);
         case PassKern::Mfma: return launch_mfma_kernel(a, m.mdesc, s);
-        case PassKern::MfmaLp: return launch_mfma_lp_kernel(a, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, s, whole_run);
+        case PassKern::MfmaLp: return launch_mfma_lp_kernel(a, m.mdesc, m.d_ring.get(), m.d_counters.get(), hd_lp_fault, s, whole_run);
         case PassKern::MfmaLs:
-            return in_pieces(f, [&](const LaunchArgs& r) { return launch_mfma_ls_kernel(r, m.mdesc, m.d_ring, m.d_counters, hd_lp_fault, m.form.products(), s, whole_run); });
+            return in_pieces(f, [&](const LaunchArgs& r) { return launch_mfma_ls_kernel(r, m.mdesc, m.d_ring.get(), m.d_counters.get(), hd_lp_fault, m.form.products(), s, whole_run); });
         case PassKern::GruGm: return launch_gru_gm_kernel(a, m.mdesc, s);
         case PassKern::GruGs: return launch_gru_gs_kernel(a, m.mdesc, m.form.products(), s);
         case PassKern::LstmGs: return launch_lstm_gs_kernel(a, m.mdesc, m.form.products(), s);
@@ -308,7 +308,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         p->enter_stream(s);
         p->flush_ctl(s);
         p->note_lp_give_up();                                          // (ahead of the form's resolution in launch)
-        LaunchArgs a = p->args(p->cur, p->d_st, d_in, d_out, n_frames, MODE_CHAIN);
+        LaunchArgs a = p->args(p->cur, p->d_st.get(), d_in, d_out, n_frames, MODE_CHAIN);
         a.n_streams = n_active;
         if (p->bank.in_force()) a.bank = p->bank.flush(s);           // the records this pass plays, ahead of it on its stream
         // with an IR history the pass ends behind the IR stage: its end markers (the submit path's event, the blocking path's completion
@@ -322,15 +322,15 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on || meter_on || mix_on) end = nullptr;                // (the markers are not handed down: nullptr to launch)
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) p->meter.launch_in(d_in, n_active, n_frames, s);  // (ahead of the pass: it may work in place)
-        a.in = p->gate.before_pass(d_in, p->d_ctl, n_active, n_frames, s);      // the gated block, where a gate is on
+        a.in = p->gate.before_pass(d_in, p->d_ctl.get(), n_active, n_frames, s);      // the gated block, where a gate is on
         HIP_TRY(p->launch(p->cur, a, s, end, form));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
         const bool limit_on = mix_on && p->limit.on;                   // the bus limiters: k_mix writes their raw side block, k_bus_limit the bus block
-        if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s, limit_on ? p->limit.d_raw : nullptr);      // the buses: a gather over the block the pass returns
-        if (mix_on && p->reverb.on) p->reverb.after_mix(limit_on ? p->limit.d_raw : p->mix.d_bus, n_frames, s);      // the bus reverbs, in place on the block k_mix wrote
-        if (limit_on) p->limit.after_mix(p->mix.d_bus, n_frames, s);
+        if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s, limit_on ? p->limit.d_raw.get() : nullptr);      // the buses: a gather over the block the pass returns
+        if (mix_on && p->reverb.on) p->reverb.after_mix(limit_on ? p->limit.d_raw.get() : p->mix.d_bus.get(), n_frames, s);      // the bus reverbs, in place on the block k_mix wrote
+        if (limit_on) p->limit.after_mix(p->mix.d_bus.get(), n_frames, s);
         if (n_frames != 0) p->any_pass = true;
         return AIDAX_OK;
     });
@@ -396,41 +396,37 @@ AIDAX_API int aidax_pool_create(uint32_t n_streams, uint32_t max_frames, double 
         p->gain_coef = exp_smoother_coef(static_cast<float>(host_samplerate), 0.1f);
         p->force = parse_force(AIDAX_HOOK_ENV("AIDAX_KERNEL"));
         if (const char* t = AIDAX_HOOK_ENV("AIDAX_TUNE")) p->tune = std::atoi(t);
-        try {
-            HIP_TRY(hipSetDevice(device_id));
-            HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, device_id));
-            // the audio side's stream outranks the worker's: a pass must not queue behind a warm-up for its CUs
-            int prio_least = 0, prio_greatest = 0;
-            HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
-            HIP_TRY(hipStreamCreateWithPriority(&p->q, hipStreamNonBlocking, prio_greatest));
-            HIP_TRY(hipStreamCreateWithPriority(&p->wq, hipStreamNonBlocking, prio_least));
-            { const char* sp = std::getenv("AIDAX_SPIN_WAIT"); p->spin_collect = !(sp && sp[0] == '0'); }
-            p->keep_warm = keep_warm().acquire(device_id);
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&p->h_lp_fault), 8192, hipHostMallocDefault));     // the fault word + the time stamps of scratch/lp_trace.py, r05_modes.py
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&p->hd_lp_fault), p->h_lp_fault, 0));
-            *p->h_lp_fault = 0;
-            HIP_TRY(hipEventCreateWithFlags(&p->ev_x, hipEventDisableTiming));
-            HIP_TRY(hipEventCreateWithFlags(&p->ev_adopt, hipEventDisableTiming));
-            HIP_TRY(hipMalloc(&p->d_ctl, sizeof(StreamCtl) * n_streams));
-            HIP_TRY(hipMalloc(&p->d_st, sizeof(StreamState) * n_streams));
-            p->io.alloc(sizeof(float) * n_streams * static_cast<size_t>(max_frames), device_id);
-            p->ctl_ring.alloc(sizeof(StreamCtl) * n_streams);
-            p->ir.init(n_streams, max_frames, p->cus, p->wq);
-            p->controls.resize(n_streams);
-            for (auto& c : p->controls) aidax_controls_default(&c);
-            p->loading.assign(n_streams, 1);
-            p->forced_off.assign(n_streams, 0);
-            p->h_ctl.resize(n_streams);
-            p->refresh_all();
-            // instantiate(), rt-neural-generic.cpp:283-321: preGain target 1 cleared, masterGain target 0 cleared,
-            // biquad z = 0, no model, loading = true
-            HIP_TRY(launch_init_streams(p->d_st, n_streams, p->q));
-            HIP_TRY(hipStreamSynchronize(p->q));
-            p->last_stream = p->q;
-        } catch (...) {
-            p->release();
-            throw;
-        }
+        // (a failure from here on: ~aidax_pool and the owning members give back what was made, the streams last)
+        HIP_TRY(hipSetDevice(device_id));
+        HIP_TRY(hipDeviceGetAttribute(&p->cus, hipDeviceAttributeMultiprocessorCount, device_id));
+        // the audio side's stream outranks the worker's: a pass must not queue behind a warm-up for its CUs
+        int prio_least = 0, prio_greatest = 0;
+        HIP_TRY(hipDeviceGetStreamPriorityRange(&prio_least, &prio_greatest));
+        p->q.create(prio_greatest);
+        p->wq.create(prio_least);
+        { const char* sp = std::getenv("AIDAX_SPIN_WAIT"); p->spin_collect = !(sp && sp[0] == '0'); }
+        p->keep_warm = keep_warm().acquire(device_id);
+        p->h_lp_fault.alloc(2048);                              // (8192 bytes) the fault word + the time stamps of scratch/lp_trace.py, r05_modes.py
+        p->hd_lp_fault = p->h_lp_fault.device();
+        *p->h_lp_fault.get() = 0;
+        p->ev_x.create();
+        p->ev_adopt.create();
+        p->d_ctl.alloc(n_streams);
+        p->d_st.alloc(n_streams);
+        p->io.alloc(n_streams * static_cast<size_t>(max_frames), device_id);
+        p->ctl_ring.alloc(sizeof(StreamCtl) * n_streams);
+        p->ir.init(n_streams, max_frames, p->cus, p->wq);
+        p->controls.resize(n_streams);
+        for (auto& c : p->controls) aidax_controls_default(&c);
+        p->loading.assign(n_streams, 1);
+        p->forced_off.assign(n_streams, 0);
+        p->h_ctl.resize(n_streams);
+        p->refresh_all();
+        // instantiate(), rt-neural-generic.cpp:283-321: preGain target 1 cleared, masterGain target 0 cleared,
+        // biquad z = 0, no model, loading = true
+        HIP_TRY(launch_init_streams(p->d_st.get(), n_streams, p->q));
+        HIP_TRY(hipStreamSynchronize(p->q));
+        p->last_stream = p->q;
         *out = p.release();
         return AIDAX_OK;
     });
@@ -445,9 +441,10 @@ AIDAX_API void aidax_pool_destroy(aidax_pool* p)
     if (p->wq) (void)hipStreamSynchronize(p->wq);
     if (p->pipe.q_up) (void)hipStreamSynchronize(p->pipe.q_up);
     if (p->pipe.q_down) (void)hipStreamSynchronize(p->pipe.q_down);
-    p->release();
-    if (p->keep_warm) keep_warm().release(p->device);
+    const bool warm = p->keep_warm;
+    const int device = p->device;
     delete p;
+    if (warm) keep_warm().release(device);
 }
 
 AIDAX_API uint32_t aidax_pool_streams(const aidax_pool* p) { return p ? p->n_streams : 0; }
@@ -459,7 +456,7 @@ AIDAX_API double aidax_pool_samplerate(const aidax_pool* p) { return p ? p->host
 AIDAX_API int aidax_pool_set_metering(aidax_pool* p, int on)
 {
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
-    if (!on || p->meter.d_rec) {
+    if (!on || p->meter.enabled()) {
         p->meter.on = on != 0;
         return AIDAX_OK;
     }
@@ -477,15 +474,25 @@ AIDAX_API int aidax_pool_read_meters(aidax_pool* p, uint32_t first, uint32_t cou
 {
     if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
     if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
-    if (!p->meter.d_rec) return fail(AIDAX_ERR_STATE, "metering was never enabled (aidax_pool_set_metering)");
+    if (!p->meter.enabled()) return fail(AIDAX_ERR_STATE, "metering was never enabled (aidax_pool_set_metering)");
     return p->on_own_stream([&]() -> int { p->meter.read(first, count, out, clear != 0, p->q); return AIDAX_OK; });
+}
+
+// the streams or buses [lo, hi) of n that a call names by one index or by AIDAX_ALL_STREAMS / AIDAX_ALL_BUSES; false: out of range
+static_assert(static_cast<int>(AIDAX_ALL_STREAMS) == static_cast<int>(AIDAX_ALL_BUSES), "one 'all' value for both");
+static bool named_range(int32_t index, uint32_t n, uint32_t* lo, uint32_t* hi)
+{
+    if (index != AIDAX_ALL_STREAMS && (index < 0 || static_cast<uint32_t>(index) >= n)) return false;
+    *lo = index == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(index);
+    *hi = index == AIDAX_ALL_STREAMS ? n : *lo + 1u;
+    return true;
 }
 
 AIDAX_API int aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_gate_params* params)
 {
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
-    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
-        return fail(AIDAX_ERR_ARG, "stream out of range");
+    uint32_t lo = 0, hi = 0;
+    if (!named_range(stream, p->n_streams, &lo, &hi)) return fail(AIDAX_ERR_ARG, "stream out of range");
     aidax_gate_rec designed{};
     if (params)
         if (const int rc = aidax_gate_design(params, aidax_pool_samplerate(p), &designed)) return rc;
@@ -495,7 +502,6 @@ AIDAX_API int aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_gat
         const int rc = guarded([&]() -> int { HIP_TRY(hipSetDevice(p->device)); g.enable(p->n_streams, p->max_frames, p->q); return AIDAX_OK; });
         if (rc != AIDAX_OK) return rc;
     }
-    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
     const auto& restart = g.set(lo, hi, params ? &designed : nullptr, params);
     if (restart.empty()) return AIDAX_OK;
     return p->on_own_stream([&]() -> int {
@@ -547,15 +553,14 @@ AIDAX_API uint32_t aidax_pool_buses(const aidax_pool* p) { return p ? p->mix.boo
 AIDAX_API int aidax_pool_set_send(aidax_pool* p, int32_t stream, uint32_t send, int32_t bus, float gain, uint32_t ramp_frames)
 {
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
-    if (stream != AIDAX_ALL_STREAMS && (stream < 0 || static_cast<uint32_t>(stream) >= p->n_streams))
-        return fail(AIDAX_ERR_ARG, "stream out of range");
+    uint32_t lo = 0, hi = 0;
+    if (!named_range(stream, p->n_streams, &lo, &hi)) return fail(AIDAX_ERR_ARG, "stream out of range");
     if (send >= AIDAX_SENDS) return fail(AIDAX_ERR_ARG, "send out of range");
     float checked = 0.f;
     if (const int rc = aidax_mix_gain(0.f, gain, ramp_frames, 0, &checked)) return rc;      // (the gain and the ramp length, by the one rule)
     MixBook& b = p->mix.book;
     if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
     if (bus != AIDAX_BUS_NONE && (bus < 0 || static_cast<uint32_t>(bus) >= b.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
-    const uint32_t lo = stream == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(stream), hi = stream == AIDAX_ALL_STREAMS ? p->n_streams : lo + 1u;
     for (uint32_t s = lo; s < hi; ++s) b.set(s, send, bus, gain, ramp_frames);
     return AIDAX_OK;
 }
@@ -588,7 +593,7 @@ AIDAX_API int aidax_pool_buses_device(aidax_pool* p, float** d_ptr)
 {
     if (!p || !d_ptr) return fail(AIDAX_ERR_ARG, "null argument");
     if (!p->mix.enabled()) return fail(AIDAX_ERR_STATE, "the pool has no buses (aidax_pool_set_buses)");
-    *d_ptr = p->mix.d_bus;
+    *d_ptr = p->mix.d_bus.get();
     return AIDAX_OK;
 }
 
@@ -624,11 +629,11 @@ AIDAX_API int aidax_pool_set_bus_limiter(aidax_pool* p, int32_t bus, const aidax
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
     LimitStage& l = p->limit;
     if (!l.enabled()) return fail(AIDAX_ERR_STATE, "bus limiting was never enabled (aidax_pool_set_bus_limiting)");
-    if (bus != AIDAX_ALL_BUSES && (bus < 0 || static_cast<uint32_t>(bus) >= l.book.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
+    uint32_t lo = 0, hi = 0;
+    if (!named_range(bus, l.book.n_buses, &lo, &hi)) return fail(AIDAX_ERR_ARG, "bus out of range");
     aidax_bus_limit_rec designed{};
     if (params)
         if (const int rc = aidax_bus_limit_design(params, aidax_pool_samplerate(p), &designed)) return rc;
-    const uint32_t lo = bus == AIDAX_ALL_BUSES ? 0u : static_cast<uint32_t>(bus), hi = bus == AIDAX_ALL_BUSES ? l.book.n_buses : lo + 1u;
     if (!l.book.set(lo, hi, params ? &designed : nullptr, params)) return fail(AIDAX_ERR_ARG, "the limiter's look-ahead or hold exceeds the capacities of aidax_pool_set_bus_limiting");
     return AIDAX_OK;
 }
@@ -687,10 +692,7 @@ static int reverb_buses(aidax_pool* p, int32_t bus, uint32_t* lo, uint32_t* hi)
     if (!p) return fail(AIDAX_ERR_ARG, "null pool");
     const ReverbStage& r = p->reverb;
     if (!r.enabled()) return fail(AIDAX_ERR_STATE, "the bus reverbs were never enabled (aidax_pool_set_bus_reverbs)");
-    if (bus != AIDAX_ALL_BUSES && (bus < 0 || static_cast<uint32_t>(bus) >= r.book.n_buses)) return fail(AIDAX_ERR_ARG, "bus out of range");
-    *lo = bus == AIDAX_ALL_BUSES ? 0u : static_cast<uint32_t>(bus);
-    *hi = bus == AIDAX_ALL_BUSES ? r.book.n_buses : *lo + 1u;
-    return AIDAX_OK;
+    return named_range(bus, r.book.n_buses, lo, hi) ? AIDAX_OK : fail(AIDAX_ERR_ARG, "bus out of range");
 }
 
 AIDAX_API int aidax_pool_set_bus_reverb(aidax_pool* p, int32_t bus, const aidax_bus_reverb_params* params)
@@ -774,10 +776,10 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
     if (start_mode != AIDAX_START_WARMUP && start_mode != AIDAX_START_RESET) return fail(AIDAX_ERR_ARG, "bad start_mode");
     return p->on_own_stream([&]() -> int {
         const ModelSlot& m = p->cur;
-        HIP_TRY(launch_init_streams(p->d_st + stream, 1, p->q));      // instantiate(), :283-321
+        HIP_TRY(launch_init_streams(p->d_st.get() + stream, 1, p->q));      // instantiate(), :283-321
         p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
         p->gate.clear_states(stream, 1, p->q);                         // ... and its gate starts at unity gain, hold expired
-        if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st + stream, p_targets[0], p_targets[1], p->q));
+        if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st.get() + stream, p_targets[0], p_targets[1], p->q));
         const ModelBank* b = p->bank.adopt();                         // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
         if (m.has_model) p->fresh_stream_model(m, stream, start_mode, b && b->assign[stream] >= 0 ? ModelBank::rec_of(b->slot[b->assign[stream]]) : m.rec(), p->q);
         p->loading[stream] = m.has_model ? 0 : 1;
@@ -797,14 +799,14 @@ int pool_adopt_stream_dsp(aidax_pool* dst, uint32_t ds, aidax_pool* src, uint32_
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(dst->device));
         hipStream_t from = src->last_stream ? src->last_stream : src->q;
-        HIP_TRY(hipEventRecord(src->ev_adopt, from));
+        HIP_TRY(hipEventRecord(src->ev_adopt.get(), from));
         dst->enter_stream(dst->q);
-        HIP_TRY(hipStreamWaitEvent(dst->q, src->ev_adopt, 0));
-        HIP_TRY(launch_adopt_dsp(dst->d_st + ds, src->d_st + ss, dst->q));
+        HIP_TRY(hipStreamWaitEvent(dst->q, src->ev_adopt.get(), 0));
+        HIP_TRY(launch_adopt_dsp(dst->d_st.get() + ds, src->d_st.get() + ss, dst->q));
         if (src != dst) {                                   // src must not overwrite the record before the copy has read it:
-            HIP_TRY(hipEventRecord(dst->ev_adopt, dst->q));  // its next operation waits for the copy (the stream is parked or
+            HIP_TRY(hipEventRecord(dst->ev_adopt.get(), dst->q));  // its next operation waits for the copy (the stream is parked or
             src->enter_stream(src->q);                       // detached by then, but a later occupant of the seat is reset on src->q)
-            HIP_TRY(hipStreamWaitEvent(src->q, dst->ev_adopt, 0));
+            HIP_TRY(hipStreamWaitEvent(src->q, dst->ev_adopt.get(), 0));
         }
         return AIDAX_OK;
     });
@@ -818,7 +820,7 @@ int pool_read_stream_state(aidax_pool* p, uint32_t stream, StreamState* out)
         HIP_TRY(hipSetDevice(p->device));
         p->sync_issued();
         HIP_TRY(hipStreamSynchronize(p->q));
-        HIP_TRY(hipMemcpy(out, p->d_st + stream, sizeof(StreamState), hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(out, p->d_st.get() + stream, sizeof(StreamState), hipMemcpyDeviceToHost));
         return AIDAX_OK;
     });
 }
@@ -831,7 +833,7 @@ int pool_peek_stream_state(aidax_pool* p, uint32_t stream, StreamState* pinned_o
 {
     if (!p || !pinned_out || stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
     return p->on_own_stream([&]() -> int {
-        HIP_TRY(hipMemcpyAsync(pinned_out, p->d_st + stream, sizeof(StreamState), hipMemcpyDeviceToHost, p->q));
+        HIP_TRY(hipMemcpyAsync(pinned_out, p->d_st.get() + stream, sizeof(StreamState), hipMemcpyDeviceToHost, p->q));
         HIP_TRY(hipEventRecord(static_cast<hipEvent_t>(done_event), p->q));
         return AIDAX_OK;
     });
@@ -868,7 +870,7 @@ AIDAX_API int aidax_pool_import_stream_dsp(aidax_pool* p, uint32_t stream, const
         st.pre_mem = in->pre_mem; st.master_mem = in->master_mem;
         st.pre_tgt = in->pre_target; st.master_tgt = in->master_target;
         st.pending &= ~static_cast<uint32_t>(PEND_ACTIVATE);
-        HIP_TRY(hipMemcpy(p->d_st + stream, &st, sizeof(StreamState), hipMemcpyHostToDevice));
+        HIP_TRY(hipMemcpy(p->d_st.get() + stream, &st, sizeof(StreamState), hipMemcpyHostToDevice));
         return AIDAX_OK;
     });
 }
@@ -911,7 +913,7 @@ AIDAX_API int aidax_pool_activate(aidax_pool* p, int32_t stream)
     return p->on_own_stream([&]() -> int {
         // paramFirstRun is only re-armed when a model exists (rt-neural-generic.cpp:344-351)
         const uint32_t bits = PEND_ACTIVATE | (p->cur.has_model ? PEND_PARAM_FIRST : 0u);
-        HIP_TRY(launch_set_pending(p->d_st, p->n_streams, stream, bits, p->q));
+        HIP_TRY(launch_set_pending(p->d_st.get(), p->n_streams, stream, bits, p->q));
         return AIDAX_OK;
     });
 }
@@ -944,7 +946,7 @@ AIDAX_API int aidax_pool_read_state(aidax_pool* p, uint32_t stream, int layer, f
             lstm = m.cell == AIDAX_CELL_LSTM;
         }
         const uint32_t n = H < cap ? H : cap;
-        const float* base = m.d_nn + static_cast<size_t>(stream) * m.nn_stride + off;
+        const float* base = m.d_nn.get() + static_cast<size_t>(stream) * m.nn_stride + off;
         HIP_TRY(hipMemcpy(h, base, n * sizeof(float), hipMemcpyDeviceToHost));
         if (c && lstm) HIP_TRY(hipMemcpy(c, base + H, n * sizeof(float), hipMemcpyDeviceToHost));
         return static_cast<int>(H);

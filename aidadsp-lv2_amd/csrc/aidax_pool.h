@@ -76,7 +76,7 @@ LpGate& lp_gate();                     // (the one instance: aidax_pool.cpp)
 
 // The device side of one loaded model: what the reference keeps in a DynamicModel (rt-neural-generic.h:115-129)
 // minus the per-stream members. A pool plays `cur`; aidax_pool_prepare_model builds the next one on the worker
-// thread and aidax_pool_commit_model swaps the two on the audio thread (plain struct assignment).
+// thread and aidax_pool_commit_model swaps the two on the audio thread (moves of host fields and owners: no HIP call). Move-only.
 struct ModelSlot {
     bool has_model = false;
     enum Kind { TABLE = 0, STACK = 1, CONV = 2, MFMA = 3, QUAD = 4 } kind = TABLE;
@@ -89,17 +89,17 @@ struct ModelSlot {
     int cell = 0, input_size = 1, input_skip = 0, hidden = 0;
     float in_gain = 1.f, out_gain = 1.f, model_sr = 48000.f;
     uint32_t nn_stride = 0;
-    float* d_wq4 = nullptr;          // k_lstm_q4's weight record (LSTM-32 snapshot models), next to the table kernels' d_wpack
-    float* d_wpack = nullptr;        // weights in the kernel's layout
-    float* d_nn = nullptr;           // recurrent state [n_streams][nn_stride]
-    float* d_ring = nullptr;         // k_mfma_lp: h of layer l-1 on its way to layer l, per stream group
-    uint32_t* d_counters = nullptr;  // k_mfma_lp: frames produced / consumed per (group, layer boundary)
-    mutable const void* lp_owner = nullptr;  // the pool whose hold on the device's LpGate this slot shares (d_ring != nullptr); given up on the launch path when the grid is refused
+    DevBuf<float> d_wq4;             // k_lstm_q4's weight record (LSTM-32 snapshot models), next to the table kernels' d_wpack
+    DevBuf<float> d_wpack;           // weights in the kernel's layout
+    DevBuf<float> d_nn;              // recurrent state [n_streams][nn_stride]
+    DevBuf<float> d_ring;            // k_mfma_lp: h of layer l-1 on its way to layer l, per stream group
+    DevBuf<uint32_t> d_counters;     // k_mfma_lp: frames produced / consumed per (group, layer boundary)
+    mutable const void* lp_owner = nullptr;  // the pool whose hold on the device's LpGate this slot shares (it has a d_ring); given up on the launch path when the grid is refused
     mutable RelaxedFlag lp_refused;  // the runtime refused this model's chained grid (cooperative launch: not co-resident on this device): k_mfma serves it — this
                                      // model only; another model of the pool, with a smaller grid, may still fit (set on the launch path, hence mutable)
 
     float p_den() const { return 0.1f * model_sr; }      // LinearValueSmoother tau * sampleRate (:1053-1054)
-    ModelRec rec() const { return model_rec(d_wpack, in_gain, out_gain, input_skip); }      // what a banked stream on this model reads of it
+    ModelRec rec() const { return model_rec(d_wpack.get(), in_gain, out_gain, input_skip); }      // what a banked stream on this model reads of it
     BankArch arch() const { return { cell, hidden, input_size, model_sr, has_model && kind == TABLE && kernel && kernel->fn_pipe_bank }; }
 };
 
@@ -107,26 +107,25 @@ struct ModelSlot {
 // word and the number to write. A launch that takes one clears it and raises its *_taken flag; the caller issues what was not taken behind the pass.
 struct PassEnd { hipEvent_t done = nullptr; uint32_t* word = nullptr; uint32_t seq = 0; bool done_taken = false, word_taken = false; };
 
-// The blocking host-buffer path's buffers (aidax_pool_process; alloc and release: aidax_pool_io.cpp)
+// The blocking host-buffer path's buffers (aidax_pool_process; alloc: aidax_pool_io.cpp)
 struct BlockingIo {
-    float* d_in = nullptr;           // staging for the host-buffer entry point
-    float* d_out = nullptr;
-    float* h_in = nullptr;           // pinned host staging (nullptr: blocks too large, pageable copies)
-    float* h_out = nullptr;
+    DevBuf<float> d_in;              // staging for the host-buffer entry point
+    DevBuf<float> d_out;
+    PinnedBuf<float> h_in;           // pinned host staging (empty: blocks too large, pageable copies)
+    PinnedBuf<float> h_out;
     float* hd_in = nullptr;          // device view of h_in / h_out (zero-copy passes)
     float* hd_out = nullptr;
     bool zero_copy = false;
     // completion word of a pass in pinned host memory: the stream writes the pass number behind its last launch and the
     // caller of aidax_pool_process polls it — no interrupt, no wake-up of a blocked thread (small pools: the plugin case)
-    uint32_t* h_done = nullptr;
+    PinnedBuf<uint32_t> h_done;
     uint32_t* hd_done = nullptr;
     uint32_t done_seq = 0;
     bool spin_wait = false;
     bool kernel_word = true;         // a one-workgroup pass (k_*_pipe / k_*_pipe4 of a one-stream pool) writes the completion word itself, behind its block:
                                      // no packet follows the pass on its queue — 1.7 us of the LV2 instance's 23 us round trip at 64 frames
                                      // (profiles/r06_host_pipeline.txt). AIDAX_KERNEL_WORD=0: the queue writes it (hipStreamWriteValue32), as in round 5
-    void alloc(size_t block_bytes, int device);      // (set-up side; reads AIDAX_ZEROCOPY, AIDAX_SPIN_WAIT, AIDAX_KERNEL_WORD)
-    void release();
+    void alloc(size_t block_floats, int device);     // (set-up side; reads AIDAX_ZEROCOPY, AIDAX_SPIN_WAIT, AIDAX_KERNEL_WORD)
 };
 
 // aidax_pool_submit / aidax_pool_collect: kPipeSets staging sets and two copy streams, so that the upload of the blocks behind
@@ -137,15 +136,15 @@ struct BlockingIo {
 // A third set takes the host's round trip off the GPU's critical path: the pass is what is left.
 constexpr int kPipeSets = 3;
 struct Pipeline {
+    Stream q_up, q_down;             // (declared first, destroyed last: behind the sets' blocks and events)
     bool ready = false;
-    float* h_in[kPipeSets] = {}; float* h_out[kPipeSets] = {}; float* d_in[kPipeSets] = {}; float* d_out[kPipeSets] = {};
-    hipEvent_t ev_up[kPipeSets] = {}, ev_pass[kPipeSets] = {}, ev_down[kPipeSets] = {};
-    hipStream_t q_up = nullptr, q_down = nullptr;
+    PinnedBuf<float> h_in[kPipeSets], h_out[kPipeSets];
+    DevBuf<float> d_in[kPipeSets], d_out[kPipeSets];
+    Event ev_up[kPipeSets], ev_pass[kPipeSets], ev_down[kPipeSets];
     uint32_t frames[kPipeSets] = {};
     float* direct_out[kPipeSets] = {};      // the block's download went straight to this caller buffer (registered): collect() only waits
     uint64_t submitted = 0, collected = 0;
-    void alloc(size_t cap);          // (the first submit: not a real-time call)
-    void release();
+    void alloc(size_t cap_floats);   // (the first submit: not a real-time call) all of it or nothing
 };
 
 }  // namespace aidax
@@ -157,36 +156,38 @@ struct aidax_staged {
     int device = 0;
     uint32_t n_streams = 0;
     ModelSlot slot;
-    StreamState* d_pst = nullptr;    // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
-    hipEvent_t fence = nullptr;      // recorded by the commit: everything that may still touch the retired buffers precedes it
+    DevBuf<StreamState> d_pst;       // per-stream DynamicModel members of the new model (PARAM smoothers, paramFirstRun), installed by the commit
+    Event fence;                     // recorded by the commit: everything that may still touch the retired buffers precedes it
     bool fenced = false;
     enum Payload { MODEL, IR, BANK_SLOT } payload = MODEL;      // what is on its way: `slot`, `ir` (aidax_pool_prepare_ir / _slot) or `bank` (aidax_pool_prepare_model_slot)
     int32_t ir_slot = AIDAX_IR_POOL; // IR: for the pool IR or for this bank slot
-    IrSlot ir;
+    IrSlot ir;                       // (ir.d_frag and bank.d_wpack are the staged object's: records that the books swap, freed by staged_release)
     uint32_t bank_slot = 0;
     BankSlot bank;
 };
 
 struct aidax_pool {
+    // The two streams are declared first, so they are destroyed last: every block, event and stage below goes back ahead of them, as the
+    // hand-written release did it. ~aidax_pool does what is not memory; the members then free themselves in reverse order.
+    Stream q;                        // the audio side's stream
+    Stream wq;                       // the worker side's stream (prepare)
     int device = 0;
     uint32_t n_streams = 0, max_frames = 0;
     double host_sr = 48000.0;
     float gain_coef = 0.f;
-    hipStream_t q = nullptr;         // the audio side's stream
-    hipStream_t wq = nullptr;        // the worker side's stream (prepare)
-    hipEvent_t ev_x = nullptr;       // edge between two streams that carry passes one after the other
-    hipEvent_t ev_adopt = nullptr;   // "everything this pool has issued so far": what a stream of ANOTHER pool waits for before it adopts one of ours
+    Event ev_x;                      // edge between two streams that carry passes one after the other
+    Event ev_adopt;                  // "everything this pool has issued so far": what a stream of ANOTHER pool waits for before it adopts one of ours
     hipStream_t last_stream = nullptr;
 
-    StreamCtl* d_ctl = nullptr;
-    StreamState* d_st = nullptr;
+    DevBuf<StreamCtl> d_ctl;
+    DevBuf<StreamState> d_st;
     BlockingIo io;                   // aidax_pool_process: staging, zero-copy views and the completion word
     Pipeline pipe;                   // aidax_pool_submit / _collect (allocated by the first submit)
     bool spin_collect = true;        // aidax_pool_collect polls the download's event instead of sleeping on it (AIDAX_SPIN_WAIT=0: off)
     bool keep_warm = false;          // this pool holds a reference on its device's keep-warm thread (AIDAX_KEEP_WARM_US)
     // k_mfma_lp: a word in pinned host memory that a workgroup bumps when a layer hand-over timed out. The pass that did
     // so is wrong; whoever notices reports it, and the pool serves the model with k_mfma from then on (lp_off).
-    uint32_t* h_lp_fault = nullptr;
+    PinnedBuf<uint32_t> h_lp_fault;
     uint32_t* hd_lp_fault = nullptr;
     mutable std::atomic<bool> lp_off{false};      // (mutable: set from the launch path, a const member function)
     std::atomic<uint32_t> lp_faults{0};
@@ -196,13 +197,13 @@ struct aidax_pool {
         if (!h_lp_fault) return false;
         // read-and-clear in ONE atomic step: workgroups bump the word with system-scope atomic adds while we look, and a
         // give-up that landed between a read and a separate store of 0 would go unreported
-        if (__atomic_load_n(h_lp_fault, __ATOMIC_RELAXED) == 0) return false;
-        if (__atomic_exchange_n(h_lp_fault, 0u, __ATOMIC_ACQ_REL) == 0) return false;
+        if (__atomic_load_n(h_lp_fault.get(), __ATOMIC_RELAXED) == 0) return false;
+        if (__atomic_exchange_n(h_lp_fault.get(), 0u, __ATOMIC_ACQ_REL) == 0) return false;
         lp_off.store(true, std::memory_order_relaxed);
         lp_faults.fetch_add(1, std::memory_order_relaxed);
         // the wrong block is in the IR history: clear it, so that it does not sound through the IR's tail (behind every pass issued so far)
         if (ir.adopt()) {
-            if (last_stream && last_stream != q && hipEventRecord(ev_x, last_stream) == hipSuccess) (void)hipStreamWaitEvent(q, ev_x, 0);
+            if (last_stream && last_stream != q && hipEventRecord(ev_x.get(), last_stream) == hipSuccess) (void)hipStreamWaitEvent(q, ev_x.get(), 0);
             last_stream = q;
             ir.clear_all(q);
         }
@@ -241,7 +242,7 @@ struct aidax_pool {
     bool packed_fits = false;        // the packed chains' eight rows of max_frames fit their LDS (chain_lds_bytes: set by aidax_pool_create)
     Force force = Force::None;       // AIDAX_KERNEL (test build) overrides the heuristics (A/B testing)
 
-    bool lp_in_use(const ModelSlot& m) const { return chained_usable(m.d_ring != nullptr && !m.lp_refused, m.mdesc.n_layers >= 2, lp_off.load(std::memory_order_relaxed)); }
+    bool lp_in_use(const ModelSlot& m) const { return chained_usable(m.d_ring && !m.lp_refused, m.mdesc.n_layers >= 2, lp_off.load(std::memory_order_relaxed)); }
     static size_t lds_bytes(const ModelSlot& m, uint32_t n_frames)
     {
         return (static_cast<size_t>((n_frames + 3) & ~3u) + static_cast<size_t>(m.hidden > 0 ? m.hidden + 4 : 4)) * sizeof(float);   // block + h row + spare slot
@@ -262,7 +263,7 @@ struct aidax_pool {
         pass.slot = m.form; pass.has = table ? &m.kernel->has : nullptr;
         pass.mode = mode; pass.n_frames = n_frames; pass.n_streams = n_pass_streams; pass.input_size = m.input_size;
         pass.pipe4_lds_ok = table && pipe4_lds_bytes(m.hidden, n_frames, m.input_size) <= 160 * 1024;      // (a CU's LDS)
-        pass.ring_ready = m.d_ring != nullptr && !m.lp_refused; pass.hand_over = m.mdesc.n_layers >= 2;
+        pass.ring_ready = m.d_ring && !m.lp_refused; pass.hand_over = m.mdesc.n_layers >= 2;
         pass.conv_st = m.cdesc.st_ok != 0;
         return resolve_pass(pool, pass);
     }
@@ -270,7 +271,7 @@ struct aidax_pool {
     PassForm playing_form(uint32_t n_frames) const { return pass_form(cur, MODE_CHAIN, n_frames, n_streams, bank.in_force()); }
     // A give-up of an earlier pass that nobody has collected yet: no further k_mfma_lp / k_mfma_ls launch of a stacked model (its counters are
     // out of step); the word stays for whoever reports it (aidax_pool_sync, the hub). AHEAD of every resolution of a form that launch executes.
-    void note_lp_give_up() const { if (h_lp_fault && *static_cast<volatile uint32_t*>(h_lp_fault) != 0) lp_off.store(true, std::memory_order_relaxed); }
+    void note_lp_give_up() const { if (h_lp_fault && *static_cast<volatile uint32_t*>(h_lp_fault.get()) != 0) lp_off.store(true, std::memory_order_relaxed); }
     // ... so the form a caller resolves ahead of pool_process_prefix, to hand it in: the one launch would resolve itself
     PassForm resolved_playing_form(uint32_t n_frames) const { note_lp_give_up(); return playing_form(n_frames); }
     void refresh_ctl(uint32_t s)
@@ -306,14 +307,14 @@ struct aidax_pool {
     }
     // Upload the changed control records, stream-ordered with the pass that follows. The records leave from a
     // ring of pinned snapshots, so the copy is asynchronous and a later set_controls cannot overtake it.
-    void flush_ctl(hipStream_t s) { ctl_ring.upload_dirty(d_ctl, h_ctl.data(), ctl_dirty, s); }
+    void flush_ctl(hipStream_t s) { ctl_ring.upload_dirty(d_ctl.get(), h_ctl.data(), ctl_dirty, s); }
     // Passes and control pokes are issued in program order by the audio side but may sit on two streams (the pool's
     // own and one handed to aidax_pool_process_device): moving from one to the other puts an event edge between them.
     void enter_stream(hipStream_t s)
     {
         if (last_stream && last_stream != s) {
-            HIP_TRY(hipEventRecord(ev_x, last_stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_x, 0));
+            HIP_TRY(hipEventRecord(ev_x.get(), last_stream));
+            HIP_TRY(hipStreamWaitEvent(s, ev_x.get(), 0));
         }
         last_stream = s;
     }
@@ -322,7 +323,7 @@ struct aidax_pool {
     LaunchArgs args(const ModelSlot& m, StreamState* st, const float* in, float* out, uint32_t n_frames, int mode) const
     {
         LaunchArgs a{};
-        a.ctl = d_ctl; a.st = st; a.nn = m.d_nn;
+        a.ctl = d_ctl.get(); a.st = st; a.nn = m.d_nn.get();
         a.in = in; a.out = out;
         a.n_streams = n_streams; a.n_frames = n_frames; a.nn_stride = m.nn_stride;
         a.mode = mode; a.input_size = m.input_size;
@@ -343,10 +344,10 @@ struct aidax_pool {
     // arguments view the pool as one stream, which plays the model of `rec` (m's own, or a bank slot's weights, gains and skip)
     void fresh_stream_model(const ModelSlot& m, uint32_t s, int start_mode, const ModelRec& rec, hipStream_t on) const
     {
-        HIP_TRY(launch_reset_for_model(d_st + s, m.d_nn + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), on));
+        HIP_TRY(launch_reset_for_model(d_st.get() + s, m.d_nn.get() + static_cast<size_t>(s) * m.nn_stride, 1, m.nn_stride, m.p_den(), on));
         const uint32_t chunk = launch_chunk(m, kWarmupFrames);
         for (uint32_t done = 0; start_mode == AIDAX_START_WARMUP && done < kWarmupFrames; done += chunk) {
-            LaunchArgs a = args(m, d_st, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+            LaunchArgs a = args(m, d_st.get(), nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
             apply_model_rec(a, rec);
             a.ctl += s; a.st += s; a.nn += static_cast<size_t>(s) * m.nn_stride;
             a.n_streams = 1;
@@ -355,41 +356,19 @@ struct aidax_pool {
     }
     // an audio-side call that issues work on the pool's own stream, behind everything issued so far
     template <class F> int on_own_stream(F&& f) { return guarded([&]() -> int { HIP_TRY(hipSetDevice(device)); enter_stream(q); return f(); }); }
-    void release()                   // (both callers delete the pool next: nothing is reset)
+    // What is not memory (aidax_pool_destroy has set the device and waited for the streams; a failed aidax_pool_create comes here on its device)
+    ~aidax_pool()
     {
-        ir.release();
-        bank.release();
-        gate.release();
-        mix.release();
-        limit.release();
-        reverb.release();
-        meter.release();
-        if (d_ctl) (void)hipFree(d_ctl);
-        if (d_st) (void)hipFree(d_st);
-        if (cur.d_nn) (void)hipFree(cur.d_nn);
-        if (cur.d_wpack) (void)hipFree(cur.d_wpack);
-        if (cur.d_wq4) (void)hipFree(cur.d_wq4);
-        if (cur.d_ring) (void)hipFree(cur.d_ring);
-        if (cur.d_counters) (void)hipFree(cur.d_counters);
-        if (cur.lp_owner) { lp_gate().release(device, cur.lp_owner); cur.lp_owner = nullptr; }
-        if (h_lp_fault)                                      // (measurement builds / AIDAX_TUNE bit 4096: the stamps behind the fault word)
+        if (cur.lp_owner) lp_gate().release(device, cur.lp_owner);
+        if (h_lp_fault)                                      // (measurement builds / AIDAX_TUNE bit 4096: the stamps behind the fault word, while it is alive)
             if (const char* f = AIDAX_HOOK_ENV("AIDAX_LP_TRACE_FILE"))
-                if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(h_lp_fault + 16, 4, 1536, fp); std::fclose(fp); }
-        if (h_lp_fault) (void)hipHostFree(h_lp_fault);
+                if (FILE* fp = std::fopen(f, "wb")) { std::fwrite(h_lp_fault.get() + 16, 4, 1536, fp); std::fclose(fp); }
         for (const HostRange& r : host_ranges) (void)hipHostUnregister(r.base);
-        host_ranges.clear();
-        pipe.release();
-        io.release();
-        ctl_ring.release();
-        if (ev_x) (void)hipEventDestroy(ev_x);
-        if (ev_adopt) (void)hipEventDestroy(ev_adopt);
-        if (q) (void)hipStreamDestroy(q);
-        if (wq) (void)hipStreamDestroy(wq);
     }
 };
 
 namespace aidax {
-// worker side (aidax_pool_model.cpp): what a staged object owns goes back; an empty staged object of pool p, with the fence its commit will record
+// worker side (aidax_pool_model.cpp): a staged object goes back, behind its fence; an empty staged object of pool p, with the fence its commit will record
 void staged_release(aidax_staged* s);
 using StagedPtr = std::unique_ptr<aidax_staged, void (*)(aidax_staged*)>;
 StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload);

@@ -24,70 +24,49 @@ template <class Done> static bool spin_until(Done&& done, uint32_t mask)
     return true;
 }
 
-void BlockingIo::alloc(size_t block_bytes, int device)
+void BlockingIo::alloc(size_t block_floats, int device)
 {
     { const char* kw = std::getenv("AIDAX_KERNEL_WORD"); kernel_word = !(kw && kw[0] == '0'); }
-    HIP_TRY(hipMalloc(&d_in, block_bytes));
-    HIP_TRY(hipMalloc(&d_out, block_bytes));
+    const size_t block_bytes = sizeof(float) * block_floats;
+    d_in.alloc(block_floats);
+    d_out.alloc(block_floats);
     if (block_bytes <= kStagingLimit) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in), block_bytes, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out), block_bytes, hipHostMallocDefault));
+        h_in.alloc(block_floats);
+        h_out.alloc(block_floats);
         const char* zc = std::getenv("AIDAX_ZEROCOPY");
         if (block_bytes <= kZeroCopyLimit && !(zc && zc[0] == '0')) {
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd_in), h_in, 0));
-            HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd_out), h_out, 0));
+            hd_in = h_in.device();
+            hd_out = h_out.device();
             zero_copy = true;
             const char* sp = std::getenv("AIDAX_SPIN_WAIT");
             int can = 0;
             (void)hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, device);
             if (can && !(sp && sp[0] == '0')) {
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_done), 64, hipHostMallocDefault));
-                HIP_TRY(hipHostGetDevicePointer(reinterpret_cast<void**>(&hd_done), h_done, 0));
-                *h_done = 0;
+                h_done.alloc(16);
+                hd_done = h_done.device();
+                *h_done.get() = 0;
                 spin_wait = true;
             }
         }
     }
 }
 
-void BlockingIo::release()
+void Pipeline::alloc(size_t cap_floats)
 {
-    if (h_done) (void)hipHostFree(h_done);
-    if (d_in) (void)hipFree(d_in);
-    if (d_out) (void)hipFree(d_out);
-    if (h_in) (void)hipHostFree(h_in);
-    if (h_out) (void)hipHostFree(h_out);
-}
-
-void Pipeline::alloc(size_t cap)
-{
-    HIP_TRY(hipStreamCreateWithFlags(&q_up, hipStreamNonBlocking));
-    HIP_TRY(hipStreamCreateWithFlags(&q_down, hipStreamNonBlocking));
+    Pipeline fresh;
+    fresh.q_up.create();
+    fresh.q_down.create();
     for (int k = 0; k < kPipeSets; ++k) {
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_in[k]), cap, hipHostMallocDefault));
-        HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_out[k]), cap, hipHostMallocDefault));
-        HIP_TRY(hipMalloc(&d_in[k], cap));
-        HIP_TRY(hipMalloc(&d_out[k], cap));
-        HIP_TRY(hipEventCreateWithFlags(&ev_up[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_pass[k], hipEventDisableTiming));
-        HIP_TRY(hipEventCreateWithFlags(&ev_down[k], hipEventDisableTiming));
+        fresh.h_in[k].alloc(cap_floats);
+        fresh.h_out[k].alloc(cap_floats);
+        fresh.d_in[k].alloc(cap_floats);
+        fresh.d_out[k].alloc(cap_floats);
+        fresh.ev_up[k].create();
+        fresh.ev_pass[k].create();
+        fresh.ev_down[k].create();
     }
-    ready = true;
-}
-
-void Pipeline::release()
-{
-    for (int k = 0; k < kPipeSets; ++k) {
-        if (h_in[k]) (void)hipHostFree(h_in[k]);
-        if (h_out[k]) (void)hipHostFree(h_out[k]);
-        if (d_in[k]) (void)hipFree(d_in[k]);
-        if (d_out[k]) (void)hipFree(d_out[k]);
-        if (ev_up[k]) (void)hipEventDestroy(ev_up[k]);
-        if (ev_pass[k]) (void)hipEventDestroy(ev_pass[k]);
-        if (ev_down[k]) (void)hipEventDestroy(ev_down[k]);
-    }
-    if (q_up) (void)hipStreamDestroy(q_up);
-    if (q_down) (void)hipStreamDestroy(q_down);
+    fresh.ready = true;
+    *this = std::move(fresh);
 }
 
 extern "C" {
@@ -103,22 +82,22 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
         int rc;
         BlockingIo& io = p->io;
         PassEnd end;                                        // the completion word, for a pass whose one workgroup can write it
-        const bool staged = io.h_in != nullptr;             // (no pinned staging: pageable copies from and to the caller's buffers — and no zero_copy or spin_wait, which aidax_pool_create sets only behind h_in)
-        if (bytes && staged) std::memcpy(io.h_in, in, bytes);
+        const bool staged = static_cast<bool>(io.h_in);      // (no pinned staging: pageable copies from and to the caller's buffers — and no zero_copy or spin_wait, which aidax_pool_create sets only behind h_in)
+        if (bytes && staged) std::memcpy(io.h_in.get(), in, bytes);
         if (io.zero_copy) {
             // small blocks (the one-instance plugin): the pass reads its input straight from pinned host memory;
             // a pass whose form allows it also writes its output there, every other pass works in place on d_out
             const PassForm form = p->resolved_playing_form(n_frames);      // (once: launch executes this one)
             const bool direct = form.host_in_place;
             if (direct && io.spin_wait && io.kernel_word) { end.word = io.hd_done; end.seq = io.done_seq + 1; }
-            rc = pool_process_prefix(p, io.hd_in, direct ? io.hd_out : io.d_out, n_frames, p->q, p->n_streams, &end, &form);
+            rc = pool_process_prefix(p, io.hd_in, direct ? io.hd_out : io.d_out.get(), n_frames, p->q, p->n_streams, &end, &form);
             if (rc != AIDAX_OK) return rc;
-            if (!direct && bytes) HIP_TRY(hipMemcpyAsync(io.h_out, io.d_out, bytes, hipMemcpyDeviceToHost, p->q));
+            if (!direct && bytes) HIP_TRY(hipMemcpyAsync(io.h_out.get(), io.d_out.get(), bytes, hipMemcpyDeviceToHost, p->q));
         } else {
-            if (bytes) HIP_TRY(hipMemcpyAsync(io.d_in, staged ? io.h_in : in, bytes, hipMemcpyHostToDevice, p->q));
-            rc = pool_process_prefix(p, io.d_in, io.d_out, n_frames, p->q, p->n_streams);
+            if (bytes) HIP_TRY(hipMemcpyAsync(io.d_in.get(), staged ? io.h_in.get() : in, bytes, hipMemcpyHostToDevice, p->q));
+            rc = pool_process_prefix(p, io.d_in.get(), io.d_out.get(), n_frames, p->q, p->n_streams);
             if (rc != AIDAX_OK) return rc;
-            if (bytes) HIP_TRY(hipMemcpyAsync(staged ? io.h_out : out, io.d_out, bytes, hipMemcpyDeviceToHost, p->q));
+            if (bytes) HIP_TRY(hipMemcpyAsync(staged ? io.h_out.get() : out, io.d_out.get(), bytes, hipMemcpyDeviceToHost, p->q));
         }
         const uint32_t seq = io.spin_wait ? ++io.done_seq : 0;
         if (io.spin_wait && !end.word_taken && hipStreamWriteValue32(p->q, io.hd_done, seq, 0) != hipSuccess) {      // (taken: the pass writes it itself) — a runtime without stream memory operations
@@ -126,7 +105,7 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
             io.spin_wait = false;
         }
         if (io.spin_wait) {
-            volatile uint32_t* w = io.h_done;
+            volatile uint32_t* w = io.h_done.get();
             if (!spin_until([&] { return *w == seq; }, 1023u)) HIP_TRY(hipStreamSynchronize(p->q));
             std::atomic_thread_fence(std::memory_order_acquire);
         } else {
@@ -136,7 +115,7 @@ AIDAX_API int aidax_pool_process(aidax_pool* p, const float* in, float* out, uin
             if (bytes) std::memset(out, 0, bytes);
             return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
         }
-        if (bytes && staged) std::memcpy(out, io.h_out, bytes);
+        if (bytes && staged) std::memcpy(out, io.h_out.get(), bytes);
         return AIDAX_OK;
     });
 }
@@ -154,18 +133,18 @@ AIDAX_API int aidax_pool_process_buses(aidax_pool* p, const float* in, float* bu
         const size_t bytes = sizeof(float) * p->n_streams * static_cast<size_t>(n_frames);
         const size_t bus_bytes = sizeof(float) * p->mix.book.n_buses * static_cast<size_t>(n_frames);
         BlockingIo& io = p->io;
-        const bool staged = io.h_in != nullptr;
-        if (bytes && staged) std::memcpy(io.h_in, in, bytes);
-        if (bytes) HIP_TRY(hipMemcpyAsync(io.d_in, staged ? io.h_in : in, bytes, hipMemcpyHostToDevice, p->q));
-        const int rc = pool_process_prefix(p, io.d_in, io.d_out, n_frames, p->q, p->n_streams);
+        const bool staged = static_cast<bool>(io.h_in);
+        if (bytes && staged) std::memcpy(io.h_in.get(), in, bytes);
+        if (bytes) HIP_TRY(hipMemcpyAsync(io.d_in.get(), staged ? io.h_in.get() : in, bytes, hipMemcpyHostToDevice, p->q));
+        const int rc = pool_process_prefix(p, io.d_in.get(), io.d_out.get(), n_frames, p->q, p->n_streams);
         if (rc != AIDAX_OK) return rc;
-        if (bus_bytes) HIP_TRY(hipMemcpyAsync(p->mix.h_bus, p->mix.d_bus, bus_bytes, hipMemcpyDeviceToHost, p->q));
+        if (bus_bytes) HIP_TRY(hipMemcpyAsync(p->mix.h_bus.get(), p->mix.d_bus.get(), bus_bytes, hipMemcpyDeviceToHost, p->q));
         HIP_TRY(hipStreamSynchronize(p->q));
         if (p->take_lp_fault()) {                           // the pass is wrong: silence, and k_mfma from the next one on
             if (bus_bytes) std::memset(bus_out, 0, bus_bytes);
             return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
         }
-        if (bus_bytes) std::memcpy(bus_out, p->mix.h_bus, bus_bytes);
+        if (bus_bytes) std::memcpy(bus_out, p->mix.h_bus.get(), bus_bytes);
         return AIDAX_OK;
     });
 }
@@ -179,31 +158,31 @@ static int pool_submit_impl(aidax_pool* p, const float* in, float* out, uint32_t
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(p->device));
         auto& pl = p->pipe;
-        if (!pl.ready) pl.alloc(sizeof(float) * p->n_streams * static_cast<size_t>(p->max_frames));      // first call: not a real-time call
+        if (!pl.ready) pl.alloc(p->n_streams * static_cast<size_t>(p->max_frames));      // first call: not a real-time call
         if (pl.submitted - pl.collected >= static_cast<uint64_t>(kPipeSets)) return fail(AIDAX_ERR_STATE, "three blocks are in flight: collect one first");
         const int s = static_cast<int>(pl.submitted % kPipeSets);
         const size_t bytes = sizeof(float) * p->n_streams * static_cast<size_t>(n_frames);
         // set s was last used by block k-3, which has been collected: its pass and both its copies are complete
         const float* up_from = in;                          // a registered caller buffer is uploaded as it lies
         if (!p->host_registered(in, bytes)) {
-            std::memcpy(pl.h_in[s], in, bytes);
-            up_from = pl.h_in[s];
+            std::memcpy(pl.h_in[s].get(), in, bytes);
+            up_from = pl.h_in[s].get();
         }
-        HIP_TRY(hipMemcpyAsync(pl.d_in[s], up_from, bytes, hipMemcpyHostToDevice, pl.q_up));
-        HIP_TRY(hipEventRecord(pl.ev_up[s], pl.q_up));
+        HIP_TRY(hipMemcpyAsync(pl.d_in[s].get(), up_from, bytes, hipMemcpyHostToDevice, pl.q_up));
+        HIP_TRY(hipEventRecord(pl.ev_up[s].get(), pl.q_up));
         p->enter_stream(p->q);
-        HIP_TRY(hipStreamWaitEvent(p->q, pl.ev_up[s], 0));
+        HIP_TRY(hipStreamWaitEvent(p->q, pl.ev_up[s].get(), 0));
         // (a launch that can carry the "pass done" event on its dispatch packet saves the marker packet behind the pass: 78 -> 72.5 us per
         // cfg2 block, profiles/r06_host_pipeline.txt)
         PassEnd end;
-        end.done = pl.ev_pass[s];
-        const int rc = pool_process_prefix(p, pl.d_in[s], pl.d_out[s], n_frames, p->q, p->n_streams, &end);
+        end.done = pl.ev_pass[s].get();
+        const int rc = pool_process_prefix(p, pl.d_in[s].get(), pl.d_out[s].get(), n_frames, p->q, p->n_streams, &end);
         if (rc != AIDAX_OK) return rc;
-        if (!end.done_taken) HIP_TRY(hipEventRecord(pl.ev_pass[s], p->q));
-        HIP_TRY(hipStreamWaitEvent(pl.q_down, pl.ev_pass[s], 0));
+        if (!end.done_taken) HIP_TRY(hipEventRecord(pl.ev_pass[s].get(), p->q));
+        HIP_TRY(hipStreamWaitEvent(pl.q_down, pl.ev_pass[s].get(), 0));
         pl.direct_out[s] = (out && p->host_registered(out, bytes)) ? out : nullptr;
-        HIP_TRY(hipMemcpyAsync(pl.direct_out[s] ? pl.direct_out[s] : pl.h_out[s], pl.d_out[s], bytes, hipMemcpyDeviceToHost, pl.q_down));
-        HIP_TRY(hipEventRecord(pl.ev_down[s], pl.q_down));
+        HIP_TRY(hipMemcpyAsync(pl.direct_out[s] ? pl.direct_out[s] : pl.h_out[s].get(), pl.d_out[s].get(), bytes, hipMemcpyDeviceToHost, pl.q_down));
+        HIP_TRY(hipEventRecord(pl.ev_down[s].get(), pl.q_down));
         pl.frames[s] = n_frames;
         ++pl.submitted;
         return AIDAX_OK;
@@ -259,14 +238,14 @@ AIDAX_API int aidax_pool_collect(aidax_pool* p, float* out, uint32_t n_frames)
         if (pl.frames[s] != n_frames) return fail(AIDAX_ERR_ARG, "n_frames differs from the submitted block's");
         if (pl.direct_out[s] && pl.direct_out[s] != out) return fail(AIDAX_ERR_ARG, "collect: the block was submitted with another destination");
         HIP_TRY(hipSetDevice(p->device));
-        if (hipEventQuery(pl.ev_down[s]) != hipSuccess) {
+        if (hipEventQuery(pl.ev_down[s].get()) != hipSuccess) {
             // like aidax_pool_process: poll, then wait the usual way
             bool done = false;
             if (p->spin_collect) {
-                done = spin_until([&] { return hipEventQuery(pl.ev_down[s]) == hipSuccess; }, 63u);
+                done = spin_until([&] { return hipEventQuery(pl.ev_down[s].get()) == hipSuccess; }, 63u);
                 (void)hipGetLastError();                        // (hipErrorNotReady of the polls)
             }
-            if (!done) HIP_TRY(hipEventSynchronize(pl.ev_down[s]));
+            if (!done) HIP_TRY(hipEventSynchronize(pl.ev_down[s].get()));
         }
         ++pl.collected;
         const size_t bytes = sizeof(float) * p->n_streams * static_cast<size_t>(n_frames);
@@ -274,7 +253,7 @@ AIDAX_API int aidax_pool_collect(aidax_pool* p, float* out, uint32_t n_frames)
             std::memset(out, 0, bytes);
             return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
         }
-        if (!pl.direct_out[s]) std::memcpy(out, pl.h_out[s], bytes);
+        if (!pl.direct_out[s]) std::memcpy(out, pl.h_out[s].get(), bytes);
         return AIDAX_OK;
     });
 }

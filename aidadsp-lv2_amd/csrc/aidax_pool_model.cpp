@@ -13,17 +13,10 @@ void staged_release(aidax_staged* s)
 {
     if (!s) return;
     (void)hipSetDevice(s->device);
-    if (s->fenced) (void)hipEventSynchronize(s->fence);         // passes that still read the retired buffers
-    if (s->slot.d_wpack) (void)hipFree(s->slot.d_wpack);
-    if (s->slot.d_wq4) (void)hipFree(s->slot.d_wq4);
-    if (s->slot.d_nn) (void)hipFree(s->slot.d_nn);
-    if (s->slot.d_ring) (void)hipFree(s->slot.d_ring);
-    if (s->slot.d_counters) (void)hipFree(s->slot.d_counters);
+    if (s->fenced) (void)hipEventSynchronize(s->fence.get());   // passes that still read the retired buffers
     if (s->slot.lp_owner) lp_gate().release(s->device, s->slot.lp_owner);
-    if (s->d_pst) (void)hipFree(s->d_pst);
-    if (s->ir.d_frag) (void)hipFree(s->ir.d_frag);
-    if (s->bank.d_wpack) (void)hipFree(s->bank.d_wpack);
-    if (s->fence) (void)hipEventDestroy(s->fence);
+    DevBuf<uint32_t>::adopt(s->ir.d_frag);                      // (the two records' blocks; the owning members go back with the object)
+    DevBuf<float>::adopt(s->bank.d_wpack);
     delete s;
 }
 
@@ -31,7 +24,7 @@ StagedPtr new_staged(const aidax_pool& p, aidax_staged::Payload payload)
 {
     StagedPtr sg(new aidax_staged(), staged_release);
     sg->device = p.device; sg->n_streams = p.n_streams; sg->payload = payload;
-    HIP_TRY(hipEventCreateWithFlags(&sg->fence, hipEventDisableTiming));
+    sg->fence.create();
     return sg;
 }
 
@@ -192,30 +185,30 @@ int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_stag
     Packed pk;                                            // (lives until the stream has been waited for below)
     if (const int rc = choose_form(p, m, ms, pk)) return rc;
     const std::vector<float>& wp = pk.wp;
-    HIP_TRY(hipMalloc(&ms.d_wpack, wp.size() * sizeof(float)));
-    HIP_TRY(hipMalloc(&ms.d_nn, static_cast<size_t>(p.n_streams) * ms.nn_stride * sizeof(float)));
-    HIP_TRY(hipMalloc(&sg->d_pst, sizeof(StreamState) * p.n_streams));
+    ms.d_wpack.alloc(wp.size());
+    ms.d_nn.alloc(static_cast<size_t>(p.n_streams) * ms.nn_stride);
+    sg->d_pst.alloc(p.n_streams);
     const bool lp_chained = ms.mdesc.n_layers >= 2;       // (only a hand-over between layers needs the hold on the device's gate)
     if (pk.lp && !(lp_chained && p.lp_off.load()) && (!lp_chained || lp_gate().acquire(p.device, &p, &p.lp_off))) {
         if (lp_chained) ms.lp_owner = &p;
         const size_t ring_bytes = pk.ls ? mfma_ls_ring_bytes(ms.mdesc, pk.ring_streams) : mfma_lp_ring_bytes(ms.mdesc, p.n_streams);
-        HIP_TRY(hipMalloc(&ms.d_ring, ring_bytes));
-        HIP_TRY(hipMalloc(&ms.d_counters, mfma_lp_counter_bytes(ms.mdesc, p.n_streams)));
-        HIP_TRY(hipMemsetAsync(ms.d_counters, 0, mfma_lp_counter_bytes(ms.mdesc, p.n_streams), p.wq));
+        ms.d_ring.alloc((ring_bytes + sizeof(float) - 1) / sizeof(float));
+        ms.d_counters.alloc((mfma_lp_counter_bytes(ms.mdesc, p.n_streams) + sizeof(uint32_t) - 1) / sizeof(uint32_t));
+        HIP_TRY(hipMemsetAsync(ms.d_counters.get(), 0, mfma_lp_counter_bytes(ms.mdesc, p.n_streams), p.wq));
     }
-    HIP_TRY(hipMemcpyAsync(ms.d_wpack, wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
+    HIP_TRY(hipMemcpyAsync(ms.d_wpack.get(), wp.data(), wp.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
     if (!pk.wq4.empty()) {
-        HIP_TRY(hipMalloc(&ms.d_wq4, pk.wq4.size() * sizeof(float)));
-        HIP_TRY(hipMemcpyAsync(ms.d_wq4, pk.wq4.data(), pk.wq4.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
+        ms.d_wq4.alloc(pk.wq4.size());
+        HIP_TRY(hipMemcpyAsync(ms.d_wq4.get(), pk.wq4.data(), pk.wq4.size() * sizeof(float), hipMemcpyHostToDevice, p.wq));
     }
     // fresh DynamicModel per stream: reset() + param smoothers around the targets the playing model holds now
     // (:822-825, :1035, :1053-1061) ...
-    HIP_TRY(launch_stage_params(p.d_st, sg->d_pst, p.n_streams, p.wq));
-    HIP_TRY(launch_reset_for_model(sg->d_pst, ms.d_nn, p.n_streams, ms.nn_stride, ms.p_den(), p.wq));
+    HIP_TRY(launch_stage_params(p.d_st.get(), sg->d_pst.get(), p.n_streams, p.wq));
+    HIP_TRY(launch_reset_for_model(sg->d_pst.get(), ms.d_nn.get(), p.n_streams, ms.nn_stride, ms.p_den(), p.wq));
     if (start_mode == AIDAX_START_WARMUP) {               // ... and 2048 zeros through applyModel (:1077-1078)
         const uint32_t chunk = p.launch_chunk(ms, kWarmupFrames);
         for (uint32_t done = 0; done < kWarmupFrames; done += chunk) {
-            LaunchArgs a = p.args(ms, sg->d_pst, nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
+            LaunchArgs a = p.args(ms, sg->d_pst.get(), nullptr, nullptr, std::min(chunk, kWarmupFrames - done), MODE_WARMUP);
             HIP_TRY(p.launch(ms, a, p.wq));
         }
     }
@@ -228,8 +221,8 @@ int prepare_impl(aidax_pool& p, const aidax_model* m, int start_mode, aidax_stag
 // pool's stream; no allocation, no free, no wait.
 int commit_impl(aidax_pool& p, aidax_staged* sg)
 {
-    if (sg->slot.has_model) HIP_TRY(launch_install_params(p.d_st, sg->d_pst, p.n_streams, p.q));
-    HIP_TRY(hipEventRecord(sg->fence, p.q));              // the retired buffers are free once this has passed
+    if (sg->slot.has_model) HIP_TRY(launch_install_params(p.d_st.get(), sg->d_pst.get(), p.n_streams, p.q));
+    HIP_TRY(hipEventRecord(sg->fence.get(), p.q));              // the retired buffers are free once this has passed
     sg->fenced = true;
     std::swap(p.cur, sg->slot);
     const uint8_t loading = p.cur.has_model ? 0 : 1;      // :889 (unload: loading = true)
@@ -266,7 +259,7 @@ AIDAX_API int aidax_pool_commit_model(aidax_pool* p, aidax_staged* staged)
         if (!b) return fail(AIDAX_ERR_STATE, "the pool has no model bank");
         if (const int rc = b->may_commit_slot(staged->bank_slot, staged->bank, p->cur.arch())) return rc;
         return p->on_own_stream([&]() -> int {
-            HIP_TRY(hipEventRecord(staged->fence, p->q));
+            HIP_TRY(hipEventRecord(staged->fence.get(), p->q));
             staged->fenced = true;
             b->commit_slot(staged->bank_slot, staged->bank);
             return AIDAX_OK;
@@ -394,7 +387,7 @@ AIDAX_API int aidax_pool_commit_ir(aidax_pool* p, aidax_staged* staged)
     if (staged->fenced) return fail(AIDAX_ERR_STATE, "staged IR was committed already");
     if (staged->device != p->device || staged->n_streams != p->n_streams) return fail(AIDAX_ERR_ARG, "staged IR belongs to another pool");
     return p->on_own_stream([&]() -> int {
-        p->ir.commit(staged->ir_slot, staged->ir, staged->fence, p->q);
+        p->ir.commit(staged->ir_slot, staged->ir, staged->fence.get(), p->q);
         staged->fenced = true;
         return AIDAX_OK;
     });
@@ -537,16 +530,17 @@ AIDAX_API int aidax_model_forward(const aidax_model* m, int device_id, const flo
     rc = aidax_pool_set_model(p, m, AIDAX_START_RESET);
     if (rc == AIDAX_OK) {
         rc = guarded([&]() -> int {
-            float* d_x = nullptr;
-            float* d_y = nullptr;
-            const size_t xb = sizeof(float) * static_cast<size_t>(n) * m->input_size;
-            HIP_TRY(hipMalloc(&d_x, xb ? xb : 4));
-            HIP_TRY(hipMalloc(&d_y, sizeof(float) * (n ? n : 1)));
-            HIP_TRY(hipMemcpyAsync(d_x, X, xb, hipMemcpyHostToDevice, p->q));
+            DevBuf<float> x_buf, y_buf;                         // (freed behind the wait below, ahead of the pool)
+            const size_t xn = static_cast<size_t>(n) * m->input_size;
+            x_buf.alloc(xn ? xn : 1);
+            y_buf.alloc(n ? n : 1);
+            float* d_x = x_buf.get();
+            float* d_y = y_buf.get();
+            HIP_TRY(hipMemcpyAsync(d_x, X, sizeof(float) * xn, hipMemcpyHostToDevice, p->q));
             hipError_t le = hipSuccess;
             const uint32_t chunk = p->launch_chunk(p->cur, n ? n : 1);
             for (uint32_t done = 0; done < n && le == hipSuccess; done += chunk) {
-                LaunchArgs a = p->args(p->cur, p->d_st, d_x + static_cast<size_t>(done) * m->input_size, d_y + done,
+                LaunchArgs a = p->args(p->cur, p->d_st.get(), d_x + static_cast<size_t>(done) * m->input_size, d_y + done,
                                        std::min(chunk, n - done), MODE_NN_ONLY);
                 if (unit_gains) { a.in_gain = 1.f; a.out_gain = 1.f; }
                 le = p->launch(p->cur, a, p->q);
@@ -555,8 +549,6 @@ AIDAX_API int aidax_model_forward(const aidax_model* m, int device_id, const flo
                 (void)hipMemcpyAsync(y, d_y, sizeof(float) * n, hipMemcpyDeviceToHost, p->q);
             }
             const hipError_t se = hipStreamSynchronize(p->q);
-            (void)hipFree(d_x);
-            (void)hipFree(d_y);
             HIP_TRY(le);
             HIP_TRY(se);
             return AIDAX_OK;

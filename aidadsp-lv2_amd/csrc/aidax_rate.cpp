@@ -49,22 +49,20 @@ using namespace aidax;
 // One conversion rate_in -> rate_out for n_streams streams. Frames and outputs are counted since creation, the same for every stream:
 // `received` input frames appended so far, `produced` outputs written so far. One caller at a time.
 struct aidax_resampler {
+    Stream q;                            // the stream of calls that name none (declared first, destroyed last: behind the blocks and the event)
     int device = 0;
     uint32_t n_streams = 0, max_in = 0, out_cap = 0;
     RsFilter f;
     int64_t d_in = 0, d_out = 0;
     uint32_t R = 0;                      // ring slots per stream, a power of two >= T + 2 max_in + 2 ceil(M / L) + 2
-    float* d_ring = nullptr;
-    float* d_wt = nullptr;               // [T][L]
+    DevBuf<float> d_ring;
+    DevBuf<float> d_wt;                  // [T][L]
     uint64_t received = 0, produced = 0;
-    hipStream_t q = nullptr;             // the stream of calls that name none
     hipStream_t last_stream = nullptr;
-    hipEvent_t ev_x = nullptr;           // edge between two streams that carry calls one after the other
+    Event ev_x;                          // edge between two streams that carry calls one after the other
     // aidax_resampler_process: pinned host and device staging of max_in resp. out_cap frames per stream (public creation only)
-    float* h_in = nullptr;
-    float* h_out = nullptr;
-    float* d_sin = nullptr;
-    float* d_sout = nullptr;
+    PinnedBuf<float> h_in, h_out;
+    DevBuf<float> d_sin, d_sout;
 
     int64_t numer(uint64_t j) const { return (static_cast<int64_t>(j) - d_out) * f.M - d_in * f.L; }
     // outputs j < ready_end(n) have their whole row inside the first n input frames: q(j) + H < n, i.e. (j - d_out) M < (n - H + d_in) L
@@ -77,21 +75,10 @@ struct aidax_resampler {
     void enter_stream(hipStream_t s)
     {
         if (last_stream && last_stream != s) {
-            HIP_TRY(hipEventRecord(ev_x, last_stream));
-            HIP_TRY(hipStreamWaitEvent(s, ev_x, 0));
+            HIP_TRY(hipEventRecord(ev_x.get(), last_stream));
+            HIP_TRY(hipStreamWaitEvent(s, ev_x.get(), 0));
         }
         last_stream = s;
-    }
-    void release()
-    {
-        if (d_ring) (void)hipFree(d_ring);
-        if (d_wt) (void)hipFree(d_wt);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (d_sin) (void)hipFree(d_sin);
-        if (d_sout) (void)hipFree(d_sout);
-        if (ev_x) (void)hipEventDestroy(ev_x);
-        if (q) (void)hipStreamDestroy(q);
     }
 };
 
@@ -119,33 +106,29 @@ int resampler_create(uint32_t n_streams, double rate_in, double rate_out, uint32
         while (R < static_cast<uint64_t>(f.T) + 2u * static_cast<uint64_t>(max_in) + 2u * static_cast<uint64_t>(ceil_div(f.M, f.L)) + 2u) R *= 2;
         rs->R = R;
         rs->out_cap = static_cast<uint32_t>(std::min<int64_t>(ceil_div((static_cast<int64_t>(max_in) + f.T) * f.L, f.M) + 2, kRsMaxOut));
-        try {
-            HIP_TRY(hipSetDevice(device));
-            HIP_TRY(hipStreamCreateWithFlags(&rs->q, hipStreamNonBlocking));
-            HIP_TRY(hipEventCreateWithFlags(&rs->ev_x, hipEventDisableTiming));
-            const size_t ring_bytes = sizeof(float) * n_streams * static_cast<size_t>(R);
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rs->d_ring), ring_bytes));
-            HIP_TRY(hipMemsetAsync(rs->d_ring, 0, ring_bytes, rs->q));
-            std::vector<float> row(static_cast<size_t>(f.T)), wt(static_cast<size_t>(f.T * f.L));
-            for (int64_t phi = 0; phi < f.L; ++phi) {
-                f.row(static_cast<uint32_t>(phi), row.data());
-                for (int64_t i = 0; i < f.T; ++i) wt[static_cast<size_t>(i * f.L + phi)] = row[static_cast<size_t>(i)];
-            }
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rs->d_wt), wt.size() * sizeof(float)));
-            HIP_TRY(hipMemcpyAsync(rs->d_wt, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, rs->q));
-            if (host_staging) {
-                const size_t in_bytes = sizeof(float) * n_streams * static_cast<size_t>(max_in), out_bytes = sizeof(float) * n_streams * static_cast<size_t>(rs->out_cap);
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&rs->h_in), in_bytes, hipHostMallocDefault));
-                HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&rs->h_out), out_bytes, hipHostMallocDefault));
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rs->d_sin), in_bytes));
-                HIP_TRY(hipMalloc(reinterpret_cast<void**>(&rs->d_sout), out_bytes));
-            }
-            HIP_TRY(hipStreamSynchronize(rs->q));                      // (the table's host copy ends with this scope)
-            rs->last_stream = rs->q;
-        } catch (...) {
-            rs->release();
-            throw;
+        // (a failure from here on: the owning members give back what was made, the stream last)
+        HIP_TRY(hipSetDevice(device));
+        rs->q.create();
+        rs->ev_x.create();
+        const size_t ring_floats = n_streams * static_cast<size_t>(R);
+        rs->d_ring.alloc(ring_floats);
+        HIP_TRY(hipMemsetAsync(rs->d_ring.get(), 0, sizeof(float) * ring_floats, rs->q));
+        std::vector<float> row(static_cast<size_t>(f.T)), wt(static_cast<size_t>(f.T * f.L));
+        for (int64_t phi = 0; phi < f.L; ++phi) {
+            f.row(static_cast<uint32_t>(phi), row.data());
+            for (int64_t i = 0; i < f.T; ++i) wt[static_cast<size_t>(i * f.L + phi)] = row[static_cast<size_t>(i)];
         }
+        rs->d_wt.alloc(wt.size());
+        HIP_TRY(hipMemcpyAsync(rs->d_wt.get(), wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, rs->q));
+        if (host_staging) {
+            const size_t in_floats = n_streams * static_cast<size_t>(max_in), out_floats = n_streams * static_cast<size_t>(rs->out_cap);
+            rs->h_in.alloc(in_floats);
+            rs->h_out.alloc(out_floats);
+            rs->d_sin.alloc(in_floats);
+            rs->d_sout.alloc(out_floats);
+        }
+        HIP_TRY(hipStreamSynchronize(rs->q));                          // (the table's host copy ends with this scope)
+        rs->last_stream = rs->q;
         *out = rs.release();
         return AIDAX_OK;
     });
@@ -157,7 +140,6 @@ void resampler_destroy(aidax_resampler* rs)
     (void)hipSetDevice(rs->device);
     if (rs->last_stream && rs->last_stream != rs->q) (void)hipStreamSynchronize(rs->last_stream);
     if (rs->q) (void)hipStreamSynchronize(rs->q);
-    rs->release();
     delete rs;
 }
 
@@ -178,7 +160,7 @@ int resampler_issue(aidax_resampler* rs, const float* d_in, uint32_t n_in, float
     if (static_cast<int64_t>(received) - oldest > static_cast<int64_t>(rs->R))
         return fail(AIDAX_ERR_STATE, "resampler: the outputs of earlier calls were not taken (the new frames would overwrite history they need)");
     ResampleArgs a{};
-    a.wt = rs->d_wt; a.ring = rs->d_ring; a.in = d_in; a.out = d_out;
+    a.wt = rs->d_wt.get(); a.ring = rs->d_ring.get(); a.in = d_in; a.out = d_out;
     a.L = static_cast<uint32_t>(f.L); a.M = static_cast<uint32_t>(f.M); a.H = static_cast<uint32_t>(f.H);
     a.mask = rs->R - 1u; a.pos = static_cast<uint32_t>(rs->received & (rs->R - 1u));
     a.n_streams = rs->n_streams; a.n_in = n_in; a.n_out = n_out;
@@ -199,7 +181,7 @@ int resampler_reset_stream(aidax_resampler* rs, uint32_t stream)
     if (stream >= rs->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
     return guarded([&]() -> int {
         HIP_TRY(hipSetDevice(rs->device));
-        HIP_TRY(hipMemsetAsync(rs->d_ring + static_cast<size_t>(stream) * rs->R, 0, sizeof(float) * rs->R, rs->last_stream));
+        HIP_TRY(hipMemsetAsync(rs->d_ring.get() + static_cast<size_t>(stream) * rs->R, 0, sizeof(float) * rs->R, rs->last_stream));
         return AIDAX_OK;
     });
 }
@@ -207,36 +189,23 @@ int resampler_reset_stream(aidax_resampler* rs, uint32_t stream)
 }  // namespace
 
 // A pool at its model's rate inside a host at another: host block -> A -> the pool's pass -> B -> host block, on one stream.
+struct ResamplerDelete { void operator()(aidax_resampler* rs) const { resampler_destroy(rs); } };
+
 struct aidax_rate {
+    Stream q;                            // the stream of calls that name none (declared first, destroyed last)
     aidax_pool* pool = nullptr;
     int device = 0;
     uint32_t n_streams = 0, max_frames = 0, pool_cap = 0, latency = 0;
     uint64_t La = 1, Ma = 1;             // pool_rate / host_rate in lowest terms
     bool equal = false;
-    aidax_resampler* A = nullptr;        // host -> pool
-    aidax_resampler* B = nullptr;        // pool -> host
-    float* d_a = nullptr;                // [n_streams][m]: the pool's input block
-    float* d_b = nullptr;                // ... and its output block
-    float* h_in = nullptr;               // aidax_rate_process: pinned staging of the host block, and its place on the device
-    float* h_out = nullptr;
-    float* d_hin = nullptr;
-    float* d_hout = nullptr;
-    hipStream_t q = nullptr;             // the stream of calls that name none
+    DevBuf<float> d_a;                   // [n_streams][m]: the pool's input block
+    DevBuf<float> d_b;                   // ... and its output block
+    PinnedBuf<float> h_in, h_out;        // aidax_rate_process: pinned staging of the host block, and its place on the device
+    DevBuf<float> d_hin, d_hout;
+    std::unique_ptr<aidax_resampler, ResamplerDelete> A;      // host -> pool (the two resamplers go first, as they did)
+    std::unique_ptr<aidax_resampler, ResamplerDelete> B;      // pool -> host
     hipStream_t last = nullptr;          // the stream last handed to the pool through the adapter
     uint64_t N = 0;                      // host frames received
-
-    void release()
-    {
-        resampler_destroy(A);
-        resampler_destroy(B);
-        if (d_a) (void)hipFree(d_a);
-        if (d_b) (void)hipFree(d_b);
-        if (h_in) (void)hipHostFree(h_in);
-        if (h_out) (void)hipHostFree(h_out);
-        if (d_hin) (void)hipFree(d_hin);
-        if (d_hout) (void)hipFree(d_hout);
-        if (q) (void)hipStreamDestroy(q);
-    }
 };
 
 namespace {
@@ -294,14 +263,14 @@ AIDAX_API int aidax_resampler_process(aidax_resampler* rs, const float* in, uint
         HIP_TRY(hipSetDevice(rs->device));
         const size_t in_bytes = sizeof(float) * rs->n_streams * static_cast<size_t>(n_in), out_bytes = sizeof(float) * rs->n_streams * static_cast<size_t>(n_out);
         if (in_bytes) {
-            std::memcpy(rs->h_in, in, in_bytes);
+            std::memcpy(rs->h_in.get(), in, in_bytes);
             rs->enter_stream(rs->q);
-            HIP_TRY(hipMemcpyAsync(rs->d_sin, rs->h_in, in_bytes, hipMemcpyHostToDevice, rs->q));
+            HIP_TRY(hipMemcpyAsync(rs->d_sin.get(), rs->h_in.get(), in_bytes, hipMemcpyHostToDevice, rs->q));
         }
-        if (const int rc = resampler_issue(rs, rs->d_sin, n_in, rs->d_sout, n_out, rs->q)) return rc;
-        if (out_bytes) HIP_TRY(hipMemcpyAsync(rs->h_out, rs->d_sout, out_bytes, hipMemcpyDeviceToHost, rs->q));
+        if (const int rc = resampler_issue(rs, rs->d_sin.get(), n_in, rs->d_sout.get(), n_out, rs->q)) return rc;
+        if (out_bytes) HIP_TRY(hipMemcpyAsync(rs->h_out.get(), rs->d_sout.get(), out_bytes, hipMemcpyDeviceToHost, rs->q));
         HIP_TRY(hipStreamSynchronize(rs->q));
-        if (out_bytes) std::memcpy(out, rs->h_out, out_bytes);
+        if (out_bytes) std::memcpy(out, rs->h_out.get(), out_bytes);
         return AIDAX_OK;
     });
 }
@@ -345,23 +314,21 @@ AIDAX_API int aidax_rate_create(aidax_pool* pool, double host_rate, uint32_t max
         r->equal = fa.equal();
         r->latency = r->equal ? 0u : static_cast<uint32_t>(fa.H) + d_b;
         if (r->equal) { *out = r.release(); return AIDAX_OK; }           // forwards to the pool: nothing of its own
-        try {
-            HIP_TRY(hipSetDevice(r->device));
-            HIP_TRY(hipStreamCreateWithFlags(&r->q, hipStreamNonBlocking));
-            int rc = resampler_create(r->n_streams, host_rate, aidax_pool_samplerate(pool), static_cast<uint32_t>(fa.H), 0, max_frames, r->device, false, &r->A);
-            if (rc == AIDAX_OK) rc = resampler_create(r->n_streams, aidax_pool_samplerate(pool), host_rate, 0, d_b, r->pool_cap, r->device, false, &r->B);
-            if (rc != AIDAX_OK) { r->release(); return rc; }
-            const size_t pool_bytes = sizeof(float) * r->n_streams * static_cast<size_t>(r->pool_cap), host_bytes = sizeof(float) * r->n_streams * static_cast<size_t>(max_frames);
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_a), pool_bytes));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_b), pool_bytes));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_in), host_bytes, hipHostMallocDefault));
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&r->h_out), host_bytes, hipHostMallocDefault));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_hin), host_bytes));
-            HIP_TRY(hipMalloc(reinterpret_cast<void**>(&r->d_hout), host_bytes));
-        } catch (...) {
-            r->release();
-            throw;
-        }
+        // (a failure from here on: the owning members give back what was made, the stream last)
+        HIP_TRY(hipSetDevice(r->device));
+        r->q.create();
+        aidax_resampler* made = nullptr;
+        if (const int rc = resampler_create(r->n_streams, host_rate, aidax_pool_samplerate(pool), static_cast<uint32_t>(fa.H), 0, max_frames, r->device, false, &made)) return rc;
+        r->A.reset(made);
+        if (const int rc = resampler_create(r->n_streams, aidax_pool_samplerate(pool), host_rate, 0, d_b, r->pool_cap, r->device, false, &made)) return rc;
+        r->B.reset(made);
+        const size_t pool_floats = r->n_streams * static_cast<size_t>(r->pool_cap), host_floats = r->n_streams * static_cast<size_t>(max_frames);
+        r->d_a.alloc(pool_floats);
+        r->d_b.alloc(pool_floats);
+        r->h_in.alloc(host_floats);
+        r->h_out.alloc(host_floats);
+        r->d_hin.alloc(host_floats);
+        r->d_hout.alloc(host_floats);
         *out = r.release();
         return AIDAX_OK;
     });
@@ -375,7 +342,6 @@ AIDAX_API void aidax_rate_destroy(aidax_rate* r)
     if (r->last) (void)hipStreamSynchronize(r->last);
     if (r->q) (void)hipStreamSynchronize(r->q);
     if (r->last) (void)pool_enter_own_stream(r->pool);
-    r->release();
     delete r;
 }
 
@@ -396,9 +362,9 @@ AIDAX_API int aidax_rate_process_device(aidax_rate* r, const float* d_in, float*
     // pool frames of this call: floor(N' La / Ma) - floor(N La / Ma), N' = N + n
     const uint32_t m = static_cast<uint32_t>((r->N + n_frames) * r->La / r->Ma - r->N * r->La / r->Ma);
     return guarded([&]() -> int {
-        if (const int rc = resampler_issue(r->A, d_in, n_frames, r->d_a, m, s)) return rc;
-        if (const int rc = aidax_pool_process_device(r->pool, r->d_a, r->d_b, m, s)) return rc;
-        if (const int rc = resampler_issue(r->B, r->d_b, m, d_out, n_frames, s)) return rc;
+        if (const int rc = resampler_issue(r->A.get(), d_in, n_frames, r->d_a.get(), m, s)) return rc;
+        if (const int rc = aidax_pool_process_device(r->pool, r->d_a.get(), r->d_b.get(), m, s)) return rc;
+        if (const int rc = resampler_issue(r->B.get(), r->d_b.get(), m, d_out, n_frames, s)) return rc;
         r->N += n_frames;
         return AIDAX_OK;
     });
@@ -414,17 +380,17 @@ AIDAX_API int aidax_rate_process(aidax_rate* r, const float* in, float* out, uin
         HIP_TRY(hipSetDevice(r->device));
         const size_t bytes = sizeof(float) * r->n_streams * static_cast<size_t>(n_frames);
         if (bytes) {
-            std::memcpy(r->h_in, in, bytes);
-            HIP_TRY(hipMemcpyAsync(r->d_hin, r->h_in, bytes, hipMemcpyHostToDevice, r->q));
+            std::memcpy(r->h_in.get(), in, bytes);
+            HIP_TRY(hipMemcpyAsync(r->d_hin.get(), r->h_in.get(), bytes, hipMemcpyHostToDevice, r->q));
         }
-        if (const int rc = aidax_rate_process_device(r, r->d_hin, r->d_hout, n_frames, r->q)) return rc;
-        if (bytes) HIP_TRY(hipMemcpyAsync(r->h_out, r->d_hout, bytes, hipMemcpyDeviceToHost, r->q));
+        if (const int rc = aidax_rate_process_device(r, r->d_hin.get(), r->d_hout.get(), n_frames, r->q)) return rc;
+        if (bytes) HIP_TRY(hipMemcpyAsync(r->h_out.get(), r->d_hout.get(), bytes, hipMemcpyDeviceToHost, r->q));
         HIP_TRY(hipStreamSynchronize(r->q));
         if (pool_take_lp_fault(r->pool)) {                    // the pool's pass is wrong: silence, as aidax_pool_process reports it
             if (bytes) std::memset(out, 0, bytes);
             return fail(AIDAX_ERR_DEVICE, "k_mfma_lp: a layer hand-over timed out (this block is silence; the pool falls back to k_mfma)");
         }
-        if (bytes) std::memcpy(out, r->h_out, bytes);
+        if (bytes) std::memcpy(out, r->h_out.get(), bytes);
         return AIDAX_OK;
     });
 }
@@ -434,8 +400,8 @@ AIDAX_API int aidax_rate_reset_stream(aidax_rate* r, uint32_t stream)
     if (!r) return fail(AIDAX_ERR_ARG, "null rate adapter");
     if (stream >= r->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
     if (r->equal) return AIDAX_OK;
-    if (const int rc = resampler_reset_stream(r->A, stream)) return rc;
-    return resampler_reset_stream(r->B, stream);
+    if (const int rc = resampler_reset_stream(r->A.get(), stream)) return rc;
+    return resampler_reset_stream(r->B.get(), stream);
 }
 
 }  // extern "C"

@@ -51,10 +51,7 @@ struct ReverbBook {
     // (max_delay + 1 frames) next to a pass of max_frames
     static uint32_t ring_row(uint32_t delay_cap, uint32_t max_frames)
     {
-        const uint32_t need = delay_cap + 1u + max_frames;
-        uint32_t row = 1u;
-        while (row < need) row <<= 1;
-        return row;
+        return pow2_at_least(delay_cap + 1u + max_frames);
     }
     // the record's own conditions (include/aidax.h), whatever the capacity; `on` and `epoch` are the book's and are not read
     static bool valid(const aidax_bus_reverb_rec& r)
@@ -120,37 +117,27 @@ struct ReverbBook {
 // record of the audio side. While it is set, k_bus_reverb of a pass works in place on the block k_mix wrote. HIP failures leave as HipFail.
 struct ReverbStage {
     ReverbBook book;
-    float* d_ring = nullptr;         // [n_buses][8][ring_row]: every line's memory; nullptr: never enabled
-    ReverbRec* d_rec = nullptr;      // [n_buses]
+    DevBuf<float> d_ring;            // [n_buses][8][ring_row]: every line's memory; empty: never enabled
+    DevBuf<ReverbRec> d_rec;         // [n_buses]
     SnapshotRing ring;
     uint32_t ring_row = 0;
     bool on = false;
 
-    bool enabled() const { return d_ring != nullptr; }
+    bool enabled() const { return static_cast<bool>(d_ring); }
     // the rings (zeroed), the records (all off) and the snapshots; all or nothing
     void enable(uint32_t n_buses, uint32_t max_frames, uint32_t delay_cap, hipStream_t q)
     {
         const size_t n = n_buses;
         ReverbStage fresh;
         fresh.ring_row = ReverbBook::ring_row(delay_cap, max_frames);
-        const size_t ring_bytes = sizeof(float) * n * kReverbLines * fresh.ring_row;
-        auto build = [&]() -> hipError_t {
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.d_ring), ring_bytes);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_rec), sizeof(ReverbRec) * n);
-            if (e != hipSuccess) return e;
-            e = hipMemsetAsync(fresh.d_ring, 0, ring_bytes, q);
-            if (e == hipSuccess) e = hipMemsetAsync(fresh.d_rec, 0, sizeof(ReverbRec) * n, q);
-            if (e == hipSuccess) e = hipStreamSynchronize(q);      // (a pass on a caller's stream must find them cleared)
-            return e;
-        };
-        try {
-            HIP_TRY(build());
-            fresh.ring.alloc(sizeof(ReverbRec) * n);
-            fresh.book.init(n_buses, delay_cap);
-        } catch (...) {
-            fresh.release();
-            throw;
-        }
+        const size_t ring_floats = n * kReverbLines * fresh.ring_row;
+        fresh.d_ring.alloc(ring_floats);
+        fresh.d_rec.alloc(n);
+        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * ring_floats, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(ReverbRec) * n, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them cleared)
+        fresh.ring.alloc(sizeof(ReverbRec) * n);
+        fresh.book.init(n_buses, delay_cap);
         fresh.on = true;
         *this = std::move(fresh);
     }
@@ -159,18 +146,12 @@ struct ReverbStage {
     void after_mix(float* block, uint32_t n_frames, hipStream_t s)
     {
         book.refresh();
-        ring.upload_dirty(d_rec, book.h_rec.data(), book.dirty, s);
+        ring.upload_dirty(d_rec.get(), book.h_rec.data(), book.dirty, s);
         BusReverbArgs a{};
-        a.block = block; a.ring = d_ring; a.rec = d_rec;
+        a.block = block; a.ring = d_ring.get(); a.rec = d_rec.get();
         a.n_buses = book.n_buses; a.n_frames = n_frames; a.mask = ring_row - 1u; a.pos = book.pos(); a.max_delay = book.max_delay;
         HIP_TRY(launch_bus_reverb(a, s));
         book.advance(n_frames);
-    }
-    void release()
-    {
-        if (d_ring) (void)hipFree(d_ring);
-        if (d_rec) (void)hipFree(d_rec);
-        ring.release();
     }
 };
 

@@ -5,6 +5,7 @@
 
 #include <algorithm>
 #include <cstring>
+#include <utility>
 
 #include "aidax_hip_host.h"
 
@@ -20,37 +21,31 @@ struct DirtyRange {                                      // records [lo, hi] to 
 };
 
 struct SnapshotRing {
-    uint8_t* snap[kRing] = {};
-    hipEvent_t ev[kRing] = {};
+    PinnedBuf<uint8_t> snap[kRing];
+    Event ev[kRing];
     bool used[kRing] = {};
     int next = 0;
 
-    void alloc(size_t bytes)                             // (set-up and worker side)
+    void alloc(size_t bytes)                             // (set-up and worker side) all four or, where one fails, nothing
     {
+        SnapshotRing fresh;
         for (int k = 0; k < kRing; ++k) {
-            HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&snap[k]), bytes, hipHostMallocDefault));
-            HIP_TRY(hipEventCreateWithFlags(&ev[k], hipEventDisableTiming));
+            fresh.snap[k].alloc(bytes);
+            fresh.ev[k].create();
         }
-    }
-    void release()
-    {
-        for (int k = 0; k < kRing; ++k) {
-            if (snap[k]) (void)hipHostFree(snap[k]);
-            if (ev[k]) (void)hipEventDestroy(ev[k]);
-            snap[k] = nullptr; ev[k] = nullptr;
-        }
+        *this = std::move(fresh);
     }
     // An upload is take(), fill what it returns, send(): the next snapshot (waited for only if its last upload, four back, is still in
     // flight: not seen in practice), then its bytes [off, off + bytes) to the same offset of `d_dst` on `s`, asynchronously.
     uint8_t* take()
     {
-        if (used[next] && hipEventQuery(ev[next]) != hipSuccess) HIP_TRY(hipEventSynchronize(ev[next]));
-        return snap[next];
+        if (used[next] && hipEventQuery(ev[next].get()) != hipSuccess) HIP_TRY(hipEventSynchronize(ev[next].get()));
+        return snap[next].get();
     }
     void send(void* d_dst, size_t off, size_t bytes, hipStream_t s)
     {
-        HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(d_dst) + off, snap[next] + off, bytes, hipMemcpyHostToDevice, s));
-        HIP_TRY(hipEventRecord(ev[next], s));
+        HIP_TRY(hipMemcpyAsync(static_cast<uint8_t*>(d_dst) + off, snap[next].get() + off, bytes, hipMemcpyHostToDevice, s));
+        HIP_TRY(hipEventRecord(ev[next].get(), s));
         used[next] = true;
         next = (next + 1) % kRing;
     }

@@ -54,100 +54,72 @@ struct GateBook {
 // uploaded ahead of the pass that follows a change. HIP failures leave as HipFail.
 struct GateStage {
     GateBook book;
-    GateRec* d_rec = nullptr;        // [n_streams], nullptr: never enabled
-    GateState* d_state = nullptr;    // [n_streams]
-    GateState* h_state = nullptr;    // pinned staging of read(), [n_streams]
-    float* d_side = nullptr;         // the gated block a pass's model launch reads: [n_streams][max_frames]
+    DevBuf<GateRec> d_rec;           // [n_streams], empty: never enabled
+    DevBuf<GateState> d_state;       // [n_streams]
+    PinnedBuf<GateState> h_state;    // pinned staging of read(), [n_streams]
+    DevBuf<float> d_side;            // the gated block a pass's model launch reads: [n_streams][max_frames]
     SnapshotRing ring;
 
-    bool enabled() const { return d_rec != nullptr; }
+    bool enabled() const { return static_cast<bool>(d_rec); }
     // records, states (zeroed), the side block, the snapshots and the pinned staging of the read; all or nothing
     void enable(uint32_t n_streams, uint32_t max_frames, hipStream_t q)
     {
         const size_t n = n_streams;
         GateStage fresh;
-        auto build = [&]() -> hipError_t {
-            hipError_t e = hipMalloc(reinterpret_cast<void**>(&fresh.d_rec), sizeof(GateRec) * n);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_state), sizeof(GateState) * n);
-            if (e == hipSuccess) e = hipMalloc(reinterpret_cast<void**>(&fresh.d_side), sizeof(float) * n * max_frames);
-            if (e == hipSuccess) e = hipHostMalloc(reinterpret_cast<void**>(&fresh.h_state), sizeof(GateState) * n, hipHostMallocDefault);
-            if (e == hipSuccess) e = hipMemsetAsync(fresh.d_rec, 0, sizeof(GateRec) * n, q);
-            if (e == hipSuccess) e = hipMemsetAsync(fresh.d_state, 0, sizeof(GateState) * n, q);
-            if (e == hipSuccess) e = hipStreamSynchronize(q);      // (a pass on a caller's stream must find them zeroed)
-            return e;
-        };
-        try {
-            HIP_TRY(build());
-            fresh.ring.alloc(sizeof(GateRec) * n);
-            fresh.book.init(n_streams);
-        } catch (...) {
-            fresh.release();
-            throw;
-        }
+        fresh.d_rec.alloc(n);
+        fresh.d_state.alloc(n);
+        fresh.d_side.alloc(n * max_frames);
+        fresh.h_state.alloc(n);
+        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(GateRec) * n, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_state.get(), 0, sizeof(GateState) * n, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
+        fresh.ring.alloc(sizeof(GateRec) * n);
+        fresh.book.init(n_streams);
         *this = std::move(fresh);
     }
     // audio side: host records; the runs that restart are zeroed by clear_states() on the pool's own stream, behind the passes issued so far
     const std::vector<GateBook::Run>& set(uint32_t lo, uint32_t hi, const aidax_gate_rec* designed, const aidax_gate_params* params) { return book.apply(lo, hi, designed, params); }
-    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) HIP_TRY(hipMemsetAsync(d_state + first, 0, sizeof(GateState) * count, q)); }
+    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) HIP_TRY(hipMemsetAsync(d_state.get() + first, 0, sizeof(GateState) * count, q)); }
     // Ahead of the model's launch of a pass: the records it plays under, then the gated block into the side block. Returns what that
     // launch reads: the side block, or d_in while no gate is on (the pass's end markers stay with the model's launch: the gate is ahead of it)
     const float* before_pass(const float* d_in, const StreamCtl* d_ctl, uint32_t n_active, uint32_t n_frames, hipStream_t s)
     {
         if (n_frames == 0 || book.n_on == 0) return d_in;
-        ring.upload_dirty(d_rec, book.h_rec.data(), book.dirty, s);
-        HIP_TRY(launch_gate(d_in, d_side, d_rec, d_state, d_ctl, n_active, n_frames, s));
-        return d_side;
+        ring.upload_dirty(d_rec.get(), book.h_rec.data(), book.dirty, s);
+        HIP_TRY(launch_gate(d_in, d_side.get(), d_rec.get(), d_state.get(), d_ctl, n_active, n_frames, s));
+        return d_side.get();
     }
     void read(uint32_t first, uint32_t count, aidax_gate_state* out, hipStream_t q)      // waits
     {
-        const size_t bytes = sizeof(GateState) * count;
-        HIP_TRY(hipMemcpyAsync(h_state + first, d_state + first, bytes, hipMemcpyDeviceToHost, q));
-        HIP_TRY(hipStreamSynchronize(q));
-        std::memcpy(out, h_state + first, bytes);
-    }
-    void release()
-    {
-        if (d_rec) (void)hipFree(d_rec);
-        if (d_state) (void)hipFree(d_state);
-        if (d_side) (void)hipFree(d_side);
-        if (h_state) (void)hipHostFree(h_state);
-        ring.release();
+        read_back(out, h_state.get() + first, d_state.get() + first, sizeof(GateState) * count, q);
     }
 };
 
 // The stream meters: nothing until enable(), the set-up side's first call that switches them on; from then on `on` is a host record of
 // the audio side. A metered pass is k_meter over the block it was handed, the pass, k_meter over the block it returns.
 struct MeterStage {
-    MeterRec* d_rec = nullptr;       // [n_streams], nullptr: never enabled
-    MeterRec* h_rec = nullptr;       // pinned staging of read(), [n_streams]
+    DevBuf<MeterRec> d_rec;          // [n_streams], empty: never enabled
+    PinnedBuf<MeterRec> h_rec;       // pinned staging of read(), [n_streams]
     bool on = false;
 
-    void enable(uint32_t n_streams, hipStream_t q)       // the records, zeroed, and the staging; switches the meters on
+    bool enabled() const { return static_cast<bool>(d_rec); }
+    void enable(uint32_t n_streams, hipStream_t q)       // the records, zeroed, and the staging; switches the meters on; all or nothing
     {
-        const size_t bytes = sizeof(MeterRec) * n_streams;
-        if (!h_rec) HIP_TRY(hipHostMalloc(reinterpret_cast<void**>(&h_rec), bytes, hipHostMallocDefault));
-        MeterRec* d = nullptr;
-        HIP_TRY(hipMalloc(reinterpret_cast<void**>(&d), bytes));
-        hipError_t cleared = hipMemsetAsync(d, 0, bytes, q);
-        if (cleared == hipSuccess) cleared = hipStreamSynchronize(q);      // (a pass on a caller's stream must find them zeroed)
-        if (cleared != hipSuccess) {
-            (void)hipFree(d);
-            HIP_TRY(cleared);
-        }
-        d_rec = d;
-        on = true;
+        MeterStage fresh;
+        fresh.h_rec.alloc(n_streams);
+        fresh.d_rec.alloc(n_streams);
+        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(MeterRec) * n_streams, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
+        fresh.on = true;
+        *this = std::move(fresh);
     }
-    void launch_in(const float* d_in, uint32_t n_active, uint32_t n_frames, hipStream_t s) { HIP_TRY(launch_meter(d_in, d_rec, n_active, n_frames, kMeterIn, s)); }
-    void launch_out(const float* d_out, uint32_t n_active, uint32_t n_frames, hipStream_t s) { HIP_TRY(launch_meter(d_out, d_rec, n_active, n_frames, kMeterOut, s)); }
+    void launch_in(const float* d_in, uint32_t n_active, uint32_t n_frames, hipStream_t s) { HIP_TRY(launch_meter(d_in, d_rec.get(), n_active, n_frames, kMeterIn, s)); }
+    void launch_out(const float* d_out, uint32_t n_active, uint32_t n_frames, hipStream_t s) { HIP_TRY(launch_meter(d_out, d_rec.get(), n_active, n_frames, kMeterOut, s)); }
     void read(uint32_t first, uint32_t count, aidax_stream_meter* out, bool clear, hipStream_t q)      // waits
     {
         const size_t bytes = sizeof(MeterRec) * count;
-        HIP_TRY(hipMemcpyAsync(h_rec + first, d_rec + first, bytes, hipMemcpyDeviceToHost, q));
-        if (clear) HIP_TRY(hipMemsetAsync(d_rec + first, 0, bytes, q));
-        HIP_TRY(hipStreamSynchronize(q));
-        std::memcpy(out, h_rec + first, bytes);
+        read_back(out, h_rec.get() + first, d_rec.get() + first, bytes, q, [&] { if (clear) HIP_TRY(hipMemsetAsync(d_rec.get() + first, 0, bytes, q)); });
     }
-    void release() { if (d_rec) (void)hipFree(d_rec); if (h_rec) (void)hipHostFree(h_rec); }
 };
 
 }  // namespace aidax
