@@ -853,6 +853,7 @@ __global__ __launch_bounds__(kStThreads, 4) void k_conv_st(LaunchArgs a, ConvDes
         master_tgt = master_target;
         c.K = isQ ? Kq : Kp;
         c.gain_lane = isQ ? Kq - 1 : 0;
+        // (chain_shape's and chain_latch's rules, aidax_device.h, in the lane-parallel wave's own form: both passes side by side; kept as it is)
         c.active = stage == 0 ? (flags & (isQ ? CTL_DC_ON : CTL_LPF_ON)) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
         c.g.arm(isQ ? master_mem : pre_mem, isQ ? master_tgt : pre_tgt, ramp_coef);
         const bool run = lane < 12 && stage < c.K;

@@ -556,6 +556,85 @@ __device__ __forceinline__ unsigned long long* cv_trace() { __shared__ unsigned 
 #endif
 
 // ------------------------------------------------------------ shared chain pieces
+// run()'s per-stream rules, stated once for every kernel form.
+
+// A. The shape of a pass, from the control flags and a lane's stage: the cascade's length, the lane of the gain ramp, whether
+// this lane's biquad is in circuit; returns its slot. PRE = LPF -> pre gain -> EQ(pre) (:622-630), else DC blocker -> EQ(post)
+// -> master gain (:645-655). A lane beyond the cascade takes stage 0's numbers; it does not run.
+template <bool PRE>
+__device__ __forceinline__ int chain_shape(ChainPass& c, uint32_t flags, int stage)
+{
+    c.K = (flags & (PRE ? CTL_EQ_PRE : CTL_EQ_POST)) ? 6 : 1;
+    c.gain_lane = PRE ? 0 : c.K - 1;
+    const int k = stage < c.K ? stage : 0;
+    const int slot = PRE ? pre_slot(k) : post_slot(k);
+    c.active = k == 0 ? (flags & (PRE ? CTL_LPF_ON : CTL_DC_ON)) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
+    return slot;
+}
+// ... and the stage's coefficients and state with it
+template <bool PRE>
+__device__ __forceinline__ int chain_setup(ChainPass& c, const StreamCtl& ctl, const StreamState& st, uint32_t flags, int stage)
+{
+    const int slot = chain_shape<PRE>(c, flags, stage);
+    chain_load(c, ctl, st, slot, c.active);
+    return slot;
+}
+
+// B. The gain ramp's latch: activate() snaps the memory to the old target (clearToTargetValue, :341-342); the pre target follows
+// its control before every early-out (:513), the master target only on the DSP path (:654: `live`). chain_latch arms the pass's
+// ramp with the pair and hands it back — it is what a stream that does not run writes back.
+struct GainLatch { float mem, tgt; };
+template <bool PRE>
+__device__ __forceinline__ GainLatch chain_latch(ChainPass& c, const StreamCtl& ctl, const StreamState& st, uint32_t pending, bool live)
+{
+    float mem = PRE ? st.pre_mem : st.master_mem;
+    float tgt = PRE ? st.pre_tgt : st.master_tgt;
+    if (pending & PEND_ACTIVATE) mem = tgt;
+    if (PRE) tgt = ctl.pre_target;
+    else if (live) tgt = ctl.master_target;
+    c.g.arm(mem, tgt, PRE ? ctl.pre_coef : ctl.master_coef);
+    return { mem, tgt };
+}
+
+// C. The PARAM smoothers of one stream (:634-640): load, begin_block at the head of a block, a value per frame, store.
+struct ParamRamps {
+    aidax_f32x2 mem, tgt, step;          // [2]: PARAM1, PARAM2
+    __device__ __forceinline__ void load(const StreamState& st)
+    {
+        mem = { st.p_mem[0], st.p_mem[1] };
+        tgt = { st.p_tgt[0], st.p_tgt[1] };
+        step = { st.p_step[0], st.p_step[1] };
+    }
+    // the targets follow the controls, the first run after a load snaps; returns `pending` with that flag cleared
+    __device__ __forceinline__ uint32_t begin_block(const StreamCtl& ctl, uint32_t pending)
+    {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {                    // LinearValueSmoother::setTargetValue (:209-216)
+            const float nt = ctl.p_target[i];
+            if (__builtin_fabsf(tgt[i] - nt) >= FLT_EPSILON) {
+                tgt[i] = nt;
+                step[i] = (tgt[i] - mem[i]) / ctl.p_den;
+            }
+        }
+        if (pending & PEND_PARAM_FIRST) {                // paramFirstRun (:636-640)
+            pending &= ~PEND_PARAM_FIRST;
+            mem = tgt;
+        }
+        return pending;
+    }
+    __device__ __forceinline__ float next(int i) { float m = mem[i]; lin_next(m, tgt[i], step[i]); mem[i] = m; return m; }
+    __device__ __forceinline__ float next1() { return next(0); }
+    __device__ __forceinline__ float next2() { return next(1); }
+    __device__ __forceinline__ void store(StreamState& st) const
+    {
+        st.p_mem[0] = mem[0]; st.p_mem[1] = mem[1];
+        st.p_tgt[0] = tgt[0]; st.p_tgt[1] = tgt[1];
+        st.p_step[0] = step[0]; st.p_step[1] = step[1];
+    }
+};
+
+// D. The whole chain by one wave: chain_prologue, the model over buf[0..n), chain_epilogue (the conv and stack kernels; stream_body,
+// aidax_kernels.hip, is the same sequence written out).
 // The per-stream prologue + pre pass of run() (:489-518, :607-630) executed by ONE wave on
 // an LDS block buffer; ChainCtx::live is false when the stream early-outs (pre-run / disabled).
 struct ChainCtx {
@@ -568,6 +647,8 @@ struct ChainCtx {
 // and state of every stage a pre pass can have are requested before the control word they depend on is waited for — one
 // trip to memory instead of three in a row. A lane beyond the cascade then holds an EQ stage's numbers instead of stage 0's;
 // it does not run either way.
+// (chain_setup's and chain_latch's rules in the spelling they had: the fused conv kernels inline this and chain_epilogue_begin,
+// and their instruction streams are kept as they are)
 template <bool EAGER = false>
 __device__ __forceinline__ ChainCtx chain_prologue(const StreamCtl& ctl, StreamState& st, const float* in_row,
                                                    float* out_row, float* buf, int n, int lane, float* hand = nullptr)
@@ -634,6 +715,7 @@ constexpr int kChainWaveStreams = 8;
 // pass of 256 frames 10.6 -> ~9 us of loop. The wave's hand-over area is [2][64 lanes][16] floats.
 constexpr int kChainPackBlock = 16;
 constexpr int kChainPackHandFloats = 2 * kWave * kChainPackBlock;
+// (chain_setup's and chain_latch's rules in the spelling they had: with the helpers k_chain<true> takes two VGPRs more)
 template <bool PRE>
 __device__ __forceinline__ void chain_wave_pass(const LaunchArgs& a, int stream0, float* rows, int nP, float* hand, int n, int lane,
                                                 bool commit, bool atomic_pending)
@@ -692,6 +774,7 @@ __device__ __forceinline__ void chain_wave_pass(const LaunchArgs& a, int stream0
 // run() :634-640 for a model that takes no PARAM input (the conv stacks): the smoothers' targets still follow the
 // controls and the first run after a load still snaps them — what a model swapped in later inherits (:822-825).
 // Nothing calls next(), so the memories move only on that snap. One lane; returns `pending` with the flag cleared.
+// (ParamRamps::begin_block's rule in its old form, storing only the words that change: k_*_pipe4 and the conv kernels inline it.)
 __device__ __forceinline__ uint32_t param_targets(const StreamCtl& ctl, StreamState& st, uint32_t pending)
 {
     float p_mem[2] = { st.p_mem[0], st.p_mem[1] };

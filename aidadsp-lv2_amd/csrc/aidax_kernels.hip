@@ -468,6 +468,8 @@ __device__ __forceinline__ void stream_body(const LaunchArgs& a, float* smem)
     }
 
     // ---- MODE_CHAIN: run(), rt-neural-generic.cpp:489-518 + :607-659
+    // (chain_prologue + the NN pass + chain_epilogue, aidax_device.h, written out: as calls k_nomodel, k_lstm<H> and k_gru<H> take other
+    // register counts — k_gru<12> and k_gru<24> one wave per SIMD fewer, profiles/chain_rules.txt — so rules A to D keep their old spelling here)
     float* buf = smem;                                   // n_frames floats (rounded up to 4)
     float* hbuf = smem + ((n + 3) & ~3);
     const StreamCtl& ctl = a.ctl[s];
@@ -713,7 +715,7 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
     if (n == 0 || !(flags & CTL_ENABLED)) {              // pre-run (:607-609) / hard bypass (:612-619)
         if (n != 0 && out_row != in_row)
             for (int i = threadIdx.x; i < n; i += kPipeWaves * kWave) out_row[i] = in_row[i];
-        if (threadIdx.x == 0) {
+        if (threadIdx.x == 0) {                             // (chain_latch's rule by hand: three waves, only the latches move, the completion word)
             if (pending0 & PEND_ACTIVATE) { st.pre_mem = st.pre_tgt; st.master_mem = st.master_tgt; }
             st.pre_tgt = ctl.pre_target;
             st.pending = pending0 & ~PEND_ACTIVATE;
@@ -732,7 +734,7 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
     // ---------------------------------------------------------------- role state
     ChainPass cp{};                       // P: pre pass / Q: post pass
     int slot = 0;
-    float p_mem[2] = {0.f, 0.f}, p_tgt[2] = {0.f, 0.f}, p_step[2] = {0.f, 0.f};
+    float p_mem[2] = {0.f, 0.f}, p_tgt[2] = {0.f, 0.f}, p_step[2] = {0.f, 0.f};     // (ParamRamps by hand: as a ParamRamps k_gru_pipe<64> takes other AGPRs, profiles/chain_rules.txt)
     uint32_t pending = pending0 & ~PEND_ACTIVATE;
     float pre_tgt = 0.f, master_tgt = 0.f;
     Cell cell;
@@ -743,16 +745,8 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
 
     if (wave == 0) {                      // ---- P prologue
         load_block(inbuf, in_row, n, lane);
-        const bool eq = flags & CTL_EQ_PRE;
-        cp.K = eq ? 6 : 1;
-        cp.gain_lane = 0;
-        const int k = lane < cp.K ? lane : 0;
-        slot = pre_slot(k);
-        const bool act = k == 0 ? (flags & CTL_LPF_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
-        chain_load(cp, ctl, st, slot, act);
-        const float pre_mem = (pending0 & PEND_ACTIVATE) ? st.pre_tgt : st.pre_mem;
-        pre_tgt = ctl.pre_target;
-        cp.g.arm(pre_mem, pre_tgt, ctl.pre_coef);
+        slot = chain_setup<true>(cp, ctl, st, flags, lane);
+        pre_tgt = chain_latch<true>(cp, ctl, st, pending0, true).tgt;
         if (net_on) {
 #pragma unroll
             for (int i = 0; i < 2; ++i) {
@@ -779,16 +773,8 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
             cell.publish_h(hh + (kRing - 1) * HS);       // h(-1): the row "before" frame 0
         }
     } else {                              // ---- Q prologue
-        const bool eq = flags & CTL_EQ_POST;
-        cp.K = eq ? 6 : 1;
-        cp.gain_lane = cp.K - 1;
-        const int k = lane < cp.K ? lane : 0;
-        slot = post_slot(k);
-        const bool act = k == 0 ? (flags & CTL_DC_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
-        chain_load(cp, ctl, st, slot, act);
-        const float master_mem = (pending0 & PEND_ACTIVATE) ? st.master_tgt : st.master_mem;
-        master_tgt = ctl.master_target;
-        cp.g.arm(master_mem, master_tgt, ctl.master_coef);
+        slot = chain_setup<false>(cp, ctl, st, flags, lane);
+        master_tgt = chain_latch<false>(cp, ctl, st, pending0, true).tgt;      // (the stream runs: the early-out is above)
         q_z1o = cp.z1; q_z2o = cp.z2;
         if (net_on) {
             const float* wd_nat = m_wpack() + (size_t)Cell::PACK * kWave;     // [H] Dense weights then bias
@@ -1399,6 +1385,7 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     c.gain_lane = isQ ? Kqj - 1 : 0;
     c.eq_skip = skipj && isQ && stage == 0;
     c.eq_p = 0.f;
+    // (chain_shape's and chain_latch's rules, aidax_device.h, in this kernel's own form — stage and slot per lane of twelve; its instruction stream is kept as it is)
     c.active = stage == 0 ? (flags & (isQ ? CTL_DC_ON : CTL_LPF_ON)) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
     c.g.arm(isQ ? master_mem : pre_mem, isQ ? master_tgt : pre_tgt, isQ ? ctl_master_coef : ctl_pre_coef);
     const bool run = lane < kP4ChainLanes && stage < c.K && live;
@@ -1661,6 +1648,7 @@ __global__ __launch_bounds__(kWave) void k_nn(LaunchArgs a)
     const float* wd_nat = a.wpack + (size_t)Cell::PACK * kWave;
     for (int i = lane; i < H + 1; i += kWave) wdl[i] = wd_nat[i];
 
+    // (ParamRamps by hand: as a ParamRamps k_nn of the cells with 40 units and more takes other register counts, profiles/chain_rules.txt)
     float p_mem[2] = { st.p_mem[0], st.p_mem[1] };
     float p_tgt[2] = { st.p_tgt[0], st.p_tgt[1] };
     float p_step[2] = { st.p_step[0], st.p_step[1] };

@@ -123,55 +123,20 @@ __device__ __forceinline__ void lp_helper(const LaunchArgs& a, float* xb, float*
     const bool live = valid && n != 0 && (flags & CTL_ENABLED);                 // :607-619
     const bool net = live && (flags & CTL_NET_ON);                             // :631-632
 
-    float p_mem[2] = { st.p_mem[0], st.p_mem[1] }, p_tgt[2] = { st.p_tgt[0], st.p_tgt[1] }, p_step[2] = { st.p_step[0], st.p_step[1] };
+    ParamRamps pr;
+    pr.load(st);
     uint32_t pending = pending0 & ~PEND_ACTIVATE;
     if (net) {
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {                      // LinearValueSmoother::setTargetValue (:209-216)
-            const float nt = ctl.p_target[i];
-            if (__builtin_fabsf(p_tgt[i] - nt) >= FLT_EPSILON) {
-                p_tgt[i] = nt;
-                p_step[i] = (p_tgt[i] - p_mem[i]) / ctl.p_den;
-            }
-        }
-        if (pending & PEND_PARAM_FIRST) {                  // paramFirstRun (:636-640)
-            pending &= ~PEND_PARAM_FIRST;
-            p_mem[0] = p_tgt[0];
-            p_mem[1] = p_tgt[1];
-        }
+        pending = pr.begin_block(ctl, pending);
     }
     if (keeper) livef[sl] = net ? 1.f : 0.f;
 
     // the two passes of this lane's stage, set up like k_chain<true> / k_chain<false>
     ChainPass P, Q;
-    float pre_mem0, pre_tgt, master_mem0, master_tgt;
-    int slot_p, slot_q;
-    {
-        const bool eq = flags & CTL_EQ_PRE;
-        P.K = eq ? 6 : 1;
-        P.gain_lane = 0;
-        const int k = stage < P.K ? stage : 0;
-        slot_p = pre_slot(k);
-        const bool act = k == 0 ? (flags & CTL_LPF_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot_p == BQ_MID : true);
-        chain_load(P, ctl, st, slot_p, act);
-        pre_mem0 = st.pre_mem; pre_tgt = st.pre_tgt;
-        if (pending0 & PEND_ACTIVATE) pre_mem0 = pre_tgt;  // activate(): clearToTargetValue (:341-342)
-        pre_tgt = ctl.pre_target;                          // :513, before every early-out
-        P.g.arm(pre_mem0, pre_tgt, ctl.pre_coef);
-    }
-    {
-        const bool eq = flags & CTL_EQ_POST;
-        Q.K = eq ? 6 : 1;
-        Q.gain_lane = Q.K - 1;
-        const int k = stage < Q.K ? stage : 0;
-        slot_q = post_slot(k);
-        const bool act = k == 0 ? (flags & CTL_DC_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot_q == BQ_MID : true);
-        chain_load(Q, ctl, st, slot_q, act);
-        master_mem0 = st.master_mem; master_tgt = st.master_tgt;
-        if (pending0 & PEND_ACTIVATE) master_mem0 = master_tgt;
-        if (live) master_tgt = ctl.master_target;          // :654, only on the DSP path
-        Q.g.arm(master_mem0, master_tgt, ctl.master_coef);
-    }
+    const int slot_p = chain_setup<true>(P, ctl, st, flags, stage);
+    const GainLatch pre0 = chain_latch<true>(P, ctl, st, pending0, live);
+    const int slot_q = chain_setup<false>(Q, ctl, st, flags, stage);
+    const GainLatch master0 = chain_latch<false>(Q, ctl, st, pending0, live);
     const bool run_p = live && stage < P.K, run_q = live && stage < Q.K;
     const bool general = (AIDAX_TUNE(a) & 8) != 0;
     const int depth_p = general || __builtin_amdgcn_ballot_w64(run_p && stage > 0) != 0 ? 6 : 1;
@@ -187,8 +152,8 @@ __device__ __forceinline__ void lp_helper(const LaunchArgs& a, float* xb, float*
 
     auto write_xin = [&](int parity, int f) {              // x * in_gain, PARAM1, PARAM2 of frame f (:171-181, :195-231)
         float q1 = 0.f, q2 = 0.f;
-        if (I >= 2) q1 = lin_next(p_mem[0], p_tgt[0], p_step[0]);
-        if (I >= 3) q2 = lin_next(p_mem[1], p_tgt[1], p_step[1]);
+        if (I >= 2) q1 = pr.next1();
+        if (I >= 3) q2 = pr.next2();
         if (keeper) {
             float* col = xin + parity * 64;
             col[sl] = net ? row[f] * a.in_gain : 0.f;
@@ -263,14 +228,12 @@ __device__ __forceinline__ void lp_helper(const LaunchArgs& a, float* xb, float*
     if (!valid) return;
     if (run_p) { st.z[slot_p][0] = P.z1; st.z[slot_p][1] = P.z2; }
     if (run_q) { st.z[slot_q][0] = Q.z1; st.z[slot_q][1] = Q.z2; }
-    if (stage == 0) { st.pre_mem = live ? P.g.mem : pre_mem0; st.pre_tgt = pre_tgt; }
-    if (stage == Q.gain_lane) { st.master_mem = live ? Q.g.mem : master_mem0; st.master_tgt = master_tgt; }
+    if (stage == 0) { st.pre_mem = live ? P.g.mem : pre0.mem; st.pre_tgt = pre0.tgt; }
+    if (stage == Q.gain_lane) { st.master_mem = live ? Q.g.mem : master0.mem; st.master_tgt = master0.tgt; }
     if (keeper) {
         st.pending = pending;
         if (net) {
-            st.p_mem[0] = p_mem[0]; st.p_mem[1] = p_mem[1];
-            st.p_tgt[0] = p_tgt[0]; st.p_tgt[1] = p_tgt[1];
-            st.p_step[0] = p_step[0]; st.p_step[1] = p_step[1];
+            pr.store(st);
         }
     }
 }

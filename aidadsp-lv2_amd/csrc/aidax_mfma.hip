@@ -154,7 +154,7 @@ __global__ __launch_bounds__(NW * kWave) void k_mfma(LaunchArgs a, MfmaDesc d)
     const int mode = a.mode;
 
     // ---- per-stream bookkeeping: lanes tid < NS own stream s_base+tid (live flag, PARAM smoothers)
-    float p_mem[2] = { 0.f, 0.f }, p_tgt[2] = { 0.f, 0.f }, p_step[2] = { 0.f, 0.f };
+    ParamRamps pr{};
     uint32_t pending = 0;
     bool mine_live = false;
     if (tid < NS) {
@@ -162,28 +162,14 @@ __global__ __launch_bounds__(NW * kWave) void k_mfma(LaunchArgs a, MfmaDesc d)
         const bool valid = sg < (int)a.n_streams;
         if (valid) {
             StreamState& st = a.st[sg];
-            p_mem[0] = st.p_mem[0]; p_mem[1] = st.p_mem[1];
-            p_tgt[0] = st.p_tgt[0]; p_tgt[1] = st.p_tgt[1];
-            p_step[0] = st.p_step[0]; p_step[1] = st.p_step[1];
+            pr.load(st);
             pending = st.pending;
             if (mode == MODE_CHAIN) {
                 const StreamCtl& ctl = a.ctl[sg];
                 const uint32_t flags = ctl.flags;
                 mine_live = n != 0 && (flags & CTL_ENABLED) && (flags & CTL_NET_ON);      // :607-619, :631-632
                 if (mine_live) {
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {            // LinearValueSmoother::setTargetValue (:209-216)
-                        const float nt = ctl.p_target[i];
-                        if (__builtin_fabsf(p_tgt[i] - nt) >= FLT_EPSILON) {
-                            p_tgt[i] = nt;
-                            p_step[i] = (p_tgt[i] - p_mem[i]) / ctl.p_den;
-                        }
-                    }
-                    if (pending & PEND_PARAM_FIRST) {        // paramFirstRun (:636-640)
-                        pending &= ~PEND_PARAM_FIRST;
-                        p_mem[0] = p_tgt[0];
-                        p_mem[1] = p_tgt[1];
-                    }
+                    pending = pr.begin_block(ctl, pending);
                 }
             } else {
                 mine_live = n != 0 && (mode == MODE_WARMUP || sg == 0);
@@ -245,11 +231,11 @@ __global__ __launch_bounds__(NW * kWave) void k_mfma(LaunchArgs a, MfmaDesc d)
             // lanes tid < NS: x * in_gain, PARAM1, PARAM2 of frame `f` (:171-181, :195-231)
             float q1 = 0.f, q2 = 0.f;
             if (mode == MODE_CHAIN) {
-                if (I >= 2) q1 = lin_next(p_mem[0], p_tgt[0], p_step[0]);
-                if (I >= 3) q2 = lin_next(p_mem[1], p_tgt[1], p_step[1]);
+                if (I >= 2) q1 = pr.next1();
+                if (I >= 3) q2 = pr.next2();
             } else if (mode == MODE_WARMUP) {             // constant params over the zero pre-buffer (:1077-1078)
-                q1 = I >= 2 ? p_mem[0] : 0.f;
-                q2 = I >= 3 ? p_mem[1] : 0.f;
+                q1 = I >= 2 ? pr.mem[0] : 0.f;
+                q2 = I >= 3 ? pr.mem[1] : 0.f;
             } else if (tid == 0) {
                 q1 = I >= 2 ? a.in[(size_t)(base + f) * I + 1] : 0.f;
                 q2 = I >= 3 ? a.in[(size_t)(base + f) * I + 2] : 0.f;
@@ -377,9 +363,7 @@ __global__ __launch_bounds__(NW * kWave) void k_mfma(LaunchArgs a, MfmaDesc d)
     }
     if (tid < NS && mine_live && mode == MODE_CHAIN) {
         StreamState& st = a.st[s_base + tid];
-        st.p_mem[0] = p_mem[0]; st.p_mem[1] = p_mem[1];
-        st.p_tgt[0] = p_tgt[0]; st.p_tgt[1] = p_tgt[1];
-        st.p_step[0] = p_step[0]; st.p_step[1] = p_step[1];
+        pr.store(st);
         st.pending = pending;
     }
 }

@@ -167,6 +167,7 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
     const MfmaLayer& L = d.L[l];
 
     // ---- per-stream bookkeeping: lanes tid < NS own stream s_base+tid (live flag; PARAM smoothers on the first layer)
+    // (ParamRamps, aidax_device.h, by hand: with it k_mfma_ls1 measured 0.3 % slower at 16384 streams, profiles/chain_rules.txt)
     float p_mem[2] = { 0.f, 0.f }, p_tgt[2] = { 0.f, 0.f }, p_step[2] = { 0.f, 0.f };
     uint32_t pending = 0, st_pending0 = 0;
     bool mine_live = false;

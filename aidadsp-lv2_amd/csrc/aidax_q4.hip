@@ -119,7 +119,7 @@ __global__ __launch_bounds__(kQ4Waves * kWave) void k_lstm_q4(LaunchArgs a)
     float* xq  = hh + kQ4HRing * kQ4Streams * HS;           // [ring][4]: pre-pass output
     int*   flg = reinterpret_cast<int*>(xq + kQ4XRing * kQ4Streams);     // [4] live, [4] net in circuit
 
-    if (n == 0) {                                           // pre-run (:607-609): targets latch, nothing else moves
+    if (n == 0) {                                           // pre-run (:607-609): targets latch, nothing else moves (chain_latch's rule by hand, as below)
         if (tid < kQ4Streams && s0 + tid < S) {
             const StreamCtl& ctl = a.ctl[s0 + tid];
             StreamState& st = a.st[s0 + tid];
@@ -247,15 +247,8 @@ __global__ __launch_bounds__(kQ4Waves * kWave) void k_lstm_q4(LaunchArgs a)
         const bool live = flg[j] != 0;
         const bool net_on = flg[kQ4Streams + j] != 0;
         ChainPass cp{};
-        cp.K = (flags & CTL_EQ_PRE) ? 6 : 1;
-        cp.gain_lane = 0;
-        const int k = stage < cp.K ? stage : 0;
-        const int slot = pre_slot(k);
-        const bool act = k == 0 ? (flags & CTL_LPF_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
-        chain_load(cp, ctl, st, slot, act);
-        const float pre_mem = (pending0 & PEND_ACTIVATE) ? st.pre_tgt : st.pre_mem;       // activate(): clearToTargetValue (:341-342)
-        const float pre_tgt = ctl.pre_target;                                             // :513
-        cp.g.arm(pre_mem, pre_tgt, ctl.pre_coef);
+        const int slot = chain_setup<true>(cp, ctl, st, flags, stage);
+        const float pre_tgt = chain_latch<true>(cp, ctl, st, pending0, live).tgt;
         const bool run = live && stage < cp.K;
         const bool writer = run && stage == cp.K - 1;
         const float* row = buf + j * nP;
@@ -274,25 +267,12 @@ __global__ __launch_bounds__(kQ4Waves * kWave) void k_lstm_q4(LaunchArgs a)
             if (live) {
                 st.pre_mem = cp.g.mem;
                 if (net_on) {                                 // :634-640 (the targets follow the ports whatever the model reads)
-                    float p_mem[2] = { st.p_mem[0], st.p_mem[1] }, p_tgt[2] = { st.p_tgt[0], st.p_tgt[1] }, p_step[2] = { st.p_step[0], st.p_step[1] };
-#pragma unroll
-                    for (int i = 0; i < 2; ++i) {             // LinearValueSmoother::setTargetValue (:209-216)
-                        const float nt = ctl.p_target[i];
-                        if (__builtin_fabsf(p_tgt[i] - nt) >= FLT_EPSILON) {
-                            p_tgt[i] = nt;
-                            p_step[i] = (p_tgt[i] - p_mem[i]) / ctl.p_den;
-                        }
-                    }
-                    if (pending & PEND_PARAM_FIRST) {         // paramFirstRun
-                        pending &= ~PEND_PARAM_FIRST;
-                        p_mem[0] = p_tgt[0];
-                        p_mem[1] = p_tgt[1];
-                    }
-                    st.p_mem[0] = p_mem[0]; st.p_mem[1] = p_mem[1];
-                    st.p_tgt[0] = p_tgt[0]; st.p_tgt[1] = p_tgt[1];
-                    st.p_step[0] = p_step[0]; st.p_step[1] = p_step[1];
+                    ParamRamps pr;
+                    pr.load(st);
+                    pending = pr.begin_block(ctl, pending);
+                    pr.store(st);
                 }
-            } else if (pending0 & PEND_ACTIVATE) {            // hard bypass (:612-619): only the latches move
+            } else if (pending0 & PEND_ACTIVATE) {            // hard bypass (:612-619): only the latches move (chain_latch's rule by hand: both sides from this one lane)
                 st.pre_mem = st.pre_tgt;
                 st.master_mem = st.master_tgt;
             }
@@ -311,15 +291,8 @@ __global__ __launch_bounds__(kQ4Waves * kWave) void k_lstm_q4(LaunchArgs a)
         const bool live = flg[j] != 0;
         const bool net_on = flg[kQ4Streams + j] != 0;
         ChainPass cp{};
-        cp.K = (flags & CTL_EQ_POST) ? 6 : 1;
-        cp.gain_lane = cp.K - 1;
-        const int k = stage < cp.K ? stage : 0;
-        const int slot = post_slot(k);
-        const bool act = k == 0 ? (flags & CTL_DC_ON) != 0 : ((flags & CTL_EQ_BANDPASS) ? slot == BQ_MID : true);
-        chain_load(cp, ctl, st, slot, act);
-        const float master_mem = (pending0 & PEND_ACTIVATE) ? st.master_tgt : st.master_mem;
-        const float master_tgt = ctl.master_target;                                       // :654
-        cp.g.arm(master_mem, master_tgt, ctl.master_coef);
+        const int slot = chain_setup<false>(cp, ctl, st, flags, stage);
+        const float master_tgt = chain_latch<false>(cp, ctl, st, pending0, live).tgt;     // (stored only for a live stream)
         const bool run = live && stage < cp.K;
         const bool writer = run && stage == cp.K - 1;
         const float* wd = a.wpack + (size_t)kQ4CellWaves * kQ4Regs * kWave;               // Dense weights [H], bias

@@ -99,6 +99,7 @@ __global__ __launch_bounds__(quad_waves(H) * kWave) void k_quad(LaunchArgs a, Qu
     float hcur = (valid && uok) ? nnst[u] : 0.f;
     float c = (CELL == 0 && valid && uok) ? nnst[H + u] : 0.f;
     if (uok) hh[((kQuadRing - 1) * kQuadStreams + j) * HS + u] = hcur;
+    // (ParamRamps by hand: as a ParamRamps k_quad<0, 80> takes other VGPRs, profiles/chain_rules.txt)
     float p_mem[2] = { st.p_mem[0], st.p_mem[1] };
     float p_tgt[2] = { st.p_tgt[0], st.p_tgt[1] };
     float p_step[2] = { st.p_step[0], st.p_step[1] };

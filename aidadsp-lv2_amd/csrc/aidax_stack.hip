@@ -26,33 +26,18 @@ namespace aidax {
 // PARAM1/2 ramps of one block (:634-640 + LinearValueSmoother::next), written to pq[t][2]
 __device__ __forceinline__ void param_ramps(const StreamCtl& ctl, StreamState& st, ChainCtx& c, float* pq, int n, int I, int lane)
 {
-    float p_mem[2] = { st.p_mem[0], st.p_mem[1] };
-    float p_tgt[2] = { st.p_tgt[0], st.p_tgt[1] };
-    float p_step[2] = { st.p_step[0], st.p_step[1] };
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-        const float nt = ctl.p_target[i];
-        if (__builtin_fabsf(p_tgt[i] - nt) >= FLT_EPSILON) {
-            p_tgt[i] = nt;
-            p_step[i] = (p_tgt[i] - p_mem[i]) / ctl.p_den;
-        }
-    }
-    if (c.pending & PEND_PARAM_FIRST) {
-        c.pending &= ~PEND_PARAM_FIRST;
-        p_mem[0] = p_tgt[0];
-        p_mem[1] = p_tgt[1];
-    }
+    ParamRamps pr;
+    pr.load(st);
+    c.pending = pr.begin_block(ctl, c.pending);
     if (I >= 2) {
         for (int t = 0; t < n; ++t) {
-            const float q1 = lin_next(p_mem[0], p_tgt[0], p_step[0]);
-            const float q2 = I >= 3 ? lin_next(p_mem[1], p_tgt[1], p_step[1]) : 0.f;
+            const float q1 = pr.next1();
+            const float q2 = I >= 3 ? pr.next2() : 0.f;
             if (lane == 0) { pq[2 * t] = q1; pq[2 * t + 1] = q2; }
         }
     }
     if (lane == 0) {
-        st.p_mem[0] = p_mem[0]; st.p_mem[1] = p_mem[1];
-        st.p_tgt[0] = p_tgt[0]; st.p_tgt[1] = p_tgt[1];
-        st.p_step[0] = p_step[0]; st.p_step[1] = p_step[1];
+        pr.store(st);
     }
 }
 
