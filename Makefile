@@ -142,11 +142,12 @@ build/asan/asan_own_harness: tests/asan_own_harness.cpp $(HDRS)
 	    -Wall -Wextra -Iinclude -I$(ROCM)/include -D__HIP_PLATFORM_AMD__ tests/asan_own_harness.cpp -o $@
 asan_own: build/asan/asan_own_harness
 
-# ... and the pass-form decision (aidax_pass_form.h: resolve_pass, a header without HIP): tests/form_harness.cpp, tests/test_pass_form_host.py
-build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_pass_form.h $(SRC)/aidax_layout.h
+# ... and the two form decisions (aidax_load_form.h: load_kind, conv_family / conv_form, mfma_form and the one-layer rule; aidax_pass_form.h:
+# resolve_pass — headers without HIP): tests/form_harness.cpp, tests/test_pass_form_host.py
+build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_load_form.h $(SRC)/aidax_pass_form.h $(SRC)/aidax_layout.h include/aidax.h
 	@mkdir -p build/asan
 	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
-	    -Wall -Wextra -I$(SRC) tests/form_harness.cpp -o $@
+	    -Wall -Wextra -Iinclude -I$(SRC) tests/form_harness.cpp -o $@
 asan_form: build/asan/form_harness
 
 oracle:

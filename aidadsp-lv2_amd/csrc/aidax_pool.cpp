@@ -1,10 +1,11 @@
-// aidax_pool.cpp — the core of the stream pool behind the C ABI (aidax_pool.h): which form serves a model, the process launches, device
+// aidax_pool.cpp — the core of the stream pool behind the C ABI (aidax_pool.h): which models have a device path, the process launches, device
 // residency, control latching and the streams' state, around the cabinet IR stage (aidax_ir_stage.h), the model bank (aidax_model_bank.h)
 // and the gate and meters (aidax_stream_stages.h). Models and IRs on their way in: aidax_pool_model.cpp; host buffers: aidax_pool_io.cpp.
 // Host logic only; the kernels are in aidax_kernels.hip. No CPU fallback: any HIP failure is AIDAX_ERR_DEVICE.
 #include <hip/hip_runtime_api.h>
 
 #include <chrono>
+#include <cstdio>
 #include <cmath>
 #include <thread>
 
@@ -25,104 +26,6 @@ bool model_supported(const aidax_model& m)
     }
     if (is_stack_model(m)) return m.n_rnn <= kMaxStackLayers && m.hidden <= 128 && m.hidden % 4 == 0;
     return m.n_rnn == 1 && find_kernel(m.cell, m.hidden) != nullptr;
-}
-
-// Which many-streams form serves a model of the reference's table best at a given stream count. Measured
-// (scratch/perf_table_mfma.py, 256-frame blocks, MI355X): k_quad (4 streams per workgroup on
-// mfma_4x4x1, weights in registers) wins for <= 32 units from 4096 streams (1.15-1.5x over the split form) and
-// for the wide cells at every stream count below that (LSTM-64 1.3-1.6x, LSTM-80 1.3-1.75x, GRU-80 1.2-1.4x);
-// k_mfma (16 streams per workgroup on mfma_16x16x4) takes over for the wide cells from 4096-8192 streams
-// (LSTM-80 @ 16384: 2.3 ms against 4.3 ms for k_quad and 8.4 ms for the one-wave kernel). GRU-64 ties with
-// its register kernel up to 8192 streams and stays there.
-// Round 3 (scratch/perf_lp1.py, profiles/r03_cfg3_forms.txt): the one-launch form of k_mfma_lp (one workgroup per 16
-// streams, the DSP chain on its helper waves) costs the same whatever the stream count while its workgroups fit the
-// machine in one round, and beats every other form when that round is (nearly) full — LSTM-32 209 us against 231,
-// GRU-32 197 / 211, LSTM-40 338 / 346, GRU-64 434 / 468 at 4096 streams on 256 CUs; at 3072 streams the others win.
-// One-layer models on k_mfma_ls1 (k_mfma_ls's body for a lone layer: the recurrent product as bf16 term products, a workgroup per
-// 16 streams): where it beats every other form at 256-frame blocks on 256 CUs (scratch/ls1_ab.py, profiles/r04_ls1_ab.txt) —
-// LSTM-64 from 2048 streams (4096: 306 us against 417 on k_mfma_lp, 16 384: 1 228 against 1 609 on k_mfma), LSTM-80 / GRU-80 from
-// 1024 (4096: 540 / 458 against 716 / 669), LSTM-40 beyond 4096 (8192: 427 against 526), 32 units beyond 6144 (8192: 286 / 248
-// against 345 / 289 on k_quad). GRU-40 / 64 have k_gru_gs (190 us per round of 4096 streams against 244 .. 275 here); 16 units never.
-// (A GRU-80 pool this rule sends to the matrix-core forms runs k_gru_gs<5, 2> — 324 us per 4096 streams against 436 here — and LSTM-40 / 64
-// have k_lstm_gs, below; k_mfma_ls1 then serves LSTM-80, 32 units at many streams, and the A/B runs.)
-// Round 5 (profiles/r05_blocklen_forms*.txt: the table re-measured at 64- and 128-frame blocks, what a host's period really is): the
-// crossovers hold at every block length but two, both wrong at 256 frames too — see many_streams_form — and ONE moves with the block:
-// LSTM-32 at 5632 .. 6144 streams is k_mfma_ls1's from 192-frame blocks (268 against 278 us on k_nn), k_nn's below (84 / 149 us at 64 /
-// 128 frames against 93 / 152). `max_frames` is the pool's block length.
-bool lone_split_pays(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames)
-{
-    const bool off = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_LP_SPLIT"); return e && e[0] == '0'; }();
-    if (off || cus <= 0) return false;
-    const bool lstm = cell == AIDAX_CELL_LSTM;
-    const uint32_t groups = (n + kMfmaStreams - 1) / kMfmaStreams, c = static_cast<uint32_t>(cus);
-    switch (hidden) {
-    case 32: return groups * 2 > c * 3 || (lstm && max_frames >= 192 && groups * 8 >= c * 11);
-    case 40: return lstm && groups > c;
-    case 64: return lstm && groups * 2 > c;
-    case 80: return groups * 4 > c;
-    default: return false;
-    }
-}
-
-// ... and k_lstm_gs (k_gru_gs's structure for one-layer LSTMs: unit-major tiles, a main wave per 16 units, the chain on helper
-// waves): LSTM-64 265 us per round of 4096 streams — ahead of k_quad from 1025 streams on (289 us at 2048) and of k_mfma_ls1
-// throughout (308 / 616 / 1 234 us at 4096 / 8192 / 16 384 against 265 / 528 / 1 057); LSTM-40 265 us, between k_quad (223 us at
-// 2048) and k_mfma_ls1 (two workgroups per CU: 418 us at 8192 against 527) — profiles/r04_ls1_ab.txt. AIDAX_LSTM_GS=0 / 1: never / wherever it serves
-// (LSTM-80 is served too — five main waves, two helpers — but only 4 % ahead of k_mfma_ls1, 483 against 503 us per 4096 streams: not in the rule).
-bool lstm_gs_pays(int cell, int hidden, uint32_t n, int cus)
-{
-    // (read on every call — the worker thread's, at model load: tests switch forms within one process)
-    const int forced = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_LSTM_GS"); return !e ? -1 : e[0] != '0' ? 1 : 0; }();
-    const bool f32 = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_GRU_GM"); return e && e[0] == 'f'; }();
-    if (cell != AIDAX_CELL_LSTM || (hidden != 40 && hidden != 64 && hidden != 80) || forced == 0 || f32) return false;
-    if (forced == 1) return true;
-    if (cus <= 0) return false;
-    const uint32_t groups = (n + kMfmaStreams - 1) / kMfmaStreams, c = static_cast<uint32_t>(cus);
-    return hidden == 64 ? groups * 4 > c : hidden == 80 ? false : groups * 2 > c && groups <= c;
-}
-
-ManyForm many_streams_form(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames)
-{
-    if (lstm_gs_pays(cell, hidden, n, cus)) return MANY_MFMA;
-    const bool lstm = cell == AIDAX_CELL_LSTM;
-    const uint32_t groups = (n + kMfmaStreams - 1) / kMfmaStreams;
-    const bool ls1_off = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_LS1"); return e && e[0] == '0'; }();
-    if (!ls1_off && lone_split_pays(cell, hidden, n, cus, max_frames)) return MANY_MFMA;
-    // Round 5: LSTM-32 between one and one and a half rounds of stream groups (4097 .. 6144 streams on 256 CUs) was k_quad's by the
-    // rule below — which nothing measured there ever supported: k_nn (the split form) is 5 .. 16 % ahead of it at every block length
-    // (5120 streams: 77 / 135 / 249 us at 64 / 128 / 256 frames against 84 / 146 / 271), and k_mfma_ls1 takes over above (lone_split_pays).
-    if (lstm && hidden == 32 && cus > 0 && groups > static_cast<uint32_t>(cus) && groups * 2 <= static_cast<uint32_t>(cus) * 3) return MANY_NONE;
-    const bool full_round = cus > 0 && groups <= static_cast<uint32_t>(cus) && groups * 8 > static_cast<uint32_t>(cus) * 7;
-    if (full_round && (hidden == 32 || hidden == 64 || (hidden == 40 && lstm))) return MANY_MFMA;
-    // One-layer GRUs of 40 (run as 48) / 64 units have k_gru_gm (gate-major tiles: three quarters of the matrix-core work,
-    // the whole run() in one launch; up to two workgroups per CU): GRU-64 326 us flat up to 4096 streams, 595 us at 8192,
-    // 1 140 us at 16384 against 257 / 408 / 859 us for k_nn at 2048 / 3072 / 8192; GRU-40 277-287 us up to 4096 against
-    // 300 (k_nn) / 278 (k_quad) at 3072 and 303 (k_quad) at 4096, 492 / 562 at 8192.
-    // Round 4: with the recurrent product on the bf16 matrix pipe (k_gru_gs) the kernel costs 190 us (GRU-64) / 186 us (GRU-40) per
-    // 256-frame block whatever the stream count up to a full round, and the crossovers moved (scratch/gs_threshold.py,
-    // profiles/r04_gs_threshold.txt): GRU-64 wins from 256 streams on (k_quad 197 us at 256 - 1024, k_nn 225 at 1536 - 2048);
-    // GRU-40 from the point where k_nn needs a second round of waves (2048 streams: 174 us; 2560: 279). AIDAX_GRU_GM=f32 (the
-    // fp32 MFMA kernel, 305 us) keeps round 3's thresholds.
-    const bool gm_f32 = [] { const char* e = AIDAX_HOOK_ENV("AIDAX_GRU_GM"); return e && e[0] == 'f'; }();
-    // Round 5: GRU-64 is k_gru_gs's at EVERY pool size, the one-stream pool of an LV2 instance included — 49.9 / 93.1 / 179 us per block
-    // of 64 / 128 / 256 frames at one stream against 55.4 / 99.1 / 187 on k_quad, 54 / 99 / 188 against 64 / 108 / 197 at 16 .. 192 streams
-    // (the 256-stream threshold of round 4 was measured at 256 frames only, where the gap is 4 %; at a 64-frame period it is 19 %).
-    // Round 6 (advisor): that evidence is blocks of 64 frames and more; a pool created for shorter blocks than any measured (hub mode's
-    // four-frame placeholder pool) keeps round 4's threshold — a sixteenth of a round of stream groups (256 streams on 256 CUs).
-    if (!lstm && cus > 0 && !gm_f32 && ((hidden == 64 && (max_frames >= 64 || groups * 16 >= static_cast<uint32_t>(cus))) || (hidden == 40 && groups * 2 > static_cast<uint32_t>(cus))))
-        return MANY_MFMA;
-    if (!lstm && cus > 0 && ((hidden == 64 && groups * 8 >= static_cast<uint32_t>(cus) * 5) || (hidden == 40 && groups * 8 >= static_cast<uint32_t>(cus) * 7)))
-        return MANY_MFMA;
-    // What is left of the table, in ROUNDS of stream groups like the rules above (round 6: these were stream counts measured on 256 CUs —
-    // 4096 streams = one round of sixteen-stream workgroups there; a partition with 32 or 64 CUs reaches its round at 512 or 1024
-    // streams). A device whose CU count is unknown (cus <= 0) is taken for the one the table was measured on.
-    const uint32_t round = static_cast<uint32_t>(kMfmaStreams) * (cus > 0 ? static_cast<uint32_t>(cus) : 256u);      // streams of one round of workgroups
-    if (hidden <= 32) return n >= round ? MANY_QUAD : MANY_NONE;
-    if (hidden == 40) return n >= 2 * round ? MANY_MFMA : n >= (lstm ? round / 8 : round) ? MANY_QUAD : MANY_NONE;
-    if (hidden == 64 && !lstm) return n >= 4 * round ? MANY_MFMA : n <= round / 4 ? MANY_QUAD : MANY_NONE;
-    // LSTM-64, LSTM-80, GRU-80: their one-wave kernels hold 250-500 weight registers; k_quad is 1.35-1.75x
-    // faster already at 64 streams, k_mfma takes over from a full round of stream groups
-    return n >= round ? MANY_MFMA : MANY_QUAD;
 }
 
 LpGate& lp_gate() { static LpGate g; return g; }
@@ -760,6 +663,17 @@ AIDAX_API int aidax_test_stream_state(aidax_pool* p, uint32_t stream, void* out,
     if (rc != AIDAX_OK) return rc;
     std::memcpy(out, &st, sizeof(StreamState));
     return (int)sizeof(StreamState);
+}
+// (test build only: what choose_form decided for the playing slot, as one text line — tests/test_gpu_load_forms.py)
+AIDAX_API int aidax_test_slot_form(aidax_pool* p, char* buf, uint32_t cap)
+{
+    if (!p || !buf || cap == 0) return fail(AIDAX_ERR_ARG, "null argument");
+    static const char* const kinds[] = { "table", "stack", "conv", "mfma", "quad" };
+    const ModelSlot& m = p->cur;
+    const SlotForm& f = m.form;
+    return std::snprintf(buf, cap, "kind=%s serve=%d fused=%d products=%d round_streams=%u pipe_capacity=%d split_pays=%d q4=%d nn_stride=%u ring=%d",
+                         m.has_model ? kinds[m.kind] : "none", static_cast<int>(f.serve()), f.fused(), f.products(), f.round_streams(), f.pipe_capacity(), f.split_pays(), f.q4(),
+                         m.nn_stride, m.d_ring ? 1 : 0);
 }
 #endif
 

@@ -1,4 +1,4 @@
-// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: the form heuristics, launch — the
+// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: launch — the
 // executor of a PassForm —, create / destroy, controls and stream state), aidax_pool_model.cpp (everything that builds or commits an
 // aidax_staged) and aidax_pool_io.cpp (the host-buffer entry points). Which kernels serve a pass is decided in ONE place, the HIP-free
 // aidax_pass_form.h: a slot carries the SlotForm that choose_form gave it, aidax_pool::pass_form gathers the facts (and reads the per-call
@@ -23,12 +23,7 @@ namespace aidax {
 
 constexpr uint32_t kWarmupFrames = 2048;        // rt-neural-generic.cpp:1077
 constexpr uint32_t kMaxFrames = 8192;           // LDS block buffer bound (32 KiB)
-enum ManyForm { MANY_NONE = 0, MANY_QUAD = 1, MANY_MFMA = 2 };
 bool model_supported(const aidax_model& m);      // which models have a device path (aidax_pool.cpp)
-// the form heuristics (aidax_pool.cpp): which many-streams form serves a table model best, and where k_mfma_ls1 / k_lstm_gs pay
-bool lone_split_pays(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames);
-bool lstm_gs_pays(int cell, int hidden, uint32_t n, int cus);
-ManyForm many_streams_form(int cell, int hidden, uint32_t n, int cus, uint32_t max_frames);
 
 // a flag written on the launch path and read by other threads (aidax_pool_kernel_name, lp_in_use from the worker): an atomic that
 // a struct assignment of its owner (a model swap is one) may copy

@@ -6,6 +6,7 @@
 #include <cmath>
 
 #include "aidax_pool.h"
+#include "aidax_load_form.h"
 
 namespace aidax {
 
@@ -34,57 +35,91 @@ namespace {
 // model gets a hand-over ring (and, stacked, a hold on the device's LpGate) — k_mfma_ls's for ring_streams streams where ls, else k_mfma_lp's
 struct Packed { std::vector<float> wp, wq4; bool lp = false, ls = false; uint32_t ring_streams = 0; };
 
-// Which kernel form serves model m in pool p: fills the slot's host fields, its SlotForm among them, and packs the weights. No allocation, no
-// launch (one device-attribute query). A chained form holds while the slot has its ring (PassFacts::ring_ready): prepare_impl may not get one.
+// The test switches of the load-form decision (aidax_load_form.h), read on every load and every ABI call: tests switch forms within one
+// process. The ONE place that reads the environment for these names; the shipped library compiles every read to "unset".
+FormHooks read_form_hooks()
+{
+    auto tri = [](const char* e) { return !e ? -1 : e[0] != '0' ? 1 : 0; };
+    auto is0 = [](const char* e) { return e && e[0] == '0'; };
+    auto one_of = [](const char* e, char a, char b) { return e && (e[0] == a || e[0] == b) ? e[0] : '\0'; };
+    FormHooks h;
+    h.ls1 = tri(AIDAX_HOOK_ENV("AIDAX_LS1"));
+    h.lstm_gs = tri(AIDAX_HOOK_ENV("AIDAX_LSTM_GS"));
+    h.gru_gm = one_of(AIDAX_HOOK_ENV("AIDAX_GRU_GM"), '0', 'f');
+    h.mfma_lp = tri(AIDAX_HOOK_ENV("AIDAX_MFMA_LP"));
+    h.lp_split = one_of(AIDAX_HOOK_ENV("AIDAX_LP_SPLIT"), '0', '9');
+    h.lp_fused_off = is0(AIDAX_HOOK_ENV("AIDAX_LP_FUSED"));
+    const char* rg = AIDAX_HOOK_ENV("AIDAX_LP_ROUND_GROUPS");
+    h.round_groups_set = rg != nullptr;
+    h.round_groups = rg ? std::atoi(rg) : 0;
+    const char* np = AIDAX_HOOK_ENV("AIDAX_GS_PRODUCTS");
+    h.gs_products = np && np[0] == '9' ? 9 : 6;
+    h.conv_ms_off = is0(AIDAX_HOOK_ENV("AIDAX_CONV_MS"));
+    h.conv_st_off = is0(AIDAX_HOOK_ENV("AIDAX_CONV_ST"));
+    h.conv_fused = tri(AIDAX_HOOK_ENV("AIDAX_CONV_FUSED"));
+    return h;
+}
+
+// Which kernel form serves model m in pool p: packs the weights in the layout of the kind that load_kind names, gathers the facts the packed
+// descriptor gives, lets aidax_load_form.h decide and fills the slot's host fields, its SlotForm among them. No allocation, no launch; the
+// CU count is the pool's (aidax_pool_create asked the device), the occupancy answers are the kernels' own. A chained form holds while the
+// slot has its ring (PassFacts::ring_ready): prepare_impl may not get one.
 int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed& pk)
 {
+    constexpr size_t kCuLds = 160 * 1024;
+    const FormHooks h = read_form_hooks();
+    const LoadPool pool{ p.n_streams, p.max_frames, p.cus, p.force, p.packed_fits };
+    const ModelShape shape{ m->cell, m->hidden, m->n_rnn, is_conv_model(*m), is_stack_model(*m), find_kernel(m->cell, m->hidden) != nullptr, mfma_form_fits(*m) };
     std::vector<float>& wp = pk.wp;
     uint32_t state_floats = 0;
-    // Models of the reference's table on the matrix-core kernels (many_streams_form); AIDAX_KERNEL=quad|mfma force one, every other forced form none
-    auto many = [&p](int cell, int hidden) {
-        return p.force == Force::Quad ? MANY_QUAD : p.force == Force::Mfma ? MANY_MFMA : p.force == Force::None ? many_streams_form(cell, hidden, p.n_streams, p.cus, p.max_frames) : MANY_NONE;
-    };
-    if (is_conv_model(*m)) {
+    switch (load_kind(pool, h, shape, quad_lds_bytes(m->hidden, p.max_frames) <= kCuLds)) {
+    case LoadKind::Conv: {
         ms.kind = ModelSlot::CONV;
         wp = pack_conv(*m, &ms.cdesc, &state_floats);
-        const bool conv_mfma = p.force != Force::Valu && convm_lds_bytes(ms.cdesc, p.ext_chunk()) <= 160 * 1024;
-        // the stacks k_conv_ms admits run there (the contraction as bf16 term products: BASELINE cfg4 60 -> see profiles/r05_cfg4_*); its
-        // per-layer histories live in the stream's state in ITS layout, so the choice holds for the life of the model in this pool
-        // (warm-up, bare-model modes and passes all run the one kernel). AIDAX_CONV_MS=0 (test build): k_conv_mfma, the fp32 partner.
-        const char* cms = AIDAX_HOOK_ENV("AIDAX_CONV_MS");
-        const bool conv_ms = conv_mfma && ms.cdesc.ms_ok && !(cms && cms[0] == '0');
-        if (conv_ms) state_floats = ms.cdesc.ms_state_floats;
-        // ... and of those, the stacks with a compiled geometry (conv_st_shape) take fused blocks of 64 / 128 / 256 frames through k_conv_st,
-        // the streaming form on the same state (AIDAX_CONV_ST=0, test build: k_conv_ms for every block)
-        const char* cst = AIDAX_HOOK_ENV("AIDAX_CONV_ST");
-        if (cst && cst[0] == '0') ms.cdesc.st_ok = 0;
-        // chain passes inside the conv launch while every workgroup of the pool is resident at once (their serial
-        // latency is then paid once per block; in a second round of workgroups it would be paid again, and the packed
-        // k_chain launches around the kernel are cheaper). AIDAX_CONV_FUSED=1 / 0 forces the form.
-        const char* fused = AIDAX_HOOK_ENV("AIDAX_CONV_FUSED");
-        const bool conv_fused = conv_mfma && (p.max_frames > 256      // long blocks go through in time slices: the one-launch form only
-                                              || (fused ? fused[0] != '0'
-                                                        : static_cast<int>(p.n_streams) <= (conv_ms ? convs_resident_streams(p.device, ms.cdesc.st_ok - 1) : convm_resident_streams(ms.cdesc, p.ext_chunk(), p.device))));
-        ms.form = conv_ms ? SlotForm::conv_ms(conv_fused) : conv_mfma ? SlotForm::conv_mfma(conv_fused) : SlotForm::conv();
-        if (!conv_mfma && conv_lds_bytes(ms.cdesc, p.max_frames) > 160 * 1024)
-            return fail(AIDAX_ERR_ARG, "conv model: pool max_frames too large for the LDS activation planes");
-    } else if (m->n_rnn == 1 && find_kernel(m->cell, m->hidden) && many(m->cell, m->hidden) == MANY_QUAD &&
-               chain_lds_bytes(p.max_frames) <= kChainLdsLimit && quad_lds_bytes(m->hidden, p.max_frames) <= 160 * 1024) {
+        const ConvFamily fam = conv_family(pool, h, convm_lds_bytes(ms.cdesc, p.ext_chunk()) <= kCuLds, ms.cdesc.ms_ok != 0, conv_lds_bytes(ms.cdesc, p.max_frames) <= kCuLds);
+        if (fam.refused) return fail(AIDAX_ERR_ARG, "conv model: pool max_frames too large for the LDS activation planes");
+        if (fam.clear_st) ms.cdesc.st_ok = 0;
+        if (fam.ms) state_floats = ms.cdesc.ms_state_floats;
+        const int resident = !fam.by_size ? 0 : fam.ms ? convs_resident_streams(p.device, ms.cdesc.st_ok - 1) : convm_resident_streams(ms.cdesc, p.ext_chunk(), p.device);
+        ms.form = conv_form(fam, pool, h, resident);
+        break;
+    }
+    case LoadKind::Quad:
         ms.kind = ModelSlot::QUAD;
         ms.form = SlotForm::quad();
         wp = pack_quad(*m, &ms.qdesc.bias_off, &ms.qdesc.dense_off);
         state_floats = static_cast<uint32_t>(m->cell == AIDAX_CELL_LSTM ? 2 * m->hidden : m->hidden);
-    } else if (mfma_form_fits(*m) && chain_lds_bytes(p.max_frames) <= kChainLdsLimit &&
-               (is_stack_model(*m) ? p.force != Force::Valu : many(m->cell, m->hidden) == MANY_MFMA)) {
+        break;
+    case LoadKind::Mfma: {
         ms.kind = ModelSlot::MFMA;
         wp = pack_mfma(*m, &ms.mdesc, &state_floats);
-    } else if (is_stack_model(*m)) {
+        const MfmaDesc& d = ms.mdesc;
+        MfmaFacts f{};
+        f.n_layers = d.n_layers; f.hidden = d.hidden; f.cell0 = d.L[0].cell;
+        f.lp_serves = mfma_lp_serves(d); f.lp_fused_serves = mfma_lp_fused_serves(d, p.max_frames);
+        f.ls_serves = mfma_ls_serves(d); f.ls_fused_serves = mfma_ls_fused_serves(d, p.max_frames);
+        f.gru_gm_serves = gru_gm_serves(d); f.gru_gs_serves = gru_gs_serves(d); f.lstm_gs_serves = lstm_gs_serves(d);
+        // (a kernel's LDS is asked of the descriptors it serves only)
+        f.lp_lds_ok = f.lp_serves && mfma_lp_lds_bytes(d, p.max_frames) <= kCuLds;
+        f.lp_fused_lds_ok = f.lp_fused_serves && mfma_lp_lds_bytes(d, p.max_frames, true) <= kCuLds;
+        f.ls_lds_ok = f.ls_serves && mfma_ls_lds_bytes(d, p.max_frames) <= kCuLds;
+        f.ls_fused_lds_ok = f.ls_fused_serves && mfma_ls_lds_bytes(d, p.max_frames, true) <= kCuLds;
+        f.gru_gm_lds_ok = f.gru_gm_serves && gru_gm_lds_bytes(d, p.max_frames) <= kCuLds;
+        f.gru_gs_lds_ok = f.gru_gs_serves && gru_gs_lds_bytes(d, p.max_frames) <= kCuLds;
+        f.lstm_gs_lds_ok = f.lstm_gs_serves && lstm_gs_lds_bytes(d, p.max_frames) <= kCuLds;
+        const MfmaChoice c = mfma_form(pool, h, shape, f);
+        ms.form = c.form;
+        pk.lp = c.lp; pk.ls = c.ls; pk.ring_streams = c.ring_streams;
+        break;
+    }
+    case LoadKind::Stack:
         ms.kind = ModelSlot::STACK;
         ms.form = SlotForm::stack();
         wp = pack_stack(*m, &ms.sdesc, &state_floats);
-        if (stack_lds_bytes(ms.sdesc, p.max_frames) > 160 * 1024)
+        if (stack_lds_bytes(ms.sdesc, p.max_frames) > kCuLds)
             return fail(AIDAX_ERR_ARG, "stacked model: pool max_frames too large for the LDS block buffers");
-    } else {
+        break;
+    case LoadKind::Table: {
         ms.kind = ModelSlot::TABLE;
         ms.kernel = find_kernel(m->cell, m->hidden);
         wp = pack_weights(*m);
@@ -95,6 +130,8 @@ int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed
         // matrix cores; the table kernels' record stays for warm-ups and the bare-model modes
         if (q4_serves(m->cell, m->hidden, m->input_size) && p.force == Force::Q4 && q4_lds_bytes(m->hidden, p.max_frames) <= 64 * 1024) pk.wq4 = pack_q4(*m);
         ms.form = SlotForm::table(pipe_resident_streams(ms.kernel, p.max_frames, p.device), split_form_pays(ms.kernel, p.max_frames), !pk.wq4.empty());
+        break;
+    }
     }
     ms.nn_stride = (state_floats + 3u) & ~3u;
     ms.cell = m->cell;
@@ -105,67 +142,6 @@ int choose_form(const aidax_pool& p, const aidax_model* m, ModelSlot& ms, Packed
     ms.out_gain = m->output_gain;
     ms.model_sr = m->samplerate;
     ms.has_model = true;
-
-    // Stacked model: one workgroup per (16 streams, layer), chained through a ring in global memory — where that adds
-    // parallelism, i.e. while every (group, layer) workgroup gets a CU of its own (2048 streams for two layers on 256
-    // CUs: 1.9x over one workgroup per group; beyond, where the CUs are full either way, a second round of workgroups
-    // costs what the resident weights save: 4096 streams 2.49 against 2.45 ms). AIDAX_MFMA_LP=1 / 0 forces it on / off.
-    const char* lp = AIDAX_HOOK_ENV("AIDAX_MFMA_LP");
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, p.device));
-    const size_t lp_groups = (p.n_streams + kMfmaStreams - 1) / kMfmaStreams;
-    // (one-layer models of <= 48 units in the one-launch form: also in several rounds of workgroups — nothing waits for anything,
-    // and LSTM-40 at 8192 streams measures 521 us against 583 us for k_mfma; profiles/r03_cfg3_forms.txt)
-    const bool lp_rounds_ok = ms.kind == ModelSlot::MFMA && ms.mdesc.n_layers == 1 && ms.mdesc.hidden <= 48 && mfma_lp_fused_serves(ms.mdesc, p.max_frames);
-    // (a one-layer model has no hand-over and nothing to wait for: no hold on the device's gate needed)
-    const bool lp_chained = ms.mdesc.n_layers >= 2;
-    // Round 4: k_mfma_ls is fast enough to pay in SEVERAL rounds too — a pass over more streams than one resident grid holds goes
-    // out as one launch per range of streams (each a resident, cooperative grid; same ring, the counters are per group):
-    // LSTM-96 x 2 at 4096 streams 2 x 0.71 ms against 2.48 ms on k_mfma, at 16 384 streams 8 x 0.71 against 9.42 ms.
-    const char* sp_env = AIDAX_HOOK_ENV("AIDAX_LP_SPLIT");
-    // (a lone layer on k_mfma_ls: AIDAX_LS1=1 / 0 forces it on / off)
-    const char* ls1_env = AIDAX_HOOK_ENV("AIDAX_LS1");
-    const bool ls1 = !lp_chained && (ls1_env ? ls1_env[0] != '0' : lone_split_pays(m->cell, m->hidden, p.n_streams, cus, p.max_frames));
-    const bool ls_ok = ms.kind == ModelSlot::MFMA && (lp_chained || ls1) && mfma_ls_serves(ms.mdesc) && !(sp_env && sp_env[0] == '0') &&
-                       mfma_ls_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
-    const char* rg_env = AIDAX_HOOK_ENV("AIDAX_LP_ROUND_GROUPS");      // (tests: ranges of this many stream groups, so that a small pool goes out in several)
-    const size_t round_groups = rg_env && std::atoi(rg_env) > 0
-                                    ? static_cast<size_t>(std::atoi(rg_env))
-                                    : static_cast<size_t>(cus) / static_cast<size_t>(ms.mdesc.n_layers > 0 ? ms.mdesc.n_layers : 1) / 8 * 8;      // workgroup ids come in eights
-    // ... where k_mfma_ls's time per resident grid beats k_mfma's rate on a full chip (profiles/r04_ls_rounds_ab.txt): 64 units and
-    // more — LSTM-96 x 2 x1.65 / GRU-96 x 2 x1.64, 64 units x 2 x1.17..1.19, x 3 x1.10..1.16, GRU-80 x1.03; below 64 units k_mfma
-    // wins by x1.4..1.65, and LSTM-80 (the four-wave geometry) pays up to two grids' worth of streams only
-    const bool ranges_pay = rg_env || (ms.mdesc.hidden >= 64 && (ms.mdesc.hidden != 80 || ms.mdesc.L[0].cell != 0 || lp_groups <= static_cast<size_t>(cus)));
-    const bool ls_rounds = ls_ok && ranges_pay && round_groups >= (rg_env ? 1u : 8u) && lp_groups > round_groups && !(lp && lp[0] == '1');
-    // (the grid a chained launch asks for: workgroup ids come in eights, so the group count is rounded up — the padded workgroups return
-    // at once, but a cooperative launch counts them: 85 groups x 3 layers are 264 workgroups, not 255)
-    const size_t lp_blocks = (lp_groups + 7) / 8 * 8 * static_cast<size_t>(ms.mdesc.n_layers);
-    const bool lp_pays = lp ? lp[0] != '0' : (lp_rounds_ok || ls_rounds || (ls_ok && !lp_chained) || lp_blocks <= static_cast<size_t>(cus));
-    pk.lp = ms.kind == ModelSlot::MFMA && mfma_lp_serves(ms.mdesc) && lp_pays && mfma_lp_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024;
-    if (ms.kind == ModelSlot::MFMA) {
-        const char* gm = AIDAX_HOOK_ENV("AIDAX_GRU_GM");        // (=0: the four-rows-per-unit kernels; =f32: k_gru_gm with fp32 MFMAs — A/B runs)
-        const char* np = AIDAX_HOOK_ENV("AIDAX_GS_PRODUCTS");   // (=9: every term product of the split operands instead of six)
-        const int gs_products = np && np[0] == '9' ? 9 : 6;
-        // stacked models whose split fragments fit the register file: the same hand-over with the contractions on the bf16 matrix
-        // pipe (k_mfma_ls; AIDAX_LP_SPLIT=0: the fp32 kernel, =9: every term product instead of six — A/B runs)
-        pk.ls = pk.lp && ls_ok;
-        pk.ring_streams = pk.ls && ls_rounds ? static_cast<uint32_t>(round_groups) * kMfmaStreams : p.n_streams;
-        const char* fu = AIDAX_HOOK_ENV("AIDAX_LP_FUSED");      // (=0: packed k_chain launches around the kernel, A/B runs)
-        const bool fused = !(fu && fu[0] == '0') &&
-                           (pk.ls ? mfma_ls_fused_serves(ms.mdesc, p.max_frames) && mfma_ls_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024
-                                  : mfma_lp_fused_serves(ms.mdesc, p.max_frames) && mfma_lp_lds_bytes(ms.mdesc, p.max_frames, true) <= 160 * 1024);
-        // one-layer models, the whole run() in one launch: k_lstm_gs; k_gru_gs (80 units: the split kernel only) ahead of the fp32 k_gru_gm
-        // (such a slot still gets the ring and counters of pk.lp, which no pass of its form can use — a one-layer GRU on k_gru_gs is one:
-        // allocation as it was, left for a change of its own)
-        if (lstm_gs_serves(ms.mdesc) && lstm_gs_pays(m->cell, m->hidden, p.n_streams, cus) && lstm_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
-            ms.form = SlotForm::lstm_gs(gs_products);
-        else if (gru_gs_serves(ms.mdesc) && !(gm && (gm[0] == 'f' || gm[0] == '0')) && gru_gs_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
-            ms.form = SlotForm::gru_gs(gs_products);
-        else if (gru_gm_serves(ms.mdesc) && !(gm && gm[0] == '0') && gru_gm_lds_bytes(ms.mdesc, p.max_frames) <= 160 * 1024)
-            ms.form = SlotForm::gru_gm();
-        else
-            ms.form = pk.ls ? SlotForm::ls(sp_env && sp_env[0] == '9' ? 9 : 6, fused, ls_rounds ? pk.ring_streams : 0u) : pk.lp ? SlotForm::lp(fused) : SlotForm::mfma();
-    }
     return AIDAX_OK;
 }
 
@@ -501,11 +477,11 @@ AIDAX_API int aidax_pool_stream_ir(const aidax_pool* p, uint32_t stream, int32_t
 
 AIDAX_API int aidax_many_streams_form(int cell, int hidden, uint32_t n_streams, int compute_units)
 {
-    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, 256));
+    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, 256, read_form_hooks()));
 }
 AIDAX_API int aidax_many_streams_form_at(int cell, int hidden, uint32_t n_streams, int compute_units, uint32_t max_frames)
 {
-    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, max_frames));
+    return static_cast<int>(many_streams_form(cell, hidden, n_streams, compute_units, max_frames, read_form_hooks()));
 }
 
 AIDAX_API int aidax_model_conv_form(const aidax_model* m)
