@@ -150,6 +150,14 @@ build/asan/form_harness: tests/form_harness.cpp $(SRC)/aidax_load_form.h $(SRC)/
 	    -Wall -Wextra -Iinclude -I$(SRC) tests/form_harness.cpp -o $@
 asan_form: build/asan/form_harness
 
+# ... and the hub's host half (HubBook, aidax_hub_book.h — a header without HIP: seats, the rotating buffers, early closes, dropped periods, the
+# give-up mapping): tests/asan_hub_harness.cpp, tests/test_asan_hub.py
+build/asan/asan_hub_harness: tests/asan_hub_harness.cpp $(SRC)/aidax_hub_book.h include/aidax.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude tests/asan_hub_harness.cpp -o $@
+asan_hub: build/asan/asan_hub_harness
+
 oracle:
 	$(MAKE) -s -C oracle all
 	$(MAKE) -s -C oracle _ref
@@ -158,4 +166,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_own asan_form
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_own asan_form asan_hub
