@@ -88,21 +88,39 @@ typedef float aidax_f32x2 __attribute__((ext_vector_type(2)));
 #define AIDAX_PKB(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", %" #ACC " op_sel:[0,1,0] op_sel_hi:[1,1,1]\n\t"
 #define AIDAX_PKA0(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", 0 op_sel_hi:[1,0,0]\n\t"
 #define AIDAX_PKB0(ACC, W, HQ) "v_pk_fma_f32 %" #ACC ", %" #W ", %" #HQ ", 0 op_sel:[0,1,0] op_sel_hi:[1,1,0]\n\t"
+#define AIDAX_PK16_LINKS AIDAX_PKA(0, 4, 20) AIDAX_PKB0(1, 5, 20) AIDAX_PKA0(2, 6, 21) AIDAX_PKB0(3, 7, 21)                                         \
+                         AIDAX_PKA(0, 8, 22) AIDAX_PKB(1, 9, 22) AIDAX_PKA(2, 10, 23) AIDAX_PKB(3, 11, 23)                                            \
+                         AIDAX_PKA(0, 12, 24) AIDAX_PKB(1, 13, 24) AIDAX_PKA(2, 14, 25) AIDAX_PKB(3, 15, 25)                                          \
+                         AIDAX_PKA(0, 16, 26) AIDAX_PKB(1, 17, 26) AIDAX_PKA(2, 18, 27) AIDAX_PKB(3, 19, 27)                                          \
+                         "v_pk_add_f32 %0, %0, %1\n\t"                                                                                                \
+                         "v_pk_add_f32 %2, %2, %3"
+#define AIDAX_PK16_OPERANDS : "+v"(pA), "=&v"(pB), "=&v"(pC), "=&v"(pD)                                                                                  \
+                 : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]),          \
+                   "v"(w[11]), "v"(w[12]), "v"(w[13]), "v"(w[14]), "v"(w[15]),                                                                         \
+                   "v"(hq[0]), "v"(hq[1]), "v"(hq[2]), "v"(hq[3]), "v"(hq[4]), "v"(hq[5]), "v"(hq[6]), "v"(hq[7])
 __device__ __forceinline__ aidax_f32x2 pk_fma_lds16(aidax_f32x2 pA, const aidax_f32x2* w, const aidax_f32x2* hq)
 {
     aidax_f32x2 pB, pC, pD;
-    asm volatile(AIDAX_PKA(0, 4, 20) AIDAX_PKB0(1, 5, 20) AIDAX_PKA0(2, 6, 21) AIDAX_PKB0(3, 7, 21)
-                 AIDAX_PKA(0, 8, 22) AIDAX_PKB(1, 9, 22) AIDAX_PKA(2, 10, 23) AIDAX_PKB(3, 11, 23)
-                 AIDAX_PKA(0, 12, 24) AIDAX_PKB(1, 13, 24) AIDAX_PKA(2, 14, 25) AIDAX_PKB(3, 15, 25)
-                 AIDAX_PKA(0, 16, 26) AIDAX_PKB(1, 17, 26) AIDAX_PKA(2, 18, 27) AIDAX_PKB(3, 19, 27)
-                 "v_pk_add_f32 %0, %0, %1\n\t"
-                 "v_pk_add_f32 %2, %2, %3"
-                 : "+v"(pA), "=&v"(pB), "=&v"(pC), "=&v"(pD)
-                 : "v"(w[0]), "v"(w[1]), "v"(w[2]), "v"(w[3]), "v"(w[4]), "v"(w[5]), "v"(w[6]), "v"(w[7]), "v"(w[8]), "v"(w[9]), "v"(w[10]),
-                   "v"(w[11]), "v"(w[12]), "v"(w[13]), "v"(w[14]), "v"(w[15]),
-                   "v"(hq[0]), "v"(hq[1]), "v"(hq[2]), "v"(hq[3]), "v"(hq[4]), "v"(hq[5]), "v"(hq[6]), "v"(hq[7]));
+    asm volatile(AIDAX_PK16_LINKS AIDAX_PK16_OPERANDS);
     return pA + pC;
 }
+// ... with the last add inside the statement as well (LstmCell<32>'s paired frame, k_lstm_pipe4<32> only). The wait state the compiler wants
+// behind a packed instruction whose first source reads both halves is not the hardware's: v_pk_add_f32 writes whole registers, and the
+// compiler's own tanh_rat steps are read in the next slot. The caller has ONE independent instruction per frame — the next frame's input
+// pair — and puts it behind this statement, where it is the wait state the compiler wants between a statement and the reader of its
+// result; the clamp that reads the sum has to be tanh_rat<., true>'s (the compiler does not know that a statement's output is no
+// signalling NaN and would quiet it first).
+// (the compiler's rule looks at the registers the next instruction WRITES as well: pB, pC, pD go back to the caller, who keeps them
+// occupied with pk_hold() until the input pair is issued — otherwise it lands in one of them and is padded itself)
+__device__ __forceinline__ aidax_f32x2 pk_fma_lds16_sum(aidax_f32x2 pA, const aidax_f32x2* w, const aidax_f32x2* hq, aidax_f32x2& pB, aidax_f32x2& pC, aidax_f32x2& pD)
+{
+    asm volatile(AIDAX_PK16_LINKS "\n\tv_pk_add_f32 %0, %0, %2" AIDAX_PK16_OPERANDS);
+    return pA;
+}
+// no instruction: the three pairs stay allocated up to here
+__device__ __forceinline__ void pk_hold(aidax_f32x2 pB, aidax_f32x2 pC, aidax_f32x2 pD) { asm volatile("" : : "v"(pB), "v"(pC), "v"(pD)); }
+#undef AIDAX_PK16_LINKS
+#undef AIDAX_PK16_OPERANDS
 #undef AIDAX_PKA
 #undef AIDAX_PKB
 #undef AIDAX_PKA0
@@ -120,6 +138,30 @@ __device__ __forceinline__ Pair share_halves(float v)
     const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
     const unsigned r0 = r[0], r1 = r[1];
     return { __builtin_bit_cast(float, r0), __builtin_bit_cast(float, r1) };
+}
+
+// share_halves(go * t).hi with the product computed TWICE by one instruction (LstmCell<32>'s paired frame, k_lstm_pipe4<32> only): the swap
+// exchanges the upper half of one register with the lower half of ANOTHER, so both must hold the product — a v_mul_f32 and a v_mov_b32
+// copy in share_halves' form, here one v_pk_mul_f32 whose two halves both read {go, t} (op_sel_hi:[0,0]): the same IEEE multiply on the
+// same operands, twice. Multiply, wait states and swap are ONE asm statement on a fixed register pair, for two reasons:
+//   * an asm operand's halves cannot be named, and the swap needs the pair's two registers one by one;
+//   * the compiler's hazard recognizer does not see a VALU write inside an asm statement: with the swap left to the compiler nothing
+//     would stand between the multiply and the swap that reads it, and that hazard is real (two wait states: the `s_nop 1` the compiler
+//     puts in front of every v_permlane32_swap of its own). It is spelled out here and stays.
+// The result comes back in the pair's EVEN register, where the next frame's packed own-unit FMA can broadcast it without a copy.
+__device__ __forceinline__ float mul_share_halves_hi(float go, float t)
+{
+    typedef float f32x2_t __attribute__((ext_vector_type(2)));
+    f32x2_t gp, tp;                      // (the upper halves are not read and stay undefined: no register is spent on them)
+    gp.x = go; tp.x = t;
+    float lo, hi;
+    asm volatile("v_pk_mul_f32 v[2:3], %2, %3 op_sel_hi:[0,0]\n\t"
+                 "s_nop 1\n\t"
+                 "v_permlane32_swap_b32 v3, v2"
+                 : "={v3}"(lo), "={v2}"(hi)
+                 : "v"(gp), "v"(tp));
+    (void)lo;
+    return hi;
 }
 
 // every lane gets (value of the even 16-lane row of its row pair, value of the odd row)
@@ -184,10 +226,12 @@ __device__ __forceinline__ float tanh_rat_clamp(float v) { return __builtin_fmin
 // broadcast {u, u} in that place (op_sel_hi:[0,1,1]: how the first step has always come out, its {p, q} being a constant). This holds as
 // long as the compiler keeps the operand order it is given — it does not canonicalise the two factors of an fma today; the per-frame tally
 // in profiles/lstm32_frame_slots.txt is what shows it if that changes. Every other caller keeps the form, and so the schedule, it had.
-template <bool kUFirst = false>
+// kMed3 (the same frame in k_lstm_pipe4<32>, on the sum an asm statement returns): the clamp as the v_med3_f32 the compiler makes of
+// tanh_rat_clamp wherever it knows that v is no signalling NaN — the same instruction, asked for by name.
+template <bool kUFirst = false, bool kMed3 = false>
 __device__ __forceinline__ float tanh_rat(float v)
 {
-    const float x = tanh_rat_clamp(v);
+    const float x = kMed3 ? __builtin_amdgcn_fmed3f(v, -kTanhClamp, kTanhClamp) : tanh_rat_clamp(v);
     const float u = x * x;
 #ifndef AIDAX_TANH_PLAIN
     // The first three Horner steps of P and all three of Q side by side in v_pk_fma_f32 ({p, q} <- {p, q} * {u, u} + {cP, cQ}: the same FMAs on the same

@@ -49,12 +49,15 @@ namespace aidax {
 // kept redundantly. S = 2 (part 0: i, g; part 1: f, o): part 0 sends i*g over with ONE swap and the cell state lives in
 // part 1 only (c, h of the part-0 lanes are scratch; they publish into a spare slot) — three instructions instead of six
 // on the recurrence's critical path.
-template <int H, bool ROTP = true>
+// PAIRS (k_lstm_pipe4<32, false> alone turns it on; every other kernel keeps the frame and the instruction stream it had): the ROT frame's
+// paired operations packed, see step.
+template <int H, bool ROTP = true, bool PAIRS = false>
 struct LstmCell {
     static constexpr LaneMap M = lstm_map(H);
     static constexpr int S = M.S, SLOTS = M.slots, NU = M.NU, GPL = M.GPL;
     static constexpr int PACK = lstm_pack_regs(H);         // of the model's primary record (the Dense tail sits behind it)
     static constexpr int STATE = 2 * H;
+    static constexpr bool kPairs = PAIRS;
     static constexpr bool ROT4 = ROTP && lstm_rot4(H);     // S = 4, H <= 16: every recurrent FMA by row rotation, no LDS read
     static constexpr int KW = lstm_row_weights(H, ROT4);   // recurrent weights per gate row in this instantiation's record
 
@@ -63,6 +66,8 @@ struct LstmCell {
     // one instruction advances both rows' accumulators by one unit (see step)
     typedef float f32x2 __attribute__((ext_vector_type(2)));
     f32x2 wl2[16];
+    // PAIRS: the two gate rows' own-unit weight, input weight and bias side by side as well, and the next frame's {a0, a1} = bias + wx * x
+    f32x2 w02, wx2, b2, ain;
     float wx[NU][GPL][kMaxInputs];
     float bias[NU][GPL];
     float wd[NU], bd;
@@ -110,6 +115,11 @@ struct LstmCell {
             constexpr int kRow = KW + kMaxInputs + 1;
 #pragma unroll
             for (int k = 0; k < 16; ++k) wl2[k] = f32x2{ wp[(16 + k) * kWave + lane], wp[(kRow + 16 + k) * kWave + lane] };
+            if constexpr (PAIRS) {
+                w02 = f32x2{ wp[lane], wp[kRow * kWave + lane] };
+                wx2 = f32x2{ wp[KW * kWave + lane], wp[(kRow + KW) * kWave + lane] };
+                b2 = f32x2{ wp[(KW + kMaxInputs) * kWave + lane], wp[(kRow + KW + kMaxInputs) * kWave + lane] };
+            }
         }
 #pragma unroll
         for (int e = 0; e < GPL; ++e) {
@@ -165,15 +175,23 @@ struct LstmCell {
     // NI = inputs that can be non-zero (the packer zero-fills the weights of absent inputs).
     // WINDOW > 0 fences the scheduler every WINDOW float4 loads of h, bounding the registers held by
     // in-flight LDS reads (the many-streams kernels trade that latency for occupancy); 0 = all at once.
-    template <int NI = kMaxInputs, int WINDOW = 0, bool TR = false>
-    __device__ __forceinline__ void step(float x0, float x1, float x2, const float* hprev, float* hout)
+    // PAIRS: {a0, a1} = {x, x} * {wx0, wx1} + {b0, b1} of the frame that comes, see step
+    // (x = half `hi` of xp, a pair as it came from LDS: selected by the instruction, no copy)
+    template <int hi>
+    __device__ __forceinline__ void input_pair(f32x2 xp) { ain = __builtin_elementwise_fma(__builtin_shufflevector(xp, xp, hi, hi), wx2, b2); }
+
+    // (PAIRS: NEXT = there is a frame behind this one in the tile and xn is its sample; the tile's first frame is input_pair()'s)
+    template <int NI = kMaxInputs, int WINDOW = 0, bool TR = false, bool NEXT = false, int kNextHi = 0>
+    __device__ __forceinline__ void step(float x0, float x1, float x2, const float* hprev, float* hout, f32x2 xn = f32x2{ 0.f, 0.f })
     {
         PT_STAMP(0);                                        // frame starts
         float acc[NU][GPL];
+        static_assert(!PAIRS || (ROTP && lstm_rot2(H) && NI == 1), "the paired frame is the ROT frame of a one-input model");
 #pragma unroll
         for (int m = 0; m < NU; ++m)
 #pragma unroll
             for (int e = 0; e < GPL; ++e) {
+                if constexpr (PAIRS) { acc[m][e] = 0.f; continue; }      // (ain holds them, see the ROT branch)
                 float a = bias[m][e];
                 a = __builtin_fmaf(wx[m][e][0], x0, a);
                 if constexpr (NI >= 2) a = __builtin_fmaf(wx[m][e][1], x1, a);
@@ -194,8 +212,24 @@ struct LstmCell {
             __builtin_amdgcn_sched_barrier(0);
             const float hr = h[0];                          // h(t-1) of this lane's unit: every lane holds its unit's
             float a0 = acc[0][0], a1 = acc[0][1];
+            if constexpr (PAIRS) {
+                // PAIRS (k_lstm_pipe4<32, false>): what the frame does to BOTH gate rows with the same second operand is one packed instruction,
+                // as the LDS half below has always been — the same FMA / multiply on the same operands in the same order, the broadcast
+                // operand written first so that the compiler pads nothing behind it (tanh_rat's kUFirst, aidax_device.h):
+                //   {a0, a1} = {x, x} * {wx0, wx1} + {b0, b1}     input_pair(): one v_pk_fma_f32 for two v_fma_f32
+                //   {a0, a1} += {h, h} * {w00, w10}               here: one v_pk_fma_f32 for two v_fmac_f32; the rotation chains stay as they are
+                //   {hn, hn} = {go, go} * {t, t}                  mul_share_halves_hi(): one v_pk_mul_f32 for v_mul_f32 + v_mov_b32
+                // The input pair is the one instruction of a frame that does not hang on h: the frame BEFORE issues it, right behind the LDS
+                // half's statement — which holds the last add as well here (pk_fma_lds16_sum) — where it is the wait state the compiler
+                // wants between a statement and the reader of its result; both pads around the last add are gone for it. 91.3 instructions
+                // per frame for 95.4, 56.08 -> 55.41 us per 256-frame launch: profiles/lstm32_frame_pairs.txt (the hazards that keep their
+                // wait states: lstm32_frame_slots.txt, section 2).
+                const f32x2 a = __builtin_elementwise_fma(f32x2{ hr, hr }, w02, ain);
+                a0 = a.x; a1 = a.y;
+            } else {
             a0 = __builtin_fmaf(w[0][0][0], hr, a0);
             a1 = __builtin_fmaf(w[0][1][0], hr, a1);
+            }
             fmac_row_ror_1_15(a0, hr, w[0][0]);               // rotations 1..15 of each row: one asm statement per row
             fmac_row_ror_1_15(a1, hr, w[0][1]);
             // (the rows' rotations as four chains — row x even / odd rotation, round robin — measured no better: 64.6 against 64.25 us)
@@ -210,8 +244,17 @@ struct LstmCell {
             // three v_mov_b64 and three s_nop 0 per frame from the compiler — eight issue slots of this wave; profiles/lstm32_frame_slots.txt)
             const f32x2 hq[8] = { f32x2{ q0.x, q0.y }, f32x2{ q0.z, q0.w }, f32x2{ q1.x, q1.y }, f32x2{ q1.z, q1.w },
                                   f32x2{ q2.x, q2.y }, f32x2{ q2.z, q2.w }, f32x2{ q3.x, q3.y }, f32x2{ q3.z, q3.w } };
-            const f32x2 a01 = pk_fma_lds16(f32x2{ a0, a1 }, wl2, hq);
+            f32x2 a01, pB, pC, pD;
+            if constexpr (PAIRS) a01 = pk_fma_lds16_sum(f32x2{ a0, a1 }, wl2, hq, pB, pC, pD);
+            else a01 = pk_fma_lds16(f32x2{ a0, a1 }, wl2, hq);
             acc[0][0] = a01.x; acc[0][1] = a01.y;
+            if constexpr (PAIRS && NEXT) {
+                // (nothing crosses a sched_barrier: the product, then the next frame's input pair, then the activations that read the product)
+                __builtin_amdgcn_sched_barrier(0);
+                input_pair<kNextHi>(xn);
+                pk_hold(pB, pC, pD);
+                __builtin_amdgcn_sched_barrier(0);
+            }
             PT_STAMP(2);                                    // products done
         } else {
         const float4* hv = reinterpret_cast<const float4*>(hprev);
@@ -243,7 +286,7 @@ struct LstmCell {
                 } else if (S == 2 && e == 0) {              // (i | f): sigmoid in both halves
                     act[e] = sigmoid_pre(acc[m][e]);
                 } else {
-                    act[e] = __builtin_fmaf(tanh_rat<ROT>(acc[m][e]), aka[e], akb[e]);
+                    act[e] = __builtin_fmaf(tanh_rat<ROT, PAIRS>(acc[m][e]), aka[e], akb[e]);
                 }
             }
             PT_STAMP(3);                                    // gate activations issued
@@ -267,12 +310,17 @@ struct LstmCell {
             const float cn = __builtin_fmaf(gf, c[m], gi_gg);
             c[m] = cn;
 #ifdef AIDAX_TANHC_EXP
-            const float hn = go * tanh_exp(cn);             // experiment: the exp form for tanh(c) only (scratch/ab_tanhc.sh)
+            const float th = tanh_exp(cn);                  // experiment: the exp form for tanh(c) only (scratch/ab_tanhc.sh)
 #else
-            const float hn = go * tanh_rat<ROT>(cn);
+            const float th = tanh_rat<ROT>(cn);
 #endif
-            if constexpr (ROT) h[m] = share_halves(hn).hi;  // the (f, o) half's h into both halves: the rotations read it
-            else h[m] = hn;
+            if constexpr (PAIRS) {
+                h[m] = mul_share_halves_hi(go, th);         // hn = go * tanh(c') twice from one instruction, then the swap
+            } else {
+                const float hn = go * th;
+                if constexpr (ROT) h[m] = share_halves(hn).hi;  // the (f, o) half's h into both halves: the rotations read it
+                else h[m] = hn;
+            }
         }
         PT_STAMP(4);                                        // h(t) in registers
         publish_h(hout);
@@ -294,6 +342,7 @@ struct GruCell {
     static constexpr int KS = H / S;          // recurrent columns per lane (K-split across the S lanes of a unit)
     static constexpr int PACK = gru_pack_regs(H);
     static constexpr int STATE = H;
+    static constexpr bool kPairs = false;                 // (LstmCell's paired frame: not here)
 #ifdef AIDAX_PIPE_TRACE
     unsigned long long ts6 = 0, ts[6] = { 0, 0, 0, 0, 0, 0 };      // (LstmCell's frame stamps: not taken here)
 #endif
@@ -1217,12 +1266,20 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
                 };
                 fetch_x(0);
                 if constexpr (!kCond) {
+                    typedef float f32x2 __attribute__((ext_vector_type(2)));
+                    if constexpr (Cell::kPairs) cell.template input_pair<0>(f32x2{ xr[0], xr[1] });
 #pragma unroll
                     for (int f = 0; f < kSB; ++f) {
                         if ((f & 3) == 1 && f / 4 + 1 < kSB / 4) fetch_x(f / 4 + 1);
 #ifndef AIDAX_P4_BARRIER
                         if (f == kSB - 4) ahead = *(const volatile p4_lds_i2*)(const p4_lds_i2*)(prog);
 #endif
+                        if constexpr (Cell::kPairs) {
+                            // (the paired LSTM-32 frame issues the NEXT frame's input pair itself, see LstmCell::step)
+                            if (f + 1 < kSB && (f & 1)) cell.template step<1, 0, false, true, 0>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f + 1], xr[(f + 2) % kSB] });
+                            else if (f + 1 < kSB) cell.template step<1, 0, false, true, 1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f], xr[f + 1] });
+                            else cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
+                        } else
                         cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
                     }
                 } else {
@@ -1563,7 +1620,9 @@ template <int H, bool kCond = false>
 __global__ __launch_bounds__(kP4Waves * kWave) void k_lstm_pipe4(LaunchArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    stream_body_pipe4<LstmCell<H>, kCond>(a, smem);
+    // (LSTM-32, unconditioned — cfg2's kernel — runs the frame with its paired operations packed; the conditioned kernel and every other
+    // kernel on LstmCell<32> keep the frame they had)
+    stream_body_pipe4<LstmCell<H, true, H == 32 && !kCond>, kCond>(a, smem);
 }
 
 template <int H, bool kCond = false>
