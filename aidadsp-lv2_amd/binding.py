@@ -87,6 +87,28 @@ class GateState(C.Structure):
 GATE_STATE_DTYPE = np.dtype([("hold_left", "<u4"), ("atten", "<u4")])
 
 
+class TunerParams(C.Structure):
+    """aidax_tuner_params: the stream tuners as a user sets them (window and hop in frames, the range in Hz)"""
+    _fields_ = [("window", C.c_uint32), ("hop", C.c_uint32), ("f_min", C.c_float), ("f_max", C.c_float), ("threshold", C.c_float),
+                ("clarity_min", C.c_float), ("level_min_db", C.c_float)]
+
+
+class TunerRec(C.Structure):
+    """aidax_tuner_rec: the designed record (40 bytes), what aidax_tuner_design makes of TunerParams at a sample rate"""
+    _fields_ = [("window", C.c_uint32), ("hop", C.c_uint32), ("tmin", C.c_uint32), ("tmax", C.c_uint32), ("threshold", C.c_float),
+                ("clarity_min", C.c_float), ("level_min", C.c_float), ("reserved", C.c_float), ("samplerate", C.c_double)]
+
+
+class TunerReadingStruct(C.Structure):
+    """aidax_tuner_reading: one stream's reading (32 bytes)"""
+    _fields_ = [("frame", C.c_uint64), ("analyses", C.c_uint32), ("lag", C.c_uint32), ("hz", C.c_float), ("period", C.c_float),
+                ("clarity", C.c_float), ("level", C.c_float)]
+
+
+TunerReading = np.dtype([("frame", "<u8"), ("analyses", "<u4"), ("lag", "<u4"), ("hz", "<f4"), ("period", "<f4"), ("clarity", "<f4"),
+                         ("level", "<f4")])
+
+
 class BusLimitParams(C.Structure):
     """aidax_bus_limit_params: a bus limiter as a user sets it (the ceiling in dB, times in ms)"""
     _fields_ = [("ceiling_db", C.c_float), ("lookahead_ms", C.c_float), ("hold_ms", C.c_float)]
@@ -281,6 +303,17 @@ def lib() -> C.CDLL:
         L.aidax_pool_set_gate.argtypes = [vp, i32, C.POINTER(GateParams)]
         L.aidax_pool_stream_gate.argtypes = [vp, u32, C.POINTER(GateParams), C.POINTER(C.c_int)]
         L.aidax_pool_read_gate.argtypes = [vp, u32, u32, C.POINTER(GateState)]
+    if hasattr(L, "aidax_pool_set_tuning"):        # (... or from before the stream tuners)
+        L.aidax_tuner_params_default.argtypes = [C.POINTER(TunerParams)]
+        L.aidax_tuner_params_default.restype = None
+        L.aidax_tuner_design.argtypes = [C.c_double, C.POINTER(TunerParams), C.POINTER(TunerRec)]
+        L.aidax_tuner_note.argtypes = [C.c_double, C.c_double, C.POINTER(i32), _fp]
+        L.aidax_pool_set_tuning.argtypes = [vp, C.POINTER(TunerParams)]
+        L.aidax_pool_tuning.argtypes = [vp, C.POINTER(TunerRec)]
+        L.aidax_pool_set_tuner.argtypes = [vp, i32, C.c_int]
+        L.aidax_pool_stream_tuner.argtypes = [vp, u32, C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
+        L.aidax_pool_read_tuners.argtypes = [vp, u32, u32, C.POINTER(TunerReadingStruct)]
+        L.aidax_pool_read_tuner_curve.argtypes = [vp, u32, _fp, u32]
     if hasattr(L, "aidax_pool_set_buses"):         # (... or from before the mix buses)
         L.aidax_pool_set_buses.argtypes = [vp, u32]
         L.aidax_pool_buses.argtypes = [vp]
@@ -348,6 +381,31 @@ def gate_design(params: GateParams, samplerate: float) -> GateRec:
     out = GateRec()
     _check(lib().aidax_gate_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
     return out
+
+
+def tuner_params(**kw) -> TunerParams:
+    """aidax_tuner_params_default, with the named fields replaced"""
+    p = TunerParams()
+    lib().aidax_tuner_params_default(C.byref(p))
+    for k, v in kw.items():
+        if k not in dict(TunerParams._fields_):
+            raise KeyError(k)
+        setattr(p, k, v)
+    return p
+
+
+def tuner_design(samplerate: float, params: TunerParams) -> TunerRec:
+    """aidax_tuner_design: the record of `params` at `samplerate` (pure, host only)"""
+    out = TunerRec()
+    _check(lib().aidax_tuner_design(samplerate, C.byref(params) if params is not None else None, C.byref(out)))
+    return out
+
+
+def tuner_note(hz: float, a4_hz: float = 440.0):
+    """aidax_tuner_note: (the nearest equal-tempered MIDI note, the deviation in cents)"""
+    note, cents = C.c_int32(0), C.c_float(0.0)
+    _check(lib().aidax_tuner_note(hz, a4_hz, C.byref(note), C.byref(cents)))
+    return note.value, cents.value
 
 
 def bus_reverb_design(params: BusReverbParams, samplerate: float) -> BusReverbRec:
@@ -671,6 +729,44 @@ class Pool:
             count = self.n_streams - first
         out = np.zeros(max(count, 0), METER_DTYPE)
         _check(lib().aidax_pool_read_meters(self.h, first, count, out.ctypes.data_as(C.POINTER(StreamMeter)), 1 if clear else 0))
+        return out
+
+    def set_tuning(self, params: Optional[TunerParams]):
+        """aidax_pool_set_tuning: the tuner stage with this design (the first enabling call allocates and fixes the design: a set-up
+        side call), None: off"""
+        _check(lib().aidax_pool_set_tuning(self.h, C.byref(params) if params is not None else None))
+
+    def tuning(self):
+        """aidax_pool_tuning: (the design as a TunerRec, whether the stage is on)"""
+        out = TunerRec()
+        on = lib().aidax_pool_tuning(self.h, C.byref(out))
+        return out, bool(on)
+
+    def set_tuner(self, on: bool, stream: int = ALL_STREAMS):
+        """aidax_pool_set_tuner: the stream's (default: every stream's) tuner on or off; off -> on restarts it"""
+        _check(lib().aidax_pool_set_tuner(self.h, stream, 1 if on else 0))
+
+    def stream_tuner(self, stream: int):
+        """aidax_pool_stream_tuner: (whether the stream's tuner is on, its frame count as the host mirrors it)"""
+        on, pos = C.c_int(0), C.c_uint64(0)
+        _check(lib().aidax_pool_stream_tuner(self.h, stream, C.byref(on), C.byref(pos)))
+        return bool(on.value), pos.value
+
+    def read_tuners(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """aidax_pool_read_tuners: the readings of `count` streams from `first` (default: all from `first` on) as a structured array with
+        aidax_tuner_reading's field names, behind every pass issued so far"""
+        if count is None:
+            count = self.n_streams - first
+        out = np.zeros(max(count, 0), TunerReading)
+        _check(lib().aidax_pool_read_tuners(self.h, first, count, out.ctypes.data_as(C.POINTER(TunerReadingStruct))))
+        return out
+
+    def read_tuner_curve(self, stream: int, count: Optional[int] = None) -> np.ndarray:
+        """aidax_pool_read_tuner_curve: the NSDF row of the stream's last analysis, lags 0 .. count - 1 (default: all tmax + 2)"""
+        if count is None:
+            count = self.tuning()[0].tmax + 2
+        out = np.zeros(max(count, 0), np.float32)
+        _check(lib().aidax_pool_read_tuner_curve(self.h, stream, out.ctypes.data_as(_fp), count))
         return out
 
     def set_gate(self, params: Optional[GateParams], stream: int = ALL_STREAMS):

@@ -334,4 +334,55 @@ AIDAX_API int aidax_bus_reverb_design(const aidax_bus_reverb_params* params, dou
     return AIDAX_OK;
 }
 
+// The stream tuners' design (include/aidax.h, "Stream tuners"): the lag range of [f_min, f_max] at the sample rate, in fp64, the
+// shortest lag rounded down and the longest rounded up so that the range holds both frequencies.
+AIDAX_API void aidax_tuner_params_default(aidax_tuner_params* params)
+{
+    if (!params) return;
+    *params = aidax_tuner_params{ 2048u, 1024u, 70.f, 1400.f, 0.93f, 0.5f, -60.f };
+}
+
+AIDAX_API int aidax_tuner_design(double samplerate, const aidax_tuner_params* params, aidax_tuner_rec* out)
+{
+    using aidax::fail;
+    if (!params || !out) return fail(AIDAX_ERR_ARG, "tuner_design: null argument");
+    const aidax_tuner_params& t = *params;
+    if (!(samplerate > 0.0) || !std::isfinite(samplerate)) return fail(AIDAX_ERR_ARG, "tuner_design: samplerate must be positive");
+    if (t.window != 1024u && t.window != 2048u && t.window != 4096u) return fail(AIDAX_ERR_ARG, "tuner_design: window must be 1024, 2048 or 4096");
+    if (t.hop < 64u || t.hop > 65536u || t.hop % 16u != 0u) return fail(AIDAX_ERR_ARG, "tuner_design: hop must be a multiple of 16 from 64 to 65536");
+    if (!std::isfinite(t.f_min) || !std::isfinite(t.f_max) || !std::isfinite(t.threshold) || !std::isfinite(t.clarity_min) || !std::isfinite(t.level_min_db))
+        return fail(AIDAX_ERR_ARG, "tuner_design: every parameter must be finite");
+    if (!(t.f_min > 0.f) || !(t.f_max > 0.f) || t.f_min > t.f_max) return fail(AIDAX_ERR_ARG, "tuner_design: 0 < f_min <= f_max");
+    if (!(t.threshold > 0.f && t.threshold <= 1.f)) return fail(AIDAX_ERR_ARG, "tuner_design: threshold must be in (0, 1]");
+    if (!(t.clarity_min >= 0.f && t.clarity_min <= 1.f)) return fail(AIDAX_ERR_ARG, "tuner_design: clarity_min must be in [0, 1]");
+    if (t.level_min_db > 0.f) return fail(AIDAX_ERR_ARG, "tuner_design: level_min_db must not exceed 0");
+    const double lo = std::floor(samplerate / static_cast<double>(t.f_max)), hi = std::ceil(samplerate / static_cast<double>(t.f_min));
+    if (!(lo >= 2.0)) return fail(AIDAX_ERR_ARG, "tuner_design: f_max is above half the samplerate (tmin < 2)");
+    if (!(hi <= static_cast<double>(t.window / 2u - 1u))) return fail(AIDAX_ERR_ARG, "tuner_design: f_min needs a longer window (tmax > window / 2 - 1)");
+    aidax_tuner_rec r{};
+    r.window = t.window;
+    r.hop = t.hop;
+    r.tmin = static_cast<uint32_t>(lo);
+    r.tmax = static_cast<uint32_t>(hi);
+    r.threshold = t.threshold;
+    r.clarity_min = t.clarity_min;
+    r.level_min = t.level_min_db <= -200.f ? 0.f : static_cast<float>(std::pow(10.0, static_cast<double>(t.level_min_db) / 20.0));
+    r.samplerate = samplerate;
+    *out = r;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_tuner_note(double hz, double a4_hz, int32_t* midi_note, float* cents)
+{
+    using aidax::fail;
+    if (!midi_note || !cents) return fail(AIDAX_ERR_ARG, "tuner_note: null argument");
+    if (!(hz > 0.0) || !std::isfinite(hz) || !(a4_hz > 0.0) || !std::isfinite(a4_hz)) return fail(AIDAX_ERR_ARG, "tuner_note: frequencies must be positive and finite");
+    const double n = 69.0 + 12.0 * std::log2(hz / a4_hz);
+    const double nearest = std::floor(n + 0.5);
+    if (!(nearest >= -1000.0 && nearest <= 1000.0)) return fail(AIDAX_ERR_ARG, "tuner_note: the frequency is out of any note range");
+    *midi_note = static_cast<int32_t>(nearest);
+    *cents = static_cast<float>(100.0 * (n - nearest));
+    return AIDAX_OK;
+}
+
 }  // extern "C"

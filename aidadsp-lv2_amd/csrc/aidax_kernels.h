@@ -218,6 +218,34 @@ static_assert(sizeof(GateRec) == 32 && sizeof(GateState) == 8, "a stream's gate 
 hipError_t launch_gate(const float* in, float* out, const GateRec* rec, GateState* state, const StreamCtl* ctl, uint32_t n_active, uint32_t n_frames,
                        hipStream_t q);
 
+// The stream tuners ahead of the model (aidax_tune.hip, k_tune): one launch, a workgroup per stream of the pass, appends the rows of the
+// block the pass was handed, [n_active][n_frames], to the tuned streams' history rings (per stream a row of mask + 1 floats, frame p of
+// the tuner's count in slot p & mask; mask + 1 >= window + the longest pass) and moves their frame counts; `analyse` also runs the
+// analysis of include/aidax.h ("Stream tuners") for every stream whose count crosses a hop boundary (the device decides per stream from
+// its own count: the host's mirror, TunerBook, only tells whether any stream of the pass can). TunerReading is aidax_tuner_reading,
+// field for field. A stream whose `on` word is 0 is not touched.
+constexpr uint32_t kTuneMaxTiles = 9;          // lag tiles of 256: tmax + 1 <= 2048
+struct TunerReading {
+    uint64_t frame;
+    uint32_t analyses, lag;
+    float hz, period, clarity, level;
+};
+static_assert(sizeof(TunerReading) == 32, "a stream's tuner reading is 32 bytes");
+struct TuneArgs {
+    const float* in;             // [n_active][n_frames]: only read
+    float* ring;                 // [n_streams][mask + 1]
+    uint64_t* pos;               // [n_streams]
+    const uint32_t* on;          // [n_streams]
+    TunerReading* reading;       // [n_streams]
+    float* curve;                // [n_streams][curve_row]: the NSDF rows, lags 0 .. tmax + 1
+    double samplerate;
+    uint32_t n_active, n_frames, mask, curve_row;
+    uint32_t window, hop, tmin, tmax;
+    float threshold, clarity_min, level_min;
+};
+size_t tune_lds_bytes(uint32_t window, uint32_t tmax);
+hipError_t launch_tune(const TuneArgs& a, bool analyse, hipStream_t q);
+
 // The mix buses behind a pool's last stage (aidax_mix.hip, k_mix): one launch gathers the rows of the block a pass returns, [n_streams]
 // [n_frames], into the pool's bus block, [n_buses][n_frames], by the rule of include/aidax.h ("Mix buses"). The plan is CSR: the entries
 // of bus b are entries[bus_start[b] .. bus_start[b + 1] - 1], in ascending (stream, send) order; frame t of the pass is ramp frame

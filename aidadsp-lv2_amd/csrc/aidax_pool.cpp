@@ -1,6 +1,6 @@
 // aidax_pool.cpp — the core of the stream pool behind the C ABI (aidax_pool.h): which models have a device path, the process launches, device
 // residency, control latching and the streams' state, around the cabinet IR stage (aidax_ir_stage.h), the model bank (aidax_model_bank.h)
-// and the gate and meters (aidax_stream_stages.h). Models and IRs on their way in: aidax_pool_model.cpp; host buffers: aidax_pool_io.cpp.
+// and the gate, meters and tuners (aidax_stream_stages.h). Models and IRs on their way in: aidax_pool_model.cpp; host buffers: aidax_pool_io.cpp.
 // Host logic only; the kernels are in aidax_kernels.hip. No CPU fallback: any HIP failure is AIDAX_ERR_DEVICE.
 #include <hip/hip_runtime_api.h>
 
@@ -225,6 +225,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         if (ir_on || meter_on || mix_on) end = nullptr;                // (the markers are not handed down: nullptr to launch)
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) p->meter.launch_in(d_in, n_active, n_frames, s);  // (ahead of the pass: it may work in place)
+        p->tuner.before_pass(d_in, n_active, n_frames, s);            // the tuners read the same block: the DI signal, ahead of the gate
         a.in = p->gate.before_pass(d_in, p->d_ctl.get(), n_active, n_frames, s);      // the gated block, where a gate is on
         HIP_TRY(p->launch(p->cur, a, s, end, form));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
@@ -430,6 +431,76 @@ AIDAX_API int aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count
     if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
     if (!p->gate.enabled()) return fail(AIDAX_ERR_STATE, "no gate was ever enabled (aidax_pool_set_gate)");
     return p->on_own_stream([&]() -> int { p->gate.read(first, count, out, p->q); return AIDAX_OK; });
+}
+
+// The stream tuners (aidax_stream_stages.h: TunerStage). The first aidax_pool_set_tuning with parameters is the set-up side's (it
+// allocates and fixes the design); everything else changes or reads host records of the audio side, and the reads wait like
+// aidax_pool_read_meters. A stream whose tuner goes from off to on has its count, reading and curve zeroed on the pool's own stream.
+AIDAX_API int aidax_pool_set_tuning(aidax_pool* p, const aidax_tuner_params* params)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    TunerStage& t = p->tuner;
+    if (!params) { t.on = false; return AIDAX_OK; }
+    aidax_tuner_rec designed{};
+    if (const int rc = aidax_tuner_design(aidax_pool_samplerate(p), params, &designed)) return rc;
+    if (t.enabled()) {
+        if (std::memcmp(&designed, &t.book.rec, sizeof designed) != 0) return fail(AIDAX_ERR_STATE, "the pool's tuner design is fixed once set");
+        t.on = true;
+        return AIDAX_OK;
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        t.enable(p->n_streams, p->max_frames, designed, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_tuning(const aidax_pool* p, aidax_tuner_rec* out)
+{
+    if (out) *out = p && p->tuner.enabled() ? p->tuner.book.rec : aidax_tuner_rec{};
+    return p && p->tuner.on ? 1 : 0;
+}
+
+AIDAX_API int aidax_pool_set_tuner(aidax_pool* p, int32_t stream, int on)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    uint32_t lo = 0, hi = 0;
+    if (!named_range(stream, p->n_streams, &lo, &hi)) return fail(AIDAX_ERR_ARG, "stream out of range");
+    TunerStage& t = p->tuner;
+    if (!t.enabled()) return fail(AIDAX_ERR_STATE, "the tuners were never set up (aidax_pool_set_tuning)");
+    const auto& restart = t.book.apply(lo, hi, on != 0);
+    if (restart.empty()) return AIDAX_OK;
+    return p->on_own_stream([&]() -> int {
+        for (const TunerBook::Run& r : restart) t.clear_streams(r.first, r.second - r.first, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_stream_tuner(const aidax_pool* p, uint32_t stream, int* on, uint64_t* pos)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const TunerStage& t = p->tuner;
+    if (on) *on = t.enabled() && t.book.h_on[stream] ? 1 : 0;
+    if (pos) *pos = t.enabled() ? t.book.pos[stream] : 0u;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_read_tuners(aidax_pool* p, uint32_t first, uint32_t count, aidax_tuner_reading* out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
+    if (!p->tuner.enabled()) return fail(AIDAX_ERR_STATE, "the tuners were never set up (aidax_pool_set_tuning)");
+    return p->on_own_stream([&]() -> int { p->tuner.read(first, count, out, p->q); return AIDAX_OK; });
+}
+
+AIDAX_API int aidax_pool_read_tuner_curve(aidax_pool* p, uint32_t stream, float* out, uint32_t count)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    if (!p->tuner.enabled()) return fail(AIDAX_ERR_STATE, "the tuners were never set up (aidax_pool_set_tuning)");
+    if (count == 0 || count > p->tuner.curve_row) return fail(AIDAX_ERR_ARG, "the curve has lags 0 .. tmax + 1");
+    return p->on_own_stream([&]() -> int { p->tuner.read_curve(stream, out, count, p->q); return AIDAX_OK; });
 }
 
 // The mix buses (aidax_mix_stage.h). The first aidax_pool_set_buses with a count is the set-up side's (it allocates); everything else
@@ -693,6 +764,7 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
         HIP_TRY(launch_init_streams(p->d_st.get() + stream, 1, p->q));      // instantiate(), :283-321
         p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
         p->gate.clear_states(stream, 1, p->q);                         // ... and its gate starts at unity gain, hold expired
+        if (p->tuner.enabled()) { p->tuner.book.restart(stream); p->tuner.clear_streams(stream, 1, p->q); }      // ... and its tuner has heard nothing
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st.get() + stream, p_targets[0], p_targets[1], p->q));
         const ModelBank* b = p->bank.adopt();                         // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
         if (m.has_model) p->fresh_stream_model(m, stream, start_mode, b && b->assign[stream] >= 0 ? ModelBank::rec_of(b->slot[b->assign[stream]]) : m.rec(), p->q);

@@ -209,6 +209,7 @@ struct aidax_pool {
     bool any_pass = false;           // the pool has issued a pass of n_frames > 0 (its first one has nothing for an IR change to fade from)
     MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
     GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
+    TunerStage tuner;                // the stream tuners ahead of the model (nothing until the first aidax_pool_set_tuning with parameters)
     MixStage mix;                    // the mix buses behind the last stage (aidax_mix_stage.h; nothing until the first aidax_pool_set_buses with a count)
     ReverbStage reverb;              // the bus reverbs between k_mix and k_bus_limit (aidax_reverb_stage.h; nothing until the first aidax_pool_set_bus_reverbs(1, ..))
     LimitStage limit;                // the bus limiters and bus meters behind k_mix (aidax_limit_stage.h; nothing until the first aidax_pool_set_bus_limiting(1, ..))

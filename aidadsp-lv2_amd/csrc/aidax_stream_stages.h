@@ -1,6 +1,7 @@
-// aidax_stream_stages.h — the two per-stream stages around a pool's pass (include/aidax.h, "Noise gate" and "Stream meters"): the gate
-// ahead of the model (k_gate) and the meters on both sides of it (k_meter). GateBook is the gate's host-only half (no HIP call: which
-// gates are on, their records, what the device has not seen), GateStage and MeterStage the device halves. Issues HIP calls: include it last.
+// aidax_stream_stages.h — the per-stream stages around a pool's pass (include/aidax.h, "Noise gate", "Stream meters" and "Stream
+// tuners"): the gate ahead of the model (k_gate), the meters on both sides of it (k_meter) and the tuners ahead of it (k_tune). GateBook
+// is the gate's host-only half (no HIP call: which gates are on, their records, what the device has not seen) and TunerBook
+// (aidax_tuner_book.h) the tuners'; GateStage, MeterStage and TunerStage are the device halves. Issues HIP calls: include it last.
 #pragma once
 
 #include <cstddef>
@@ -8,6 +9,7 @@
 #include <vector>
 
 #include "aidax_snapshot_ring.h"
+#include "aidax_tuner_book.h"
 
 namespace aidax {
 
@@ -119,6 +121,89 @@ struct MeterStage {
     {
         const size_t bytes = sizeof(MeterRec) * count;
         read_back(out, h_rec.get() + first, d_rec.get() + first, bytes, q, [&] { if (clear) HIP_TRY(hipMemsetAsync(d_rec.get() + first, 0, bytes, q)); });
+    }
+};
+
+// The stream tuners: nothing until enable(), the set-up side's first aidax_pool_set_tuning with parameters; from then on `on` and the
+// book's records are the audio side's. A tuned pass is k_tune over the block it was handed, ahead of the model's launch.
+static_assert(sizeof(aidax_tuner_reading) == sizeof(TunerReading) && offsetof(aidax_tuner_reading, analyses) == offsetof(TunerReading, analyses) &&
+                  offsetof(aidax_tuner_reading, hz) == offsetof(TunerReading, hz) && offsetof(aidax_tuner_reading, level) == offsetof(TunerReading, level),
+              "k_tune's reading is aidax_tuner_reading");
+struct TunerStage {
+    TunerBook book;
+    DevBuf<float> d_ring;            // [n_streams][ring_row], empty: never enabled
+    DevBuf<uint64_t> d_pos;          // [n_streams]
+    DevBuf<uint32_t> d_on;           // [n_streams]
+    DevBuf<TunerReading> d_reading;  // [n_streams]
+    DevBuf<float> d_curve;           // [n_streams][curve_row]
+    PinnedBuf<TunerReading> h_reading;   // pinned staging of read(), [n_streams]
+    PinnedBuf<float> h_curve;        // ... and of read_curve(), [curve_row]
+    SnapshotRing ring;
+    uint32_t ring_row = 0, curve_row = 0;
+    bool on = false;
+
+    bool enabled() const { return static_cast<bool>(d_ring); }
+    // rings, counts, `on` words, readings and curves (all zeroed), the snapshots and the pinned staging; switches the stage on; all or nothing
+    void enable(uint32_t n_streams, uint32_t max_frames, const aidax_tuner_rec& designed, hipStream_t q)
+    {
+        const size_t n = n_streams;
+        TunerStage fresh;
+        fresh.ring_row = pow2_at_least(designed.window + max_frames);
+        fresh.curve_row = designed.tmax + 2u;
+        fresh.d_ring.alloc(n * fresh.ring_row);
+        fresh.d_pos.alloc(n);
+        fresh.d_on.alloc(n);
+        fresh.d_reading.alloc(n);
+        fresh.d_curve.alloc(n * fresh.curve_row);
+        fresh.h_reading.alloc(n);
+        fresh.h_curve.alloc(fresh.curve_row);
+        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * n * fresh.ring_row, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_pos.get(), 0, sizeof(uint64_t) * n, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_on.get(), 0, sizeof(uint32_t) * n, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_reading.get(), 0, sizeof(TunerReading) * n, q));
+        HIP_TRY(hipMemsetAsync(fresh.d_curve.get(), 0, sizeof(float) * n * fresh.curve_row, q));
+        HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
+        fresh.ring.alloc(sizeof(uint32_t) * n);
+        fresh.book.init(n_streams, designed);
+        fresh.on = true;
+        *this = std::move(fresh);
+    }
+    // a restart's device half, on the pool's own stream behind the passes issued so far: count, reading and curve (the ring needs no
+    // clear: a window never reaches behind the restart, rule 1 asks for b >= window)
+    void clear_streams(uint32_t first, uint32_t count, hipStream_t q)
+    {
+        if (!d_ring) return;
+        HIP_TRY(hipMemsetAsync(d_pos.get() + first, 0, sizeof(uint64_t) * count, q));
+        HIP_TRY(hipMemsetAsync(d_reading.get() + first, 0, sizeof(TunerReading) * count, q));
+        HIP_TRY(hipMemsetAsync(d_curve.get() + static_cast<size_t>(first) * curve_row, 0, sizeof(float) * count * curve_row, q));
+    }
+    // Ahead of the model's launch of a pass: the `on` words it plays under, then k_tune over the block it was handed
+    void before_pass(const float* d_in, uint32_t n_active, uint32_t n_frames, hipStream_t s)
+    {
+        if (!on || n_frames == 0 || book.n_on == 0) return;
+        if (book.dirty()) {
+            const size_t off = sizeof(uint32_t) * book.dirty_lo, bytes = sizeof(uint32_t) * (static_cast<size_t>(book.dirty_hi - book.dirty_lo) + 1);
+            std::memcpy(ring.take() + off, book.h_on.data() + book.dirty_lo, bytes);
+            ring.send(d_on.get(), off, bytes, s);
+            book.flushed();
+        }
+        const bool analyse = book.advance(n_active, n_frames);
+        const aidax_tuner_rec& r = book.rec;
+        TuneArgs a{};
+        a.in = d_in; a.ring = d_ring.get(); a.pos = d_pos.get(); a.on = d_on.get(); a.reading = d_reading.get(); a.curve = d_curve.get();
+        a.samplerate = r.samplerate;
+        a.n_active = n_active; a.n_frames = n_frames; a.mask = ring_row - 1u; a.curve_row = curve_row;
+        a.window = r.window; a.hop = r.hop; a.tmin = r.tmin; a.tmax = r.tmax;
+        a.threshold = r.threshold; a.clarity_min = r.clarity_min; a.level_min = r.level_min;
+        HIP_TRY(launch_tune(a, analyse, s));
+    }
+    void read(uint32_t first, uint32_t count, aidax_tuner_reading* out, hipStream_t q)      // waits
+    {
+        read_back(out, h_reading.get() + first, d_reading.get() + first, sizeof(TunerReading) * count, q);
+    }
+    void read_curve(uint32_t stream, float* out, uint32_t count, hipStream_t q)             // waits
+    {
+        read_back(out, h_curve.get(), d_curve.get() + static_cast<size_t>(stream) * curve_row, sizeof(float) * count, q);
     }
 };
 

@@ -605,6 +605,91 @@ AIDAX_API int  aidax_pool_set_gate(aidax_pool* p, int32_t stream, const aidax_ga
 AIDAX_API int  aidax_pool_stream_gate(const aidax_pool* p, uint32_t stream, aidax_gate_params* out, int* on);
 AIDAX_API int  aidax_pool_read_gate(aidax_pool* p, uint32_t first, uint32_t count, aidax_gate_state* out);
 
+/* Stream tuners: a monophonic pitch tracker per stream, computed where the blocks are (k_tune, aidax_tune.hip): the McLeod pitch method,
+ * a normalised autocorrelation over a window of W frames, with the autocorrelation on the matrix cores. Opt-in: a pool that never calls
+ * aidax_pool_set_tuning, or has the stage off, allocates and launches exactly what it did before these calls existed, bit for bit, and
+ * the tuners only read the block a pass was handed: a tuned pool's audio is bit-identical to an untuned pool's.
+ * While the stage is on and at least one stream's tuner is on, every pass of n_frames > 0 issues one launch of k_tune on the pass's
+ * stream, ahead of the model's launch (next to the meters' input side: the pass may work in place). It reads rows < n_active of the block
+ * the pass was HANDED — the DI signal: ungated, whatever the stream's `enabled` control says — appends each tuned stream's row to that
+ * stream's history ring, and analyses the streams that cross a hop boundary.
+ * The rule, normative (tests/tunehelp.py restates it in numpy). A stream's tuner has a frame count `pos`: the frames of the blocks the
+ * stream was handed since its tuner went on or was restarted. With the design's window W, hop H, lags tmin .. tmax, threshold k:
+ *  1. A pass that takes pos from p0 to p1 analyses the stream if and only if b = floor(p1 / H) * H > p0 and b >= W. The window x[0 .. W)
+ *     is the W frames that end at frame b (exclusive), oldest first: not "the last W frames of the block". A stream's readings do not
+ *     depend on how the host cuts its blocks; a pass that crosses several boundaries analyses the last one only.
+ *  2. r[t] = sum_{j = 0}^{W - 1 - t} x[j] x[j + t] for t = 0 .. tmax + 1 (zeros outside the window). Computed as bf16 term products
+ *     accumulated in fp32 (both operands split exactly into three bf16 terms, six of the nine products kept, the partial sums of the
+ *     four waves added in a fixed order): within 2^-23 sum |x[j] x[j + t]| plus the accumulation's rounding of the exact sum, and EXACT
+ *     where every product and partial sum is an fp32 number (small integers times a power of two).
+ *  3. With c the prefix sums of x^2 in fp64 (c[0] = 0, summation order unspecified): m[t] = c[W - t] + (c[W] - c[t]).
+ *  4. The NSDF: n[t] = (float)((2.0 * (double)r[t]) / m[t]), or 0.0f where m[t] <= 0.
+ *  5. Key maxima, over the lags 1 .. tmax + 1 (lag tmax + 2 counts as not positive). Skip the lobe around lag 0: lags 1, 2, .. while
+ *     n > 0. From there on every maximal run of lags with n > 0 is a lobe; its candidates are the lags t with tmin <= t <= tmax,
+ *     n[t] >= n[t - 1] and n[t] > n[t + 1]; its key maximum is the candidate of largest n, the earliest on a tie; a lobe without a
+ *     candidate has none. (A NaN compares false: not positive, no candidate.)
+ *  6. With nmax the largest key maximum, the chosen lag q is the first key maximum with n[q] >= k * nmax (fp32, one rounded product).
+ *  7. In fp64 from the fp32 values a = n[q - 1], b = n[q], c = n[q + 1], every operation rounded on its own: den = (a - 2 b) + c;
+ *     d = den < 0 ? (0.5 (a - c)) / den : 0; period = q + d; clarity = b - (0.25 (a - c)) d; hz = samplerate / period. Each of the
+ *     three is rounded once to fp32.
+ *  8. level = (float)sqrt(c[W] / W). The reading is UNVOICED when there is no key maximum (clarity is then 0), when clarity <
+ *     clarity_min or when level < the level floor: hz = 0, period = 0, lag = 0; clarity and level are still reported.
+ * The reading of the last analysis stays until the next one; `analyses` counts them since the restart, `frame` is the last one's b.
+ * A row of silence or of NaN gives an unvoiced reading (level 0, or NaN) and touches nothing but the stream's own tuner.
+ * aidax_tuner_design       pure, host only, any thread: the record of `params` at `samplerate`: tmin = floor(samplerate / f_max),
+ *                          tmax = ceil(samplerate / f_min), level_min = (float)pow(10, level_min_db / 20) (0 for <= -200 dB).
+ *                          AIDAX_ERR_ARG (the reason in aidax_last_error()) for a null pointer, a window other than 1024, 2048 or 4096,
+ *                          a hop that is no multiple of 16 or outside 64 .. 65536, a non-finite field, f_min or f_max not positive,
+ *                          f_min > f_max, tmin < 2, tmax > window / 2 - 1, a threshold outside (0, 1], a clarity_min outside [0, 1],
+ *                          level_min_db > 0, a samplerate that is not positive.
+ * aidax_tuner_params_default   window 2048, hop 1024, 70 .. 1400 Hz, threshold 0.93, clarity_min 0.5, level_min_db -60.
+ * aidax_tuner_note         pure: the nearest equal-tempered MIDI note of `hz` for A4 = a4_hz (note 69) and the deviation in cents,
+ *                          n = 69 + 12 log2(hz / a4_hz) in fp64, midi_note = the integer nearest n, cents = (float)(100 (n - midi_note)).
+ *                          AIDAX_ERR_ARG for a null pointer or a frequency that is not positive and finite.
+ * aidax_pool_set_tuning    the FIRST call with params != NULL is a SET-UP side call, like the first aidax_pool_set_metering(.., 1): it
+ *                          fixes the design at aidax_pool_samplerate for the pool's life and allocates, per stream, a history ring (R
+ *                          floats, R the power of two >= window + max_frames), the frame count, the reading, the NSDF row (tmax + 2
+ *                          floats) and the snapshots and pinned staging; it switches the stage on, every stream's tuner off, and may
+ *                          wait. A later call with params != NULL must name the same design (AIDAX_ERR_STATE otherwise) and switches
+ *                          the stage on; params == NULL switches it off (the tuners' counts do not move while it is off). Both are
+ *                          AUDIO side host records. AIDAX_ERR_ARG for a null pool and whatever aidax_tuner_design refuses.
+ * aidax_pool_tuning        the design (zeros if never set); returns 1 while the stage is on, else 0.
+ * aidax_pool_set_tuner     AUDIO side host record: the tuner of `stream` (AIDAX_ALL_STREAMS: every stream) on or off, from the next
+ *                          pass on. Off -> on restarts it: pos = 0, an empty history, reading and NSDF row zeroed, on the pool's own
+ *                          stream behind the passes issued so far; aidax_pool_reset_stream does the same. A stream whose tuner is
+ *                          off keeps the reading it has (zeros if it was never on). AIDAX_ERR_STATE before aidax_pool_set_tuning.
+ * aidax_pool_stream_tuner  whether the stream's tuner is on, and its frame count as the host mirrors it.
+ * aidax_pool_read_tuners   AUDIO side, and it waits, like aidax_pool_read_meters: the readings of `count` streams from `first`, behind
+ *                          every pass issued so far. AIDAX_ERR_ARG for a null argument, count == 0 or first + count > n_streams,
+ *                          AIDAX_ERR_STATE before aidax_pool_set_tuning.
+ * aidax_pool_read_tuner_curve  the same for the NSDF row of the stream's last analysis, lags 0 .. count - 1, count <= tmax + 2: what
+ *                          a tuner display draws.
+ * Not covered: hub seats (aidax_hub never enables the stage on its pool) and so the LV2 shell, polyphonic pitch, a tuner behind the
+ * model, a window or range per stream. */
+typedef struct { uint32_t window, hop; float f_min, f_max, threshold, clarity_min, level_min_db; } aidax_tuner_params;
+typedef struct {
+    uint32_t window, hop, tmin, tmax;      /* W, H, the lag range                                             */
+    float    threshold, clarity_min;       /* k, the clarity floor                                            */
+    float    level_min, reserved;          /* the level floor, linear                                         */
+    double   samplerate;
+} aidax_tuner_rec;                         /* 40 bytes */
+typedef struct {
+    uint64_t frame;            /* b of the last analysis: the window is frames b - W .. b - 1 of the stream's count */
+    uint32_t analyses;         /* analyses since the restart                                          */
+    uint32_t lag;              /* the chosen lag q, 0: unvoiced                                       */
+    float    hz, period;       /* samplerate / period; q + the parabola's offset, in frames; 0: unvoiced */
+    float    clarity, level;   /* the interpolated NSDF peak; the window's RMS                        */
+} aidax_tuner_reading;         /* 32 bytes, no padding */
+AIDAX_API void aidax_tuner_params_default(aidax_tuner_params* params);
+AIDAX_API int  aidax_tuner_design(double samplerate, const aidax_tuner_params* params, aidax_tuner_rec* out);
+AIDAX_API int  aidax_tuner_note(double hz, double a4_hz, int32_t* midi_note, float* cents);
+AIDAX_API int  aidax_pool_set_tuning(aidax_pool* p, const aidax_tuner_params* params);
+AIDAX_API int  aidax_pool_tuning(const aidax_pool* p, aidax_tuner_rec* out);
+AIDAX_API int  aidax_pool_set_tuner(aidax_pool* p, int32_t stream, int on);
+AIDAX_API int  aidax_pool_stream_tuner(const aidax_pool* p, uint32_t stream, int* on, uint64_t* pos);
+AIDAX_API int  aidax_pool_read_tuners(aidax_pool* p, uint32_t first, uint32_t count, aidax_tuner_reading* out);
+AIDAX_API int  aidax_pool_read_tuner_curve(aidax_pool* p, uint32_t stream, float* out, uint32_t count);
+
 /* Mix buses: the streams of a pool summed into output buses where the blocks are (k_mix, aidax_mix.hip): two amps of one player, a
  * stereo pair from two cabinets, monitor mixes, the rooms of a service. Opt-in: a pool that never calls aidax_pool_set_buses, or has
  * its buses off, allocates and launches exactly what it did before these calls existed, bit for bit, and the buses only read the
