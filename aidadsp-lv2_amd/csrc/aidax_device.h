@@ -233,7 +233,6 @@ __device__ __forceinline__ float tanh_rat(float v)
 {
     const float x = kMed3 ? __builtin_amdgcn_fmed3f(v, -kTanhClamp, kTanhClamp) : tanh_rat_clamp(v);
     const float u = x * x;
-#ifndef AIDAX_TANH_PLAIN
     // The first three Horner steps of P and all three of Q side by side in v_pk_fma_f32 ({p, q} <- {p, q} * {u, u} + {cP, cQ}: the same FMAs on the same
     // operands, so the same bits), the last three of P alone: six instructions for nine. A lone wave issues a packed FMA in a plain one's interval
     // (profiles/r05_lone_wave_issue.txt), and the recurrent wave's frame is its instruction count (profiles/r05_cfg2_frame_trace.txt): two rationals per frame.
@@ -249,19 +248,7 @@ __device__ __forceinline__ float tanh_rat(float v)
     pp = __builtin_fmaf(pp, u, kTanhP[1]);
     pp = __builtin_fmaf(pp, u, kTanhP[0]);
     return (pp * x) * __builtin_amdgcn_rcpf(pq.y);
-#endif
-    float p = kTanhP[6];
-    p = __builtin_fmaf(p, u, kTanhP[5]);
-    p = __builtin_fmaf(p, u, kTanhP[4]);
-    p = __builtin_fmaf(p, u, kTanhP[3]);
-    p = __builtin_fmaf(p, u, kTanhP[2]);
-    p = __builtin_fmaf(p, u, kTanhP[1]);
-    p = __builtin_fmaf(p, u, kTanhP[0]);
-    float q = kTanhQ[3];
-    q = __builtin_fmaf(q, u, kTanhQ[2]);
-    q = __builtin_fmaf(q, u, kTanhQ[1]);
-    q = __builtin_fmaf(q, u, kTanhQ[0]);
-    return (p * x) * __builtin_amdgcn_rcpf(q);
+    // (The two plain Horner chains this replaced, nine FMAs: cfg2 64.87 against 64.08 us, profiles/r05_cfg2_ledger.txt.)
 }
 
 // tanh for FEED-FORWARD layers (the conv1d stacks): 1 - 2 / (1 + e^(2x)) on v_exp_f32 / v_rcp_f32, five instructions
@@ -409,10 +396,7 @@ __device__ __forceinline__ void chain_sweep(ChainPass& c, int stage, bool run, i
 // (`hand`: [2][64 lanes][kChainBlock] floats). Same operations in the same order per sample and per stage as
 // chain_step, so the results are bit-identical. `row` is processed in place; n_full is a multiple of
 // kChainBlock (the caller finishes a ragged tail with chain_sweep).
-#ifndef AIDAX_CHAIN_BLOCK
-#define AIDAX_CHAIN_BLOCK 8
-#endif
-constexpr int kChainBlock = AIDAX_CHAIN_BLOCK;
+constexpr int kChainBlock = 8;     // (no measurement of another default is recorded; callers that gain from more pass their own B below)
 
 // PLAIN: every lane that runs has its biquad in circuit and every gain ramp of the wave sits on its fixed point
 // (mem * coef + tc == mem, so next() returns the same value for the rest of the block): the per-sample select

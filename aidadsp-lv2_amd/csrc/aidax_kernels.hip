@@ -309,11 +309,8 @@ struct LstmCell {
             }
             const float cn = __builtin_fmaf(gf, c[m], gi_gg);
             c[m] = cn;
-#ifdef AIDAX_TANHC_EXP
-            const float th = tanh_exp(cn);                  // experiment: the exp form for tanh(c) only (scratch/ab_tanhc.sh)
-#else
+            // (tanh_exp here, five instructions: british_lead's drift 8.8e-6 -> 1.16e-5, over the reference's 1e-5 — profiles/r05_cfg2_ledger.txt)
             const float th = tanh_rat<ROT>(cn);
-#endif
             if constexpr (PAIRS) {
                 h[m] = mul_share_halves_hi(go, th);         // hn = go * tanh(c') twice from one instruction, then the swap
             } else {
@@ -896,26 +893,9 @@ __device__ __forceinline__ void stream_body_pipe(const LaunchArgs& a, float* sme
                         else cell.template step<1>(xr[t], 0.f, 0.f, t == 0 ? hprev : hcur + (t - 1) * HS, hcur + t * HS);
                         if (t == 9) cell.ts6 = __builtin_amdgcn_s_memtime();      // the frame after the traced one has been issued
                     }
-#elif defined(AIDAX_PIPE_ROLL)
-                    // (measurement build, scratch/r06_pipe_roll.sh: the stage as a LOOP of AIDAX_PIPE_ROLL frames per iteration instead of
-                    // sixteen unrolled — 11 KB of straight-line code per stage against 0.7 KB per frame: does instruction fetch bound a lone wave?)
-                    {
-                        const float* hp = hprev;
-                        float* hc = hcur;
-#pragma unroll 1
-                        for (int t0 = 0; t0 < kSB; t0 += AIDAX_PIPE_ROLL) {
-                            float xs[AIDAX_PIPE_ROLL];
-#pragma unroll
-                            for (int i = 0; i < AIDAX_PIPE_ROLL; ++i) xs[i] = stage[t0 + i] * in_gain;
-#pragma unroll
-                            for (int i = 0; i < AIDAX_PIPE_ROLL; ++i) {
-                                cell.template step<1>(xs[i], 0.f, 0.f, hp, hc);
-                                hp = hc;
-                                hc += HS;
-                            }
-                        }
-                    }
 #else
+                    // (round 6, measured and not kept: the stage as a loop of 8, 4, 2 or 1 frames per iteration instead of sixteen unrolled —
+                    // less code is slower at every size, 64.8 .. 74.9 against 63.5 us: profiles/r06_cfg2_pipe4.txt, addendum 3)
 #pragma unroll
                     for (int t = 0; t < kSB; ++t)
                         cell.template step<1>(xr[t], 0.f, 0.f, t == 0 ? hprev : hcur + (t - 1) * HS, hcur + t * HS);
@@ -1159,6 +1139,8 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     // together run the same instructions in lockstep for the whole tile, and whether their LDS accesses and instruction fetches then
     // collide is decided by a few cycles of phase: the same kernel measured 61.4 .. 66.8 us over seven builds that differed by
     // 4 .. 64 bytes of padding (profiles/r06_cfg2_pipe4.txt). Left to themselves the waves drift apart and stay apart.
+    // (That first form — one workgroup barrier per tick — with the phase between the waves as a run-time delay: 63.0 .. 67.3 us by phase
+    // alone, never the lucky build's 61.4; addendum 2 of the same file. It was given up for this one.)
     int* prog = reinterpret_cast<int*>(wdl + H + 4);      // [0] tiles the helpers have made ready (pre pass done, times in_gain)
                                                           // [1] tiles whose Dense is done (their rows of the h ring are free)
                                                           // [2 + j] tiles the cell of stream j has finished
@@ -1168,12 +1150,9 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     const int I = kCond ? (int)a.input_size : 1;
 
     // every wave derives the launch's timing from the four control words (wave-uniform): the longest cascades set it
-    // (the post side's length is the helper's alone in the free-running form — it knows only behind its loads whether a stream's post EQ is
-    // transparent, see there; the barrier form, where every wave counts the ticks, keeps the control words' answer and never skips)
+    // (the post side's length, and with it the number of ticks, is the helper's alone — it knows only behind its loads whether a stream's
+    // post EQ is transparent, see there)
     int Kp = 1;
-#ifdef AIDAX_P4_BARRIER
-    int Kq = 1;
-#endif
     uint32_t fw[kP4Streams];                              // the four control words' flags (scalar loads: registers of the scalar file)
 #pragma unroll
     for (int j = 0; j < kP4Streams; ++j) {
@@ -1184,14 +1163,8 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         const uint32_t f = a.ctl[jc].flags;
         fw[j] = s0 + j < (int)a.n_streams ? f : 0u;
         if ((f & CTL_EQ_PRE) && s0 + j < (int)a.n_streams) Kp = 6;
-#ifdef AIDAX_P4_BARRIER
-        if ((f & CTL_EQ_POST) && s0 + j < (int)a.n_streams) Kq = 6;
-#endif
     }
     const int d1 = Kp / 2 + 1;                            // ticks between a tile entering the pre pass and the cell reading it
-#ifdef AIDAX_P4_BARRIER
-    const int T = (n / B - 1 + (Kq - 1) + 2 * (d1 + 1)) / 2 + 1;
-#endif
 
     if (wave < kP4Streams) {
         // ---------------------------------------------------------------- a recurrent wave
@@ -1216,18 +1189,7 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         cell.publish_h(hj + (kRing - 1) * HS);            // h(-1): the row "before" frame 0 (unconditionally: a stream out of circuit publishes into its own ring for nothing)
         __syncthreads();                                  // (the progress words are zero)
         P4_STAMP(2);
-#ifndef AIDAX_P4_BARRIER
         if (!net) { p4_post(prog + 2 + wave, NT, lane); return; }
-#endif
-#ifdef AIDAX_P4_BARRIER
-        // (measurement build, scratch/r06_p4_phase.sh: the first form — one workgroup barrier per tick, the waves in lockstep — with the
-        // phase between the waves as a RUN-TIME parameter: bits 20 .. 23 of AIDAX_TUNE = sixteen-cycle steps the helper waits behind every
-        // barrier, bits 24 .. 25 = steps recurrent wave j waits, times j. Same code for every setting: what changes is phase alone.)
-        for (int tick = 0; tick < T; ++tick) {
-            const int t = tick - d1;
-            for (int i = 0; i < wave * ((AIDAX_TUNE(a) >> 24) & 3); ++i) asm volatile("s_nop 15");
-            if (t >= 0 && t < NT) {
-#else
         // (test build: bits 24 .. 27 of AIDAX_TUNE = sixteen-cycle steps recurrent wave j waits ONCE, times j, before its first tile — nothing
         // brings free-running waves back into step)
         for (int i = 0; i < wave * ((AIDAX_TUNE(a) >> 24) & 15); ++i) asm volatile("s_nop 15");
@@ -1251,64 +1213,53 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
                 __builtin_amdgcn_sched_barrier(0);
             }
 #endif
-            {
-#endif
-                const int base = t * kSB;
-                const float* hprev = hj + ((base + kRing - 1) & (kRing - 1)) * HS;
-                float* hcur = hj + (base & (kRing - 1)) * HS;
-                const float* xs = row + base;             // x * in_gain (the helper's product, in place)
-                float xr[kSB];
-                asm volatile(".p2align 6");
-                auto fetch_x = [&](int q) {
-                    const float4 v = reinterpret_cast<const float4*>(xs)[q];
-                    xr[4 * q] = v.x; xr[4 * q + 1] = v.y;
-                    xr[4 * q + 2] = v.z; xr[4 * q + 3] = v.w;
+            const int base = t * kSB;
+            const float* hprev = hj + ((base + kRing - 1) & (kRing - 1)) * HS;
+            float* hcur = hj + (base & (kRing - 1)) * HS;
+            const float* xs = row + base;             // x * in_gain (the helper's product, in place)
+            float xr[kSB];
+            asm volatile(".p2align 6");
+            auto fetch_x = [&](int q) {
+                const float4 v = reinterpret_cast<const float4*>(xs)[q];
+                xr[4 * q] = v.x; xr[4 * q + 1] = v.y;
+                xr[4 * q + 2] = v.z; xr[4 * q + 3] = v.w;
+            };
+            fetch_x(0);
+            if constexpr (!kCond) {
+                typedef float f32x2 __attribute__((ext_vector_type(2)));
+                if constexpr (Cell::kPairs) cell.template input_pair<0>(f32x2{ xr[0], xr[1] });
+#pragma unroll
+                for (int f = 0; f < kSB; ++f) {
+                    if ((f & 3) == 1 && f / 4 + 1 < kSB / 4) fetch_x(f / 4 + 1);
+                    if (f == kSB - 4) ahead = *(const volatile p4_lds_i2*)(const p4_lds_i2*)(prog);
+                    if constexpr (Cell::kPairs) {
+                        // (the paired LSTM-32 frame issues the NEXT frame's input pair itself, see LstmCell::step)
+                        if (f + 1 < kSB && (f & 1)) cell.template step<1, 0, false, true, 0>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f + 1], xr[(f + 2) % kSB] });
+                        else if (f + 1 < kSB) cell.template step<1, 0, false, true, 1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f], xr[f + 1] });
+                        else cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
+                    } else
+                    cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
+                }
+            } else {
+                // conditioned models (input_size 2 / 3, :186-233): PARAM1 / PARAM2 of every frame are the helper's (LinearValueSmoother per sample)
+                const float* p1s = prow + (wave * 2 + 0) * n + base;
+                const float* p2s = prow + (wave * 2 + 1) * n + base;
+                float p1r[kSB], p2r[kSB];
+                auto fetch_p = [&](int q) {
+                    const float4 u = reinterpret_cast<const float4*>(p1s)[q];
+                    const float4 w = reinterpret_cast<const float4*>(p2s)[q];
+                    p1r[4 * q] = u.x; p1r[4 * q + 1] = u.y; p1r[4 * q + 2] = u.z; p1r[4 * q + 3] = u.w;
+                    p2r[4 * q] = w.x; p2r[4 * q + 1] = w.y; p2r[4 * q + 2] = w.z; p2r[4 * q + 3] = w.w;
                 };
-                fetch_x(0);
-                if constexpr (!kCond) {
-                    typedef float f32x2 __attribute__((ext_vector_type(2)));
-                    if constexpr (Cell::kPairs) cell.template input_pair<0>(f32x2{ xr[0], xr[1] });
+                fetch_p(0);
 #pragma unroll
-                    for (int f = 0; f < kSB; ++f) {
-                        if ((f & 3) == 1 && f / 4 + 1 < kSB / 4) fetch_x(f / 4 + 1);
-#ifndef AIDAX_P4_BARRIER
-                        if (f == kSB - 4) ahead = *(const volatile p4_lds_i2*)(const p4_lds_i2*)(prog);
-#endif
-                        if constexpr (Cell::kPairs) {
-                            // (the paired LSTM-32 frame issues the NEXT frame's input pair itself, see LstmCell::step)
-                            if (f + 1 < kSB && (f & 1)) cell.template step<1, 0, false, true, 0>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f + 1], xr[(f + 2) % kSB] });
-                            else if (f + 1 < kSB) cell.template step<1, 0, false, true, 1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS, f32x2{ xr[f], xr[f + 1] });
-                            else cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
-                        } else
-                        cell.template step<1>(xr[f], 0.f, 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
-                    }
-                } else {
-                    // conditioned models (input_size 2 / 3, :186-233): PARAM1 / PARAM2 of every frame are the helper's (LinearValueSmoother per sample)
-                    const float* p1s = prow + (wave * 2 + 0) * n + base;
-                    const float* p2s = prow + (wave * 2 + 1) * n + base;
-                    float p1r[kSB], p2r[kSB];
-                    auto fetch_p = [&](int q) {
-                        const float4 u = reinterpret_cast<const float4*>(p1s)[q];
-                        const float4 w = reinterpret_cast<const float4*>(p2s)[q];
-                        p1r[4 * q] = u.x; p1r[4 * q + 1] = u.y; p1r[4 * q + 2] = u.z; p1r[4 * q + 3] = u.w;
-                        p2r[4 * q] = w.x; p2r[4 * q + 1] = w.y; p2r[4 * q + 2] = w.z; p2r[4 * q + 3] = w.w;
-                    };
-                    fetch_p(0);
-#pragma unroll
-                    for (int f = 0; f < kSB; ++f) {
-                        if ((f & 3) == 1 && f / 4 + 1 < kSB / 4) { fetch_x(f / 4 + 1); fetch_p(f / 4 + 1); }
-#ifndef AIDAX_P4_BARRIER
-                        if (f == kSB - 4) ahead = *(const volatile p4_lds_i2*)(const p4_lds_i2*)(prog);
-#endif
-                        cell.template step<3>(xr[f], p1r[f], I >= 3 ? p2r[f] : 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
-                    }
+                for (int f = 0; f < kSB; ++f) {
+                    if ((f & 3) == 1 && f / 4 + 1 < kSB / 4) { fetch_x(f / 4 + 1); fetch_p(f / 4 + 1); }
+                    if (f == kSB - 4) ahead = *(const volatile p4_lds_i2*)(const p4_lds_i2*)(prog);
+                    cell.template step<3>(xr[f], p1r[f], I >= 3 ? p2r[f] : 0.f, f == 0 ? hprev : hcur + (f - 1) * HS, hcur + f * HS);
                 }
             }
-#ifdef AIDAX_P4_BARRIER
-            __syncthreads();
-#else
             p4_post(prog + 2 + wave, t + 1, lane);
-#endif
         }
         P4_STAMP(6);                                          // (the last tile is done)
         cell.store(nnst);
@@ -1425,19 +1376,12 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
     // five compute nothing, and the stream's post cascade is then its first stage alone — K = 1, the gain on it, as without CTL_EQ_POST —
     // with eq_skip_sample where the EQ's output would have been. Five macro-steps of drain behind the last tile go with it when none of the
     // workgroup's streams runs an EQ (the longest cascade sets the launch's ticks; every stream runs its own K).
-    bool skipj = false;
-#ifndef AIDAX_P4_BARRIER
-    {
-        const unsigned long long flat = __builtin_amdgcn_ballot_w64(eq_stage_transparent(c.a0, c.a1, c.a2, c.b1, c.b2, c.z1, c.z2));
-        skipj = ((flat >> (12 * j + 7)) & 31u) == 31u && (flags & (CTL_EQ_POST | CTL_EQ_BANDPASS)) == CTL_EQ_POST
-             && !(AIDAX_TUNE(a) & kTuneEqFull);              // (test build: the full cascade, to compare the skip with)
-    }
-#endif
+    const unsigned long long flat = __builtin_amdgcn_ballot_w64(eq_stage_transparent(c.a0, c.a1, c.a2, c.b1, c.b2, c.z1, c.z2));
+    const bool skipj = ((flat >> (12 * j + 7)) & 31u) == 31u && (flags & (CTL_EQ_POST | CTL_EQ_BANDPASS)) == CTL_EQ_POST
+                    && !(AIDAX_TUNE(a) & kTuneEqFull);       // (test build: the full cascade, to compare the skip with)
     const int Kpj = (flags & CTL_EQ_PRE) ? 6 : 1, Kqj = (flags & CTL_EQ_POST) && !skipj ? 6 : 1;
-#ifndef AIDAX_P4_BARRIER
     const int Kq = __builtin_amdgcn_ballot_w64(there && lane < kP4ChainLanes && Kqj == 6) != 0 ? 6 : 1;
     const int T = (n / B - 1 + (Kq - 1) + 2 * (d1 + 1)) / 2 + 1;
-#endif
     c.K = isQ ? Kqj : Kpj;
     c.gain_lane = isQ ? Kqj - 1 : 0;
     c.eq_skip = skipj && isQ && stage == 0;
@@ -1475,9 +1419,6 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         if (tick == T - 1) P4_STAMP(4);                       // (the last tick begins)
 #endif
         // my turn: the helper before me has finished tick - 1 and left the cascades' state
-#ifdef AIDAX_P4_BARRIER
-        for (int i = 0; i < ((AIDAX_TUNE(a) >> 20) & 15); ++i) asm volatile("s_nop 15");
-#endif
         if (kP4Helpers > 1 && tick != 0) {
             while (p4_peek(prog + 6) < tick) __builtin_amdgcn_s_sleep(8);
             const double* zs = reinterpret_cast<const double*>(hstate);
@@ -1487,11 +1428,9 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
         // Dense + skip / output gain of the tile the cells finished a tick ago (applyModel :171-181), into the row: the post pass's input
         const int td = tick - d1 - 1;
         if (td >= 0 && td < NT) {
-#ifndef AIDAX_P4_BARRIER
 #pragma unroll
             for (int jj = 0; jj < kP4Streams; ++jj)
                 while (p4_peek(prog + 2 + jj) <= td) __builtin_amdgcn_s_sleep(4);      // every cell has finished the tile
-#endif
         }
         if (td >= 0 && td < NT && netd && !(AIDAX_TUNE(a) & 524288)) {      // (bit 524288, test build: no Dense — what it costs the recurrent wave it shares a SIMD with; wrong output)
             const int f = td * kSB + df;
@@ -1536,9 +1475,6 @@ __device__ __forceinline__ void stream_body_pipe4(const LaunchArgs& a, float* sm
             __builtin_amdgcn_wave_barrier();
             p4_post(prog, ts + 1, lane);
         }
-#ifdef AIDAX_P4_BARRIER
-        __syncthreads();
-#endif
         if (kP4Helpers > 1 && tick + 1 < T) {
             // the next tick is another helper's: the state, then the word that says so
             double* zs = reinterpret_cast<double*>(hstate);

@@ -188,11 +188,10 @@ struct StackDesc {
 constexpr int kQ4Regs = 21;
 
 constexpr int kMfmaStreams = 16;
-#ifndef AIDAX_MFMA_WIDE
-#define AIDAX_MFMA_WIDE 1
-#endif
 // waves per k_mfma workgroup: 8 (two per SIMD) when the tiles divide, else 4
-constexpr int mfma_waves(int hidden) { return (AIDAX_MFMA_WIDE && hidden % 32 == 0) ? 8 : 4; }
+// (four everywhere was a build switch once; no measurement with it is recorded — the nearest is k_mfma_ls's first version on four waves,
+// 908 against 694 us, profiles/r05_DESIGN_archive.md)
+constexpr int mfma_waves(int hidden) { return hidden % 32 == 0 ? 8 : 4; }
 struct MfmaLayer {
     int32_t cell;          // 0 LSTM, 1 GRU
     int32_t in_size;       // layer 0: 1..3 model inputs (one small segment); deeper: hidden of the layer below

@@ -13,14 +13,9 @@ namespace aidax {
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kLpChunk = 256;            // frames of audio staged in LDS at a time
-#ifndef AIDAX_LP_RING
-#define AIDAX_LP_RING 32                 // (measurement builds: -DAIDAX_LP_RING=16 -DAIDAX_LP_BATCH=4, scratch/mkvariant_lp.sh)
-#endif
-#ifndef AIDAX_LP_BATCH
-#define AIDAX_LP_BATCH 8
-#endif
-constexpr int kLpRing = AIDAX_LP_RING;   // frames of h in flight between two layers
-constexpr int kLpBatch = AIDAX_LP_BATCH; // frames per counter update (a release costs ~2-6 us, an acquire ~1.7 us: MI355X_MICROARCH.md)
+constexpr int kLpRing = 32;              // frames of h in flight between two layers
+constexpr int kLpBatch = 8;              // frames per counter update (a release costs ~2-6 us, an acquire ~1.7 us: MI355X_MICROARCH.md)
+// (a ring of 16 with counters every 4: cfg5 710.1 against 707.7 us, within the noise — profiles/r05_cfg5_modes.txt)
 // A waiting workgroup gives up after kLpGiveUpTicks of the 100 MHz wall clock (250 ms: far beyond any wait that co-tenant
 // kernels can cause while the partner still gets a CU — a launch must end even if its partner never runs). The pass is then
 // wrong; the workgroup says so in the pool's fault word (pinned host memory), the pool reports AIDAX_ERR_DEVICE for it
@@ -46,23 +41,19 @@ constexpr int kLpCounterStride = 32;     // uint32 per (group, boundary): produc
 // compiler keeps track of their completion (vmcnt) like of any other load.
 typedef unsigned lp_u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kLpDeviceScope = 17;                         // aux bits: sc0 | sc1
-#ifndef AIDAX_LP_LOAD_AUX
-#define AIDAX_LP_LOAD_AUX kLpDeviceScope                   // (measurement builds: the ring's loads / stores at another scope — 16 = sc1, 1 = sc0, 0 = none)
-#endif
-#ifndef AIDAX_LP_STORE_AUX
-#define AIDAX_LP_STORE_AUX kLpDeviceScope
-#endif
+// (The ring's loads / stores at a nearer scope — sc1, sc0 or none — buy no time, and below device scope a layer on another XCD reads
+// stale lines: profiles/r05_cfg5_modes.txt, profiles/r04_ls_parts8.txt.)
 __device__ __forceinline__ __amdgpu_buffer_rsrc_t lp_rsrc(const float* base, size_t bytes)
 {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(base), 0, (int)bytes, 0x00020000);
 }
 __device__ __forceinline__ f32x4 lp_load16(__amdgpu_buffer_rsrc_t r, uint32_t byte_off)
 {
-    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, AIDAX_LP_LOAD_AUX));
+    return __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(r, byte_off, 0, kLpDeviceScope));
 }
 __device__ __forceinline__ void lp_store16(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, f32x4 v)
 {
-    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lp_u32x4, v), r, byte_off, 0, AIDAX_LP_STORE_AUX);
+    __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(lp_u32x4, v), r, byte_off, 0, kLpDeviceScope);
 }
 
 __device__ __forceinline__ float lp_row_sum16(float v)
@@ -305,10 +296,10 @@ __device__ __forceinline__ unsigned gs_pack_bf16(float a, float b)
 typedef float gs_f32x2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void gs_split4(const float (&v)[4], u32x2 (&t)[3])
 {
-#ifndef AIDAX_GS_NOPK
     // The residuals' subtractions two values per instruction (v_pk_add_f32: the same IEEE subtraction per value). The main waves of the
     // tick kernels share their SIMD with one helper wave: they issue like a lone wave, for which a packed instruction costs what a plain
     // one does (profiles/r05_lone_wave_issue.txt) — and this split sits between a tick's last MFMA and its barrier.
+    // (One value per instruction, here and in k_gru_gs's cell update: cfg3 192.6 against 188.0 us, profiles/r05_DESIGN_archive.md.)
     gs_f32x2 r01 = { v[0], v[1] }, r23 = { v[2], v[3] };
 #pragma unroll
     for (int k = 0; k < 3; ++k) {
@@ -317,20 +308,6 @@ __device__ __forceinline__ void gs_split4(const float (&v)[4], u32x2 (&t)[3])
         if (k < 2) {
             r01 = r01 - gs_f32x2{ __builtin_bit_cast(float, p01 << 16), __builtin_bit_cast(float, p01 & 0xffff0000u) };
             r23 = r23 - gs_f32x2{ __builtin_bit_cast(float, p23 << 16), __builtin_bit_cast(float, p23 & 0xffff0000u) };
-        }
-    }
-    return;
-#endif
-    float r[4] = { v[0], v[1], v[2], v[3] };
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const unsigned p01 = gs_pack_bf16(r[0], r[1]), p23 = gs_pack_bf16(r[2], r[3]);
-        t[k] = u32x2{ p01, p23 };
-        if (k < 2) {
-            r[0] -= __builtin_bit_cast(float, p01 << 16);
-            r[1] -= __builtin_bit_cast(float, p01 & 0xffff0000u);
-            r[2] -= __builtin_bit_cast(float, p23 << 16);
-            r[3] -= __builtin_bit_cast(float, p23 & 0xffff0000u);
         }
     }
 }

@@ -28,14 +28,14 @@ struct LsGeo { int nw, tpw, m, nx; };      // nx: resident tile segments of a wa
 __host__ __device__ constexpr int ls_ks2(int hidden) { return (hidden + 31) / 32; }
 __host__ __device__ constexpr int ls_frag_vecs(int hidden) { return 3 * ls_ks2(hidden) * 64; }      // 16-byte vectors of one h buffer
 __host__ __device__ constexpr int ls_segments(int tpw, int m) { return tpw + (tpw - m > m ? tpw - m : m); }      // resident tile segments of a wave (the larger role)
+// LSTM-96 x 2 on eight waves: tiles per wave the lower layer starts for the upper one (1: 32 / 40 tile segments per workgroup, 2: 40 / 32;
+// no measurement of 1 is recorded)
+constexpr int kLsMoved96 = 2;
 __host__ __device__ constexpr LsGeo ls_geo(int n_layers, int hidden)
 {
     if (hidden < 16 || hidden % 16 != 0 || n_layers < 1) return LsGeo{ 0, 0, 0, 0 };
-#ifndef AIDAX_LS_M96
-#define AIDAX_LS_M96 2      // LSTM-96 x 2 on eight waves: tiles per wave the lower layer starts for the upper one (1: 32 / 40 tile segments per workgroup, 2: 40 / 32)
-#endif
     // registers a wave spends on resident fragments: all three terms of its own-h segments, term 0 of the others
-    const int nw = mfma_waves(hidden), tpw = hidden / 4 / nw, m = lp_moved_tiles(n_layers, tpw, nw) == 2 ? AIDAX_LS_M96 : lp_moved_tiles(n_layers, tpw, nw);
+    const int nw = mfma_waves(hidden), tpw = hidden / 4 / nw, m = lp_moved_tiles(n_layers, tpw, nw) == 2 ? kLsMoved96 : lp_moved_tiles(n_layers, tpw, nw);
     const int nx = n_layers == 1 ? 0 : ls_segments(tpw, m) - tpw;
     if (tpw * ls_ks2(hidden) * 12 + nx * ls_ks2(hidden) * 4 <= 140) return LsGeo{ nw, tpw, m, nx };
     const int tpw4 = hidden / 16, m4 = n_layers == 2 ? tpw4 / 2 : 0, nx4 = n_layers == 1 ? 0 : ls_segments(tpw4, m4) - tpw4;
@@ -98,11 +98,7 @@ __device__ __forceinline__ void ls_gates(f32x4 (&acc)[NACC], const LsFrags<KS2>&
                 for (int tw = 0; tw < n_w; ++tw) {
 #pragma unroll
                     for (int tl = TL0; tl < TL1; ++tl)
-#ifdef AIDAX_LS_NOMFMA                                            // (measurement build: everything but the matrix instructions)
-                        acc[tl][0] += __builtin_bit_cast(f32x4, hb.v[th][ks])[0] * __builtin_bit_cast(f32x4, wfrag(tl, ks, tw))[0];
-#else
                         acc[tl] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfrag(tl, ks, tw), hb.v[th][ks], acc[tl], 0, 0, 0);
-#endif
                     __builtin_amdgcn_sched_barrier(0);
                     valu(step++);
                     __builtin_amdgcn_sched_barrier(0);
@@ -291,10 +287,6 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
     for (int i = tid; i < 2 * kFrag; i += NT) below[i] = u32x4{ 0u, 0u, 0u, 0u };
     // where a lane's h values go in the fragments: unit u = 4T + q -> k-step u / 32, lane row (u % 32) / 8, element u % 8
     auto publish_tile = [&](u32x4* dst, int tl) {
-#ifdef AIDAX_LS_NOPUBLISH                                            // (measurement build, wrong results: what split + fragment writes cost)
-        (void)dst; (void)tl;
-        return;
-#endif
         const int u = 4 * (wave * TPW + tl) + q;
         uint16_t* p16 = reinterpret_cast<uint16_t*>(dst + (u >> 5) * 64 + ((u & 31) >> 3) * 16 + (lane & 15)) + (u & 7);
         float r = hv[tl];
@@ -312,15 +304,13 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
     // ---- the cell update of one tile in steps of three to five instructions, so that it can be dealt out behind the MFMA
     // groups of the NEXT tiles (bf16 MFMAs leave the VALU free while they run). Same operations in the same order as
     // sigmoid_pre / tanh_rat / tanh_exp_pre; the last step splits the new h and writes its fragments.
+    // (What each part adds to the cfg5 launch of 720 us, from builds with the part switched off and wrong results: cell update 90, ring
+    // stores 93, MFMAs 80, split + fragment writes 61, LDS-resident weight terms read at use 40 — profiles/r04_ls_parts8.txt.)
     struct CellTmp { float e0, e1, e2, x, u, p, qq, gg; };
     constexpr int NSTEP = CELL == 0 ? 12 : 5;
     CellTmp ct[TPW];
     auto cell_step = [&](int tl, int k, const f32x4& g, u32x4* h_dst) {
         CellTmp& t = ct[tl];
-#ifdef AIDAX_LS_NOCELL                                               // (measurement build, wrong results: what the cell update costs)
-        if (k == NSTEP - 1) { hv[tl] = g.x * 1e-9f; publish_tile(h_dst, tl); }
-        return;
-#endif
         if constexpr (CELL == 0) {                          // LSTM: g = (i, f, g, o), the sigmoid rows carrying -log2 e
             switch (k) {
             case 0: t.x = tanh_rat_clamp(g.z); t.u = t.x * t.x; t.e0 = __builtin_amdgcn_exp2f(g.x); break;
@@ -354,31 +344,19 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
     // whose shadow the cell update issues in) and leave at the head of the next one, so that every store has a whole tick to
     // drain before the barrier that precedes its publication.
     auto ship_h = [&](const u32x4* h_src, int Fprev) {
-#ifndef AIDAX_LS_NOSHIP                                              // (measurement build without the ring's stores: what the hand-over costs the lower layer)
         const uint32_t slot_off = (uint32_t)(((base_out + (uint32_t)Fprev) % kLpRing) * kSlot * sizeof(float));
         for (int i = tid; i < kFrag; i += NT) lp_store16(rs_out, slot_off + (uint32_t)i * 16u, __builtin_bit_cast(f32x4, h_src[i]));
-#else
-        (void)h_src; (void)Fprev;
-#endif
     };
     auto ship_started = [&](const f32x4 (&pacc)[MA], int Fprev) {
-#ifndef AIDAX_LS_NOSHIP
         const uint32_t slot_off = (uint32_t)(((base_out + (uint32_t)Fprev) % kLpRing) * kSlot * sizeof(float));
 #pragma unroll
         for (int tl = 0; tl < MW; ++tl)
             lp_store16(rs_out, slot_off + (uint32_t)(kFrag * 16) + (uint32_t)(((wave * M + tl) * kWave + lane) * 16), pacc[tl]);
-#else
-        (void)pacc; (void)Fprev;
-#endif
     };
     auto no_valu = [](int) {};
     auto own_w = [&](int tl, int ks, int tw) -> bf16x8 { return wq[tl][ks][tw]; };
     // the segments nobody waits for: x = tile (first layer: the tiles started for the layer above) / tile - MW (others)
-#ifdef AIDAX_LS_NOXW                                                 // (measurement build, wrong results: what reading the LDS-resident terms at use costs)
-    auto x_w = [&](int x, int ks, int tw) -> bf16x8 { (void)tw; return wx[x][ks]; };
-#else
     auto x_w = [&](int x, int ks, int tw) -> bf16x8 { return tw == 0 ? wx[x][ks] : __builtin_bit_cast(bf16x8, w2x[((x * KS2 + ks) * 2 + tw - 1) * 64]); };
-#endif
     auto up_w = [&](int tl, int ks, int tw) -> bf16x8 { return x_w(tl, ks, tw); };
     auto below_w = [&](int tl, int ks, int tw) -> bf16x8 { return x_w(tl - MW, ks, tw); };
     auto bias_of = [&](int tl, bool above) { return *reinterpret_cast<const f32x4*>(biasL + (above ? H * 4 : 0) + 4 * (4 * (wave * TPW + tl) + q)); };
@@ -562,31 +540,25 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
                     for (int tl = 0; tl < TPW; ++tl)
                         acc[tl] = __builtin_amdgcn_mfma_f32_16x16x4f32(w_in0[tl], b, acc[tl], 0, 0, 0);
                 }
-                // the cell steps of the tiles [T0, T1), dealt out over the G groups of a phase (the tiles advance together)
+                // the cell steps of the tiles [T0, T1), dealt out over the G groups of a phase (the tiles advance together; one tile's
+                // update after the other has eight temporaries fewer and less to overlap — tried, no result recorded)
                 auto deal = [&](int T0, int T1, int g) {
                     const int nt = T1 - T0, S = nt * NSTEP;
 #pragma unroll
-                    for (int sidx = g * S / G; sidx < (g + 1) * S / G; ++sidx) {
-#ifdef AIDAX_LS_SEQ_CELLS                                           // (one tile's update after the other: eight temporaries fewer, less to overlap)
-                        cell_step(T0 + sidx / NSTEP, sidx % NSTEP, acc[T0 + sidx / NSTEP], h_wr);
-#else
+                    for (int sidx = g * S / G; sidx < (g + 1) * S / G; ++sidx)
                         cell_step(T0 + sidx % nt, sidx / nt, acc[T0 + sidx % nt], h_wr);
-#endif
-                    }
                 };
                 // phase A: own h(t-1) against the first half of the tiles
                 LS_STAMP(2);
                 ls_gates<KS2, NPROD, 0, HALF, TPW>(acc, hb, own_w, no_valu);
                 LS_STAMP(3);
-#ifndef AIDAX_LS_STASH_LATE
                 if constexpr (!first) {
                     // frame F+2's fragments (requested at the head of the tick) go where frame F's were: their product was taken
-                    // a tick ago, and the registers they travelled in are free for the phases below. (At the END of the tick —
-                    // AIDAX_LS_STASH_LATE — the load has the whole tick to arrive: measured the same for LSTM-96 x 2, 712.5
-                    // against 713.3 us, and 3 % slower for LSTM-64 x 2.)
+                    // a tick ago, and the registers they travelled in are free for the phases below. (At the END of the tick
+                    // the load has the whole tick to arrive: measured the same for LSTM-96 x 2, 712.5 against 713.3 us
+                    // — profiles/r04_ls_parts8.txt — and 3 % slower for LSTM-64 x 2.)
                     if (more2) stash_below(tick & 1);
                 }
-#endif
                 // phase B: ... the second half, the first half's cell update in its shadow
                 if constexpr (HALF < TPW) ls_gates<KS2, NPROD, HALF, TPW, TPW>(acc, hb, own_w, [&](int g) { deal(0, HALF, g); });
                 else {
@@ -622,9 +594,6 @@ __device__ __forceinline__ void ls_body(const LaunchArgs& a, const MfmaDesc& d, 
                     }
                 }
                 LS_STAMP(5);
-#ifdef AIDAX_LS_STASH_LATE
-                if constexpr (!first) { if (more2) stash_below(tick & 1); }
-#endif
                 par = wr;
                 if (!last) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");     // this wave's ring stores (issued at the head of the tick) have left before the barrier (G16)
                 LS_STAMP(6);

@@ -344,12 +344,10 @@ struct GruGs : GsCell<UT, NPROD, 3> {
         // MFMA holds the VALU for its whole issue time. So the source says where it goes.
         ax = __builtin_amdgcn_mfma_f32_16x16x4f32(w_in[2], bx, ax, 0, 0, 0);
         LP_STAMP(2);
-#ifdef AIDAX_GS_PRIO                                             // (measurement: the main wave's tail — cell update, split, publish — ahead of the helpers)
-        __builtin_amdgcn_s_setprio(3);
-#endif
-#ifndef AIDAX_GS_NOPK
         // the cell update two units per instruction (v_pk_fma_f32 / v_pk_add_f32 around the two exponentials and reciprocals: the
-        // same operations per unit, the same bits): 18 instructions for 28 between the last MFMA and the publish
+        // same operations per unit, the same bits): 18 instructions for 28 between the last MFMA and the publish — with gs_split4's
+        // packed subtractions cfg3 192.6 -> 188.0 us against one unit per instruction (profiles/r05_DESIGN_archive.md).
+        // (Also tried: issue priority 3 for this tail — cell update, split, publish — ahead of the helpers. No result is recorded.)
 #pragma unroll
         for (int e = 0; e < 4; e += 2) {
             const gs_f32x2 gz = { sg8[e], sg8[e + 1] }, gr = { sg8[4 + e], sg8[5 + e] };
@@ -361,20 +359,9 @@ struct GruGs : GsCell<UT, NPROD, 3> {
             const gs_f32x2 hh = __builtin_elementwise_fma(gz, gs_f32x2{ hreg[e], hreg[e + 1] } - nn, nn);
             hreg[e] = hh.x; hreg[e + 1] = hh.y;
         }
-#else
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-            const float gz = sg8[e], gr = sg8[4 + e];
-            const float nn = tanh_exp_pre(__builtin_fmaf(gr, acc[2][e], ax[e]));      // (the record's candidate rows carry 2 log2 e)
-            hreg[e] = __builtin_fmaf(gz, hreg[e] - nn, nn);
-        }
-#endif
         LP_STAMP(3);
         publish(a, m, par ^ 1);
         LP_STAMP(4);
-#ifdef AIDAX_GS_PRIO
-        __builtin_amdgcn_s_setprio(0);
-#endif
     }
     __device__ __forceinline__ void store_state(float* dst, int Ht) const
     {
