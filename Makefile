@@ -23,7 +23,7 @@ HIPFLAGS := --offload-arch=$(ARCH) $(CXXFLAGS) -fno-slp-vectorize
 
 HOST_SRCS := $(SRC)/aidax_model.cpp $(SRC)/aidax_dsp_host.cpp $(SRC)/aidax_pack.cpp $(SRC)/aidax_pool.cpp $(SRC)/aidax_pool_model.cpp $(SRC)/aidax_pool_io.cpp $(SRC)/aidax_hub.cpp $(SRC)/aidax_ir.cpp $(SRC)/aidax_ir_stage.cpp $(SRC)/aidax_model_bank.cpp $(SRC)/aidax_rate.cpp $(SRC)/aidax_mix_book.cpp
 HOST_OBJS := $(patsubst $(SRC)/%.cpp,$(OBJDIR)/%.o,$(HOST_SRCS))
-KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp.o $(OBJDIR)/aidax_tick.o $(OBJDIR)/aidax_mfmals.o $(OBJDIR)/aidax_mfmals2.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o $(OBJDIR)/aidax_tune.o $(OBJDIR)/aidax_mix.o $(OBJDIR)/aidax_bus_limit.o $(OBJDIR)/aidax_bus_reverb.o
+KERN_OBJS := $(OBJDIR)/aidax_kernels.o $(OBJDIR)/aidax_stack.o $(OBJDIR)/aidax_mfma.o $(OBJDIR)/aidax_mfmalp.o $(OBJDIR)/aidax_tick.o $(OBJDIR)/aidax_mfmals.o $(OBJDIR)/aidax_mfmals2.o $(OBJDIR)/aidax_convm.o $(OBJDIR)/aidax_convs.o $(OBJDIR)/aidax_quad.o $(OBJDIR)/aidax_q4.o $(OBJDIR)/aidax_ir_mfma.o $(OBJDIR)/aidax_resample.o $(OBJDIR)/aidax_meter.o $(OBJDIR)/aidax_gate.o $(OBJDIR)/aidax_tune.o $(OBJDIR)/aidax_mix.o $(OBJDIR)/aidax_bus_limit.o $(OBJDIR)/aidax_bus_reverb.o $(OBJDIR)/aidax_delay.o
 HDRS      := $(wildcard $(SRC)/*.h) include/aidax.h
 
 LV2SO := $(PKG)/lv2/rt-neural-generic.so
@@ -166,6 +166,14 @@ build/asan/asan_tuner_harness: tests/asan_tuner_harness.cpp $(SRC)/aidax_tuner_b
 	    -Wall -Wextra -Iinclude tests/asan_tuner_harness.cpp -o $@
 asan_tuner: build/asan/asan_tuner_harness
 
+# ... and the stream delays' host half (DelayBook, aidax_delay_book.h — a header without HIP: the capacity and what fits it, the records and
+# parameters, which delays are on, the dirty range, the runs that restart): tests/asan_delay_harness.cpp, tests/test_asan_delay.py
+build/asan/asan_delay_harness: tests/asan_delay_harness.cpp $(SRC)/aidax_delay_book.h include/aidax.h
+	@mkdir -p build/asan
+	$(CXX) -O1 -g -std=c++17 -ffp-contract=off -fno-omit-frame-pointer -fsanitize=address,undefined -fno-sanitize-recover=undefined \
+	    -Wall -Wextra -Iinclude tests/asan_delay_harness.cpp -o $@
+asan_delay: build/asan/asan_delay_harness
+
 oracle:
 	$(MAKE) -s -C oracle all
 	$(MAKE) -s -C oracle _ref
@@ -174,4 +182,4 @@ clean:
 	rm -rf build $(LIBDIR) $(HOOKS_LIBDIR) $(LV2SO)
 	$(MAKE) -s -C oracle clean
 
-.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_own asan_form asan_hub asan_tuner
+.PHONY: all hooks oracle bundle clean asan asan_ir asan_ir_blend asan_bank asan_gate asan_mix asan_limit asan_reverb asan_own asan_form asan_hub asan_tuner asan_delay

@@ -140,6 +140,29 @@ BUS_METER_DTYPE = np.dtype([("frames", "<u8"), ("passes", "<u8"), ("in_nonfinite
                             ("in_peak", "<f4"), ("out_peak", "<f4"), ("min_gain", "<f4"), ("reserved", "<f4")])
 
 
+class DelayParams(C.Structure):
+    """aidax_delay_params: a stream delay as a user sets it (times in ms, the modulation rate in Hz)"""
+    _fields_ = [("time_ms", C.c_float), ("feedback", C.c_float), ("damping", C.c_float), ("wet", C.c_float), ("dry", C.c_float),
+                ("mod_rate_hz", C.c_float), ("mod_depth_ms", C.c_float), ("fade_ms", C.c_float)]
+
+
+class DelayRec(C.Structure):
+    """aidax_delay_rec: the record k_delay reads (48 bytes), what aidax_delay_design makes of DelayParams at a sample rate"""
+    _fields_ = [("m", C.c_uint32), ("depth_q16", C.c_uint32), ("lfo_step", C.c_uint32), ("fade", C.c_uint32), ("fb", C.c_float),
+                ("damp", C.c_float), ("wet", C.c_float), ("dry", C.c_float), ("on", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
+class DelayStateStruct(C.Structure):
+    """aidax_delay_state: one stream's delay state (32 bytes)"""
+    _fields_ = [("pos", C.c_uint64), ("m_cur", C.c_uint32), ("m_old", C.c_uint32), ("fade_len", C.c_uint32), ("fade_left", C.c_uint32),
+                ("phase", C.c_uint32), ("replaced", C.c_uint32)]
+
+
+DelayState = np.dtype([("pos", "<u8"), ("m_cur", "<u4"), ("m_old", "<u4"), ("fade_len", "<u4"), ("fade_left", "<u4"), ("phase", "<u4"),
+                       ("replaced", "<u4")])
+DELAY_MIN, DELAY_MAX = 64, 1 << 18               # AIDAX_DELAY_MIN, AIDAX_DELAY_MAX: frames
+
+
 def lib_path() -> str:
     # AIDAX_LIB: another build of the library (A/B measurements of two builds in one gpurun call)
     return os.environ.get("AIDAX_LIB") or os.path.join(_HERE, "lib", "libaidax_hip.so")
@@ -339,6 +362,15 @@ def lib() -> C.CDLL:
         L.aidax_pool_set_bus_reverb_rec.argtypes = [vp, i32, C.POINTER(BusReverbRec)]
         L.aidax_pool_bus_reverb.argtypes = [vp, u32, C.POINTER(BusReverbParams), C.POINTER(BusReverbRec), C.POINTER(C.c_int), C.POINTER(C.c_uint64)]
         L.aidax_pool_reset_bus_reverb.argtypes = [vp, i32]
+    if hasattr(L, "aidax_pool_set_delays"):       # (... or from before the stream delays)
+        L.aidax_delay_design.argtypes = [C.POINTER(DelayParams), C.c_double, C.POINTER(DelayRec)]
+        L.aidax_pool_set_delays.argtypes = [vp, C.c_int, u32]
+        L.aidax_pool_delays.argtypes = [vp]
+        L.aidax_pool_set_delay.argtypes = [vp, i32, C.POINTER(DelayParams)]
+        L.aidax_pool_set_delay_rec.argtypes = [vp, i32, C.POINTER(DelayRec)]
+        L.aidax_pool_stream_delay.argtypes = [vp, u32, C.POINTER(DelayParams), C.POINTER(DelayRec), C.POINTER(C.c_int)]
+        L.aidax_pool_read_delays.argtypes = [vp, u32, u32, C.POINTER(DelayStateStruct)]
+        L.aidax_pool_reset_delay.argtypes = [vp, i32]
     _lib = L
     return L
 
@@ -412,6 +444,13 @@ def bus_reverb_design(params: BusReverbParams, samplerate: float) -> BusReverbRe
     """aidax_bus_reverb_design: the record of `params` at `samplerate` (pure, host only)"""
     out = BusReverbRec()
     _check(lib().aidax_bus_reverb_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
+    return out
+
+
+def delay_design(params: DelayParams, samplerate: float) -> DelayRec:
+    """aidax_delay_design: the record of `params` at `samplerate` (pure, host only)"""
+    out = DelayRec()
+    _check(lib().aidax_delay_design(C.byref(params) if params is not None else None, samplerate, C.byref(out)))
     return out
 
 
@@ -788,6 +827,42 @@ class Pool:
         out = np.zeros(max(count, 0), GATE_STATE_DTYPE)
         _check(lib().aidax_pool_read_gate(self.h, first, count, out.ctypes.data_as(C.POINTER(GateState))))
         return out
+
+    def set_delays(self, on: bool, max_delay_frames: int = 48000):
+        """aidax_pool_set_delays: the stream delays behind the IR stage on or off (the first enabling call allocates and fixes the
+        capacity: a set-up side call; off -> on restarts every line)"""
+        _check(lib().aidax_pool_set_delays(self.h, 1 if on else 0, max_delay_frames))
+
+    @property
+    def delays(self) -> bool:
+        return bool(lib().aidax_pool_delays(self.h))
+
+    def set_delay(self, params: Optional[DelayParams], stream: int = ALL_STREAMS):
+        """aidax_pool_set_delay: the stream's (default: every stream's) delay from the next pass on, None: off"""
+        _check(lib().aidax_pool_set_delay(self.h, stream, C.byref(params) if params is not None else None))
+
+    def set_delay_rec(self, rec: Optional[DelayRec], stream: int = ALL_STREAMS):
+        """aidax_pool_set_delay_rec: the same with a record of the caller's own, None: off"""
+        _check(lib().aidax_pool_set_delay_rec(self.h, stream, C.byref(rec) if rec is not None else None))
+
+    def stream_delay(self, stream: int):
+        """aidax_pool_stream_delay: (the stream's DelayParams as last set, its DelayRec, whether its delay is on)"""
+        out, rec, on = DelayParams(), DelayRec(), C.c_int(0)
+        _check(lib().aidax_pool_stream_delay(self.h, stream, C.byref(out), C.byref(rec), C.byref(on)))
+        return out, rec, bool(on.value)
+
+    def read_delays(self, first: int = 0, count: Optional[int] = None) -> np.ndarray:
+        """aidax_pool_read_delays: the delay states of `count` streams from `first` (default: all from `first` on) as a structured array
+        with aidax_delay_state's field names, behind every pass issued so far"""
+        if count is None:
+            count = self.n_streams - first
+        out = np.zeros(max(count, 0), DelayState)
+        _check(lib().aidax_pool_read_delays(self.h, first, count, out.ctypes.data_as(C.POINTER(DelayStateStruct))))
+        return out
+
+    def reset_delay(self, stream: int = ALL_STREAMS):
+        """aidax_pool_reset_delay: the stream's (default: every stream's) line restarts at the next pass's first frame"""
+        _check(lib().aidax_pool_reset_delay(self.h, stream))
 
     def set_buses(self, n_buses: int):
         """aidax_pool_set_buses: the pool's mix buses (the first call with a count allocates: a set-up side call; 0: off)"""

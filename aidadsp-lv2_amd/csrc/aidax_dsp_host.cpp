@@ -334,6 +334,43 @@ AIDAX_API int aidax_bus_reverb_design(const aidax_bus_reverb_params* params, dou
     return AIDAX_OK;
 }
 
+// The record of a stream delay (include/aidax.h, "Stream delays"), in fp64: the times as frames, the depth as Q16 frames, the rate as a
+// step of the 32-bit phase, the damping as the FIR's coefficient.
+AIDAX_API int aidax_delay_design(const aidax_delay_params* params, double samplerate, aidax_delay_rec* out)
+{
+    using aidax::fail;
+    if (!params || !out) return fail(AIDAX_ERR_ARG, "delay_design: null argument");
+    const aidax_delay_params& v = *params;
+    if (!(samplerate > 0.0) || !std::isfinite(samplerate)) return fail(AIDAX_ERR_ARG, "delay_design: samplerate must be positive");
+    // (compared as fp64 ahead of the rounding: a time of any size is refused, never wrapped)
+    const double m = static_cast<double>(v.time_ms) * samplerate / 1000.0;
+    if (!(m < AIDAX_DELAY_MAX + 1.0) || !(m >= 0.0) || std::llround(m) < AIDAX_DELAY_MIN || std::llround(m) > AIDAX_DELAY_MAX)
+        return fail(AIDAX_ERR_ARG, "delay_design: the delay must be 64 .. 262144 frames");
+    if (!(std::fabs(v.feedback) <= 0.98f)) return fail(AIDAX_ERR_ARG, "delay_design: feedback must be in [-0.98, 0.98]");
+    if (!(v.damping >= 0.f && v.damping <= 1.f)) return fail(AIDAX_ERR_ARG, "delay_design: damping must be in [0, 1]");
+    if (!(std::fabs(v.wet) <= 4.f) || !(std::fabs(v.dry) <= 4.f)) return fail(AIDAX_ERR_ARG, "delay_design: wet and dry must be finite and at most 4 in magnitude");
+    const double depth = static_cast<double>(v.mod_depth_ms) * samplerate / 1000.0 * 65536.0;
+    if (!(depth >= 0.0) || !(depth < AIDAX_DELAY_MAX_DEPTH * 65536.0 + 1.0) || std::llround(depth) > AIDAX_DELAY_MAX_DEPTH * 65536ll)
+        return fail(AIDAX_ERR_ARG, "delay_design: the modulation depth must be 0 .. 4096 frames");
+    if (!(v.mod_rate_hz >= 0.f && v.mod_rate_hz <= 1000.f) || !(static_cast<double>(v.mod_rate_hz) <= samplerate / 2.0))
+        return fail(AIDAX_ERR_ARG, "delay_design: mod_rate_hz must be in [0, 1000] and at most half the samplerate");
+    const double fade = static_cast<double>(v.fade_ms) * samplerate / 1000.0;
+    if (!(fade >= 0.0) || !(fade < AIDAX_DELAY_MAX_FADE + 1.0) || std::llround(fade) > AIDAX_DELAY_MAX_FADE)
+        return fail(AIDAX_ERR_ARG, "delay_design: the fade must be 0 .. 1048576 frames");
+    aidax_delay_rec r{};
+    r.m = static_cast<uint32_t>(std::llround(m));
+    r.depth_q16 = static_cast<uint32_t>(std::llround(depth));
+    r.lfo_step = static_cast<uint32_t>(std::llround(static_cast<double>(v.mod_rate_hz) / samplerate * 4294967296.0));
+    r.fade = static_cast<uint32_t>(std::llround(fade));
+    r.fb = v.feedback;
+    r.damp = static_cast<float>(static_cast<double>(v.damping) * 0.5);
+    r.wet = v.wet;
+    r.dry = v.dry;
+    r.on = 1u;
+    *out = r;
+    return AIDAX_OK;
+}
+
 // The stream tuners' design (include/aidax.h, "Stream tuners"): the lag range of [f_min, f_max] at the sample rate, in fp64, the
 // shortest lag rounded down and the longest rounded up so that the range holds both frequencies.
 AIDAX_API void aidax_tuner_params_default(aidax_tuner_params* params)

@@ -17,7 +17,7 @@
 
 #ifdef AIDAX_TEST_HOOKS
 // Test build only: per thread, how often the pool's sources call each HIP runtime entry point they use (every call site, checked with
-// HIP_TRY or not), each IR stage launcher, the meters' (launch_meter), the gate's (launch_gate), the tuners' (launch_tune), the mix buses' (launch_mix), the bus reverbs' (launch_bus_reverb) and the bus limiters' (launch_bus_limit), read and cleared by aidax_test_hip_calls (aidax_pool.cpp). ONE fixed table per thread for
+// HIP_TRY or not), each IR stage launcher, the meters' (launch_meter), the gate's (launch_gate), the tuners' (launch_tune), the mix buses' (launch_mix), the bus reverbs' (launch_bus_reverb), the stream delays' (launch_delay) and the bus limiters' (launch_bus_limit), read and cleared by aidax_test_hip_calls (aidax_pool.cpp). ONE fixed table per thread for
 // every source (an inline function's static): counting allocates nothing.
 // (tests/test_gpu_ir_bank_rt.py: the audio-thread calls allocate, free and wait for nothing.)
 namespace aidax {
@@ -80,6 +80,7 @@ inline int read_hip_calls(char* buf, uint32_t cap)
 #define launch_mix(...) (aidax::note_hip_call("launch_mix"), aidax::launch_mix(__VA_ARGS__))
 #define launch_bus_limit(...) (aidax::note_hip_call("launch_bus_limit"), aidax::launch_bus_limit(__VA_ARGS__))
 #define launch_bus_reverb(...) (aidax::note_hip_call("launch_bus_reverb"), aidax::launch_bus_reverb(__VA_ARGS__))
+#define launch_delay(...) (aidax::note_hip_call("launch_delay"), aidax::launch_delay(__VA_ARGS__))
 #endif
 
 namespace aidax {

@@ -317,6 +317,33 @@ struct BusReverbArgs {
 };
 hipError_t launch_bus_reverb(const BusReverbArgs& a, hipStream_t q);
 
+// The stream delays behind the IR stage (aidax_delay.hip, k_delay): one launch delays, in place, the block a pass returns, [n_active]
+// [n_frames], by the per-frame rule of include/aidax.h ("Stream delays"), a workgroup per stream. DelayRec is aidax_delay_rec and
+// DelayState aidax_delay_state, field for field. Each stream has one row of mask + 1 floats in `ring`, its line's memory: d of the line's
+// frame k lives in slot k & mask, and a frame before the line's frame 0 reads as 0. A row holds cap + 3 frames of history next to the
+// longest pass. A stream whose record is off, or whose control record lacks CTL_ENABLED, is not touched: its row keeps its bits and its
+// state does not move.
+constexpr uint32_t kDelayMin = 64, kDelayMax = 1u << 18, kDelayMaxDepth = 4096, kDelayMaxFade = 1u << 20;
+struct DelayRec {
+    uint32_t m, depth_q16, lfo_step, fade;
+    float fb, damp, wet, dry;
+    uint32_t on, reserved[3];
+};
+struct DelayState {
+    uint64_t pos;
+    uint32_t m_cur, m_old, fade_len, fade_left, phase, replaced;
+};
+static_assert(sizeof(DelayRec) == 48 && sizeof(DelayState) == 32, "a stream's delay record is 48 bytes, its state 32");
+struct DelayArgs {
+    float* block;                // [n_active][n_frames]: what the pass returns, delayed in place
+    float* ring;                 // [n_streams][mask + 1]
+    const DelayRec* rec;         // [n_streams]
+    DelayState* state;           // [n_streams]
+    const StreamCtl* ctl;        // [n_streams]
+    uint32_t n_active, n_frames, mask, cap;
+};
+hipError_t launch_delay(const DelayArgs& a, hipStream_t q);
+
 hipError_t launch_keep_warm_kernel(int workgroups, hipStream_t stream);      // an empty grid (AIDAX_KEEP_WARM_US, aidax_pool.cpp)
 
 }  // namespace aidax

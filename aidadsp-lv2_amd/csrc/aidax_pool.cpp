@@ -222,7 +222,9 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         const bool meter_on = n_frames != 0 && p->meter.on;
         // ... and a pass with the mix buses on behind k_mix: a pass that has ended for the host has been mixed
         const bool mix_on = n_frames != 0 && p->mix.on;
-        if (ir_on || meter_on || mix_on) end = nullptr;                // (the markers are not handed down: nullptr to launch)
+        // ... and a pass with a stream delay on behind k_delay, which works in place on the block the pass returns
+        const bool delay_on = n_frames != 0 && p->delay.plays();
+        if (ir_on || meter_on || mix_on || delay_on) end = nullptr;    // (the markers are not handed down: nullptr to launch)
         if (ir_on) p->ir.begin_pass(s, p->any_pass);                   // the plan this pass is issued with, ahead of it
         if (meter_on) p->meter.launch_in(d_in, n_active, n_frames, s);  // (ahead of the pass: it may work in place)
         p->tuner.before_pass(d_in, n_active, n_frames, s);            // the tuners read the same block: the DI signal, ahead of the gate
@@ -230,6 +232,7 @@ int pool_process_prefix(aidax_pool* p, const float* d_in, float* d_out, uint32_t
         HIP_TRY(p->launch(p->cur, a, s, end, form));
         if (ir_on) p->ir.issue(s, d_out, n_active, n_frames);
         else p->ir.plan.advance(n_active, n_frames);                   // (no history yet: both sides of a blend are the dry block, its ramps run on)
+        if (delay_on) p->delay.after_pass(d_out, p->d_ctl.get(), n_active, n_frames, s);      // the stream delays, in place: the meters and the buses see the delayed block
         if (meter_on) p->meter.launch_out(d_out, n_active, n_frames, s);
         const bool limit_on = mix_on && p->limit.on;                   // the bus limiters: k_mix writes their raw side block, k_bus_limit the bus block
         if (mix_on) p->mix.after_pass(d_out, n_active, n_frames, s, limit_on ? p->limit.d_raw.get() : nullptr);      // the buses: a gather over the block the pass returns
@@ -713,6 +716,101 @@ AIDAX_API int aidax_pool_reset_bus_reverb(aidax_pool* p, int32_t bus)
     return AIDAX_OK;
 }
 
+// The stream delays (aidax_delay_stage.h). The first aidax_pool_set_delays with on != 0 is the set-up side's (it allocates); everything
+// else changes or reads host records of the audio side, a restart is a memset on the pool's own stream behind every pass issued so far,
+// and the read of the states waits like aidax_pool_read_gate.
+AIDAX_API int aidax_pool_set_delays(aidax_pool* p, int on, uint32_t max_delay_frames)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    DelayStage& d = p->delay;
+    if (!on) {
+        d.on = false;                                       // (off before any on: nothing to change)
+        return AIDAX_OK;
+    }
+    if (max_delay_frames < AIDAX_DELAY_MIN || max_delay_frames > AIDAX_DELAY_MAX) return fail(AIDAX_ERR_ARG, "the stream delays' capacity is 64 .. 262144 frames");
+    if (d.enabled()) {
+        if (max_delay_frames != d.book.cap) return fail(AIDAX_ERR_STATE, "the stream delays' capacity is fixed once set");
+        if (d.on) return AIDAX_OK;
+        d.on = true;                                        // off -> on: every line restarts
+        return p->on_own_stream([&]() -> int { d.clear_states(0, p->n_streams, p->q); return AIDAX_OK; });
+    }
+    return guarded([&]() -> int {
+        HIP_TRY(hipSetDevice(p->device));
+        d.enable(p->n_streams, p->max_frames, max_delay_frames, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_delays(const aidax_pool* p) { return p && p->delay.on ? 1 : 0; }
+
+// the range of streams a call names, or an error
+static int delay_streams(aidax_pool* p, int32_t stream, uint32_t* lo, uint32_t* hi)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (!p->delay.enabled()) return fail(AIDAX_ERR_STATE, "the stream delays were never enabled (aidax_pool_set_delays)");
+    return named_range(stream, p->n_streams, lo, hi) ? AIDAX_OK : fail(AIDAX_ERR_ARG, "stream out of range");
+}
+
+// the record (or nullptr: off) into the book; the runs that went from off to on restart
+static int delay_set(aidax_pool* p, uint32_t lo, uint32_t hi, const aidax_delay_rec* rec, const aidax_delay_params* params)
+{
+    DelayStage& d = p->delay;
+    bool ok = true;
+    const auto& restart = d.book.set(lo, hi, rec, params, &ok);
+    if (!ok) return fail(AIDAX_ERR_ARG, "the delay and its modulation depth exceed the capacity of aidax_pool_set_delays");
+    if (restart.empty()) return AIDAX_OK;
+    return p->on_own_stream([&]() -> int {
+        for (const DelayBook::Run& r : restart) d.clear_states(r.first, r.second - r.first, p->q);
+        return AIDAX_OK;
+    });
+}
+
+AIDAX_API int aidax_pool_set_delay(aidax_pool* p, int32_t stream, const aidax_delay_params* params)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = delay_streams(p, stream, &lo, &hi)) return rc;
+    aidax_delay_rec designed{};
+    if (params)
+        if (const int rc = aidax_delay_design(params, aidax_pool_samplerate(p), &designed)) return rc;
+    return delay_set(p, lo, hi, params ? &designed : nullptr, params);
+}
+
+AIDAX_API int aidax_pool_set_delay_rec(aidax_pool* p, int32_t stream, const aidax_delay_rec* rec)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = delay_streams(p, stream, &lo, &hi)) return rc;
+    if (rec && !DelayBook::valid(*rec))
+        return fail(AIDAX_ERR_ARG, "delay record: m 64 .. 262144, depth at most 4096 frames, fade at most 1048576, |fb| <= 0.98, 0 <= damp <= 0.5, wet and dry finite and at most 4 in magnitude");
+    return delay_set(p, lo, hi, rec, nullptr);
+}
+
+AIDAX_API int aidax_pool_stream_delay(const aidax_pool* p, uint32_t stream, aidax_delay_params* params, aidax_delay_rec* rec, int* on)
+{
+    if (!p) return fail(AIDAX_ERR_ARG, "null pool");
+    if (stream >= p->n_streams) return fail(AIDAX_ERR_ARG, "stream out of range");
+    const DelayStage& d = p->delay;
+    const bool is_on = d.enabled() && d.book.h_rec[stream].on;
+    if (params) *params = is_on ? d.book.params[stream] : aidax_delay_params{};
+    if (rec) *rec = is_on ? d.book.h_rec[stream] : aidax_delay_rec{};
+    if (on) *on = is_on ? 1 : 0;
+    return AIDAX_OK;
+}
+
+AIDAX_API int aidax_pool_read_delays(aidax_pool* p, uint32_t first, uint32_t count, aidax_delay_state* out)
+{
+    if (!p || !out) return fail(AIDAX_ERR_ARG, "null argument");
+    if (count == 0 || first > p->n_streams || count > p->n_streams - first) return fail(AIDAX_ERR_ARG, "stream range out of the pool's streams");
+    if (!p->delay.enabled()) return fail(AIDAX_ERR_STATE, "the stream delays were never enabled (aidax_pool_set_delays)");
+    return p->on_own_stream([&]() -> int { p->delay.read(first, count, out, p->q); return AIDAX_OK; });
+}
+
+AIDAX_API int aidax_pool_reset_delay(aidax_pool* p, int32_t stream)
+{
+    uint32_t lo = 0, hi = 0;
+    if (const int rc = delay_streams(p, stream, &lo, &hi)) return rc;
+    return p->on_own_stream([&]() -> int { p->delay.clear_states(lo, hi - lo, p->q); return AIDAX_OK; });
+}
+
 AIDAX_API int aidax_pool_reset_stream(aidax_pool* p, uint32_t stream, int start_mode) { return aidax::pool_reset_stream_inherit(p, stream, start_mode, nullptr); }
 
 #ifdef AIDAX_TEST_HOOKS
@@ -765,6 +863,7 @@ int pool_reset_stream_inherit(aidax_pool* p, uint32_t stream, int start_mode, co
         p->ir.clear_stream(stream, p->q);                              // a fresh instance has no past for the IR to sound
         p->gate.clear_states(stream, 1, p->q);                         // ... and its gate starts at unity gain, hold expired
         if (p->tuner.enabled()) { p->tuner.book.restart(stream); p->tuner.clear_streams(stream, 1, p->q); }      // ... and its tuner has heard nothing
+        p->delay.clear_states(stream, 1, p->q);                        // ... and its delay line is empty
         if (p_targets) HIP_TRY(launch_set_param_targets(p->d_st.get() + stream, p_targets[0], p_targets[1], p->q));
         const ModelBank* b = p->bank.adopt();                         // (a stream on a bank slot keeps it: that slot's weights, gains and skip)
         if (m.has_model) p->fresh_stream_model(m, stream, start_mode, b && b->assign[stream] >= 0 ? ModelBank::rec_of(b->slot[b->assign[stream]]) : m.rec(), p->q);

@@ -18,6 +18,7 @@
 #include "aidax_mix_stage.h"
 #include "aidax_limit_stage.h"
 #include "aidax_reverb_stage.h"
+#include "aidax_delay_stage.h"
 
 namespace aidax {
 
@@ -210,6 +211,7 @@ struct aidax_pool {
     MeterStage meter;                // the stream meters on both sides of a pass (aidax_stream_stages.h; nothing until the first aidax_pool_set_metering(1))
     GateStage gate;                  // the noise gate ahead of the model (nothing until the first aidax_pool_set_gate that enables one)
     TunerStage tuner;                // the stream tuners ahead of the model (nothing until the first aidax_pool_set_tuning with parameters)
+    DelayStage delay;                // the stream delays behind the IR stage (aidax_delay_stage.h; nothing until the first aidax_pool_set_delays(1, ..))
     MixStage mix;                    // the mix buses behind the last stage (aidax_mix_stage.h; nothing until the first aidax_pool_set_buses with a count)
     ReverbStage reverb;              // the bus reverbs between k_mix and k_bus_limit (aidax_reverb_stage.h; nothing until the first aidax_pool_set_bus_reverbs(1, ..))
     LimitStage limit;                // the bus limiters and bus meters behind k_mix (aidax_limit_stage.h; nothing until the first aidax_pool_set_bus_limiting(1, ..))

@@ -943,15 +943,114 @@ AIDAX_API int      aidax_pool_set_bus_reverb_rec(aidax_pool* p, int32_t bus, con
 AIDAX_API int      aidax_pool_bus_reverb(const aidax_pool* p, uint32_t bus, aidax_bus_reverb_params* params, aidax_bus_reverb_rec* rec, int* on, uint64_t* frames_since_epoch);
 AIDAX_API int      aidax_pool_reset_bus_reverb(aidax_pool* p, int32_t bus);
 
+/* Stream delays: the player's own time effect — an echo, a slap-back, a chorus, a flanger — per stream, computed where the blocks are
+ * (k_delay, aidax_delay.hip): behind the cabinet IR stage and ahead of the meters' output side and the mix buses, which then see the
+ * DELAYED block. Opt-in: a pool that never calls aidax_pool_set_delays, or has the stage off or every delay off, allocates and
+ * launches exactly what it did before these calls existed, bit for bit. While the stage is on and a delay is on, one launch of k_delay
+ * behind every pass of n_frames > 0 works in place on the block the pass returns.
+ * The rule, normative (tests/delayhelp.py restates it in numpy, frame by frame; the kernel agrees with it bit for bit). Each stream has
+ * a record (aidax_delay_rec) and a state (aidax_delay_state, all zero after a restart). The record: m, the delay in frames
+ * (AIDAX_DELAY_MIN = 64 <= m); depth_q16, the modulation depth in frames * 2^16 (at most AIDAX_DELAY_MAX_DEPTH = 4096 frames); lfo_step,
+ * the phase increment per frame of a 32-bit phase; fade, the crossfade length in frames (0 .. AIDAX_DELAY_MAX_FADE = 2^20); fb (fp32,
+ * |fb| <= 0.98; negative feedback is allowed: a flanger uses it); damp (fp32, 0 .. 0.5); wet and dry (fp32, finite, magnitude <= 4);
+ * on. The pool's capacity `cap` bounds m + ceil(depth) <= cap.
+ * At the FIRST FRAME OF A PASS, for a stream that plays (below): if m_cur == 0 (a fresh line) m_cur = m, no fade; else if m != m_cur
+ * then m_old = m_cur, m_cur = m, fade_len = fade_left = fade. A fade still in progress at that moment is dropped at its target: the
+ * second change of time inside a fade is NOT click-free.
+ * Then FOR EVERY FRAME, with n = pos its index in the line's own time, x_raw the sample in the block, x the SANITISED sample (NaN and
+ * +-Inf replaced by +0.0f, then clamped to +-2^64) and d[k] the line's memory, 0 for k < 0. Every fp32 operation below is ONE operation
+ * rounded to nearest; there is no fma anywhere:
+ *     u   = (phase >> 8) & 0xffffff;   tri = u < 2^23 ? u : 2^24 - u                              (a triangle, 0 .. 2^23)
+ *     off = ((uint64)depth_q16 * tri) >> 23                                                       (Q16 frames, >= 0)
+ *     tap(M): D = ((uint64)M << 16) + off;   i = min(D >> 16, cap);   fr = (float)(D & 0xffff) * 2^-16
+ *             a = d[n - i], b = d[n - i - 1], c = d[n - i - 2]
+ *             p0 = a + fr * (b - a);   p1 = b + fr * (c - b);   tap = p0 + damp * (p1 - p0)
+ *     f = tap(m_cur)
+ *     if fade_left > 0:   w = (float)((double)(fade_len - fade_left) / (double)fade_len)
+ *                         f = tap(m_old) + w * (f - tap(m_old));   fade_left -= 1
+ *     d[n]   = x + fb * f
+ *     out[n] = dry * x + wet * f
+ *     pos += 1;   phase += lfo_step (mod 2^32);   replaced += (x_raw is NaN or +-Inf)
+ * (min(.., cap) changes nothing for the record's own delay, whose reach fits the capacity; it bounds the OLD delay of a fade under a
+ * record whose depth has grown at the same time.) What follows: a frame reads nothing younger than n - min(m_cur, m_old while fading),
+ * so the frames of a chunk of K <= that minimum are independent of one another; every tap is a convex combination, so |fb| <= 0.98
+ * bounds the line and every output of a playing stream is finite (below 2^72 under a constant 2^64 input at fb = 0.98, wet = dry = 4);
+ * the output does not depend on how the host cuts the stream into blocks; wet = 0 and dry = 1 return the bits of a finite input
+ * below 2^64 (a -0.0f may come back as +0.0f).
+ * Which streams play: those whose delay is on and whose control record is enabled (not a disabled plugin, not a parked seat). Any
+ * other row is left untouched bit for bit and its state does not move. A line restarts — its state is zeroed on the pool's own stream,
+ * behind every pass issued so far; its memory needs no clearing — when its delay goes from off to on, when the stage goes from off to
+ * on (every line), by aidax_pool_reset_delay and by aidax_pool_reset_stream. A change of fb, damp, wet, dry, depth_q16, lfo_step or fade
+ * acts at the next pass's first frame and keeps the line; only m fades.
+ * aidax_delay_design        pure, host only, any thread: the record of `params` at `samplerate`, in fp64. m = llround(time_ms *
+ *                           samplerate / 1000), 64 .. AIDAX_DELAY_MAX; fb = feedback, |fb| <= 0.98; damp = (float)(damping * 0.5),
+ *                           damping 0 .. 1; wet and dry finite with magnitude <= 4; depth_q16 = llround(mod_depth_ms * samplerate /
+ *                           1000 * 65536), mod_depth_ms >= 0 and at most 4096 frames; lfo_step = llround(mod_rate_hz / samplerate *
+ *                           2^32), 0 <= mod_rate_hz <= 1000 and at most samplerate / 2; fade = llround(fade_ms * samplerate / 1000),
+ *                           0 .. 2^20; on = 1. AIDAX_ERR_ARG for a null pointer, anything outside these bounds (a NaN is), a
+ *                           samplerate that is not positive; `out` is untouched then.
+ * aidax_pool_set_delays     SET-UP side. The first call with on != 0 allocates everything the feature ever needs — a ring row per
+ *                           stream (the smallest power of two >= capacity + 3 + max_frames floats), the records (every delay off),
+ *                           the states and their snapshots — all or nothing, fixes the capacity (max_delay_frames 64 ..
+ *                           AIDAX_DELAY_MAX = 1 << 18), switches the stage on, and may wait. Later calls only flip a host record of
+ *                           the audio side (off -> on restarts every line): on != 0 with another capacity is AIDAX_ERR_STATE, on == 0
+ *                           ignores it. AIDAX_ERR_ARG for a null pool or a capacity out of range.
+ * aidax_pool_delays         1 while the stage is on, else 0 (0 for a null pool).
+ * aidax_pool_set_delay      AUDIO thread, between passes: `stream` (AIDAX_ALL_STREAMS: every stream) is delayed with `params`,
+ *                           designed at aidax_pool_samplerate, from the next pass on; params == NULL switches its delay off. Host
+ *                           records only (they reach the device from a ring of snapshots ahead of the next delayed pass; a restart
+ *                           is one memset on the pool's own stream): no allocation, no free, no wait. AIDAX_ERR_ARG for a null
+ *                           pool, a stream out of range, whatever aidax_delay_design refuses and a record beyond the capacity (a
+ *                           refused call changes nothing); AIDAX_ERR_STATE before the stage's first enabling.
+ * aidax_pool_set_delay_rec  the same with a record of the caller's own; its `on` is ignored. AIDAX_ERR_ARG also for a record outside
+ *                           the conditions above; rec == NULL switches the delay off.
+ * aidax_pool_stream_delay   the stream's host record (any pointer may be NULL): its parameters as last set (zeros while off or set
+ *                           by a record), its record (zeros while off), whether its delay is on.
+ * aidax_pool_read_delays    AUDIO thread, waits like aidax_pool_read_gate: the states of `count` streams from `first`, behind every
+ *                           pass issued so far.
+ * aidax_pool_reset_delay    AUDIO thread, between passes: the line of `stream` (AIDAX_ALL_STREAMS: every stream) restarts at the
+ *                           next pass's first frame. Errors as aidax_pool_set_delay's.
+ * Not covered: hub seats and so the LV2 shell, a fade that survives a second change of time, ping-pong / stereo, tempo sync (the host
+ * converts BPM to ms), a line per IR side. */
+#define AIDAX_DELAY_MIN 64
+#define AIDAX_DELAY_MAX (1 << 18)
+#define AIDAX_DELAY_MAX_DEPTH 4096
+#define AIDAX_DELAY_MAX_FADE (1 << 20)
+typedef struct { float time_ms, feedback, damping, wet, dry, mod_rate_hz, mod_depth_ms, fade_ms; } aidax_delay_params;
+typedef struct {
+    uint32_t m;                /* the delay in frames                                  */
+    uint32_t depth_q16;        /* the modulation depth in frames * 2^16                */
+    uint32_t lfo_step;         /* the phase increment per frame                        */
+    uint32_t fade;             /* the crossfade length in frames                       */
+    float    fb, damp, wet, dry;
+    uint32_t on;
+    uint32_t reserved[3];
+} aidax_delay_rec;             /* 48 bytes, no padding */
+typedef struct {
+    uint64_t pos;              /* frames the line has taken                            */
+    uint32_t m_cur, m_old;     /* the delay in force, the one a fade comes from        */
+    uint32_t fade_len, fade_left;
+    uint32_t phase;
+    uint32_t replaced;         /* NaN and +-Inf samples replaced by 0 (modulo 2^32)    */
+} aidax_delay_state;           /* 32 bytes, no padding */
+AIDAX_API int      aidax_delay_design(const aidax_delay_params* params, double samplerate, aidax_delay_rec* out);
+AIDAX_API int      aidax_pool_set_delays(aidax_pool* p, int on, uint32_t max_delay_frames);
+AIDAX_API int      aidax_pool_delays(const aidax_pool* p);
+AIDAX_API int      aidax_pool_set_delay(aidax_pool* p, int32_t stream, const aidax_delay_params* params);
+AIDAX_API int      aidax_pool_set_delay_rec(aidax_pool* p, int32_t stream, const aidax_delay_rec* rec);
+AIDAX_API int      aidax_pool_stream_delay(const aidax_pool* p, uint32_t stream, aidax_delay_params* params, aidax_delay_rec* rec, int* on);
+AIDAX_API int      aidax_pool_read_delays(aidax_pool* p, uint32_t first, uint32_t count, aidax_delay_state* out);
+AIDAX_API int      aidax_pool_reset_delay(aidax_pool* p, int32_t stream);
+
 /* Threads. A pool is driven by ONE audio-side caller at a time (set_controls, set_loading, activate,
- * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, set_bus_limiting after its first enabling call, set_bus_limiter, read_bus_meters, set_bus_reverbs after its first enabling call, set_bus_reverb, set_bus_reverb_rec, reset_bus_reverb, process*, sync; around a wrapped pool also aidax_rate_process,
+ * reset_stream, commit_model, commit_ir, assign_ir, assign_ir_b, set_ir_mix, assign_model, set_ir_fade, set_metering after its first enabling call, read_meters, set_gate after its first enabling call, read_gate, set_buses after its first enabling call, set_send, read_buses, set_bus_limiting after its first enabling call, set_bus_limiter, read_bus_meters, set_bus_reverbs after its first enabling call, set_bus_reverb, set_bus_reverb_rec, reset_bus_reverb, set_delays after its first enabling call, set_delay, set_delay_rec, reset_delay, read_delays, process*, sync; around a wrapped pool also aidax_rate_process,
  * aidax_rate_process_device, aidax_rate_reset_stream) plus, concurrently, ONE worker-side caller (prepare_model,
  * prepare_model_slot, prepare_ir, prepare_ir_slot, staged_free). set_ir_capacity is a set-up side call, made before the first prepare_ir / prepare_ir_slot and
- * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side) and the first aidax_pool_set_bus_limiting with on != 0 (it allocates; aidax_pool_bus_limiting and aidax_pool_bus_limiter read host records of the audio side) and the first aidax_pool_set_bus_reverbs with on != 0 (it allocates; aidax_pool_bus_reverbs and aidax_pool_bus_reverb read host records of the audio side); aidax_gate_design, aidax_mix_gain, aidax_bus_limit_design and aidax_bus_reverb_design are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
+ * before the two threads start, and so is the first aidax_pool_set_metering with on != 0 (it allocates; aidax_pool_metering reads a host record of the audio side) and the first aidax_pool_set_gate with parameters (it allocates too; aidax_pool_stream_gate reads a host record of the audio side) and the first aidax_pool_set_buses with a count (it allocates as well; aidax_pool_buses and aidax_pool_stream_send read host records of the audio side) and the first aidax_pool_set_bus_limiting with on != 0 (it allocates; aidax_pool_bus_limiting and aidax_pool_bus_limiter read host records of the audio side) and the first aidax_pool_set_bus_reverbs with on != 0 (it allocates; aidax_pool_bus_reverbs and aidax_pool_bus_reverb read host records of the audio side) and the first aidax_pool_set_delays with on != 0 (it allocates; aidax_pool_delays and aidax_pool_stream_delay read host records of the audio side); aidax_gate_design, aidax_mix_gain, aidax_bus_limit_design, aidax_bus_reverb_design and aidax_delay_design are pure: any thread; aidax_ir_resample and aidax_ir_load_wav are host only and touch no pool: any thread, the worker by
  * habit. aidax_rate_create and aidax_rate_destroy are set-up side calls (the adapter's blocks are the audio side's, above), a bare
  * aidax_resampler belongs to one caller at a time, and aidax_rate_latency and aidax_resampler_row touch nothing: any thread. None of the audio-side calls allocates or frees device or pinned memory, and only
- * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses / aidax_pool_read_bus_meters wait for the GPU (for the stream that carries the pass, never for the
- * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate), a changed mix plan (after a set_send) changed bus limiter records (after a set_bus_limiter) and changed bus reverb records (after a set_bus_reverb, a set_bus_reverb_rec or a reset_bus_reverb, and once in 2^30 frames when an epoch is moved forward), go
+ * aidax_pool_process / aidax_pool_process_buses / aidax_pool_sync / aidax_rate_process / aidax_pool_read_meters / aidax_pool_read_gate / aidax_pool_read_buses / aidax_pool_read_bus_meters / aidax_pool_read_delays wait for the GPU (for the stream that carries the pass, never for the
+ * device) — with one exception in every pass: changed control records, a changed IR plan (after an assign_ir, an assign_ir_b, a set_ir_mix or a commit_ir, and when a ramp ends on 0 or 1) changed model-bank records (after an assign_model) changed gate records (after a set_gate), a changed mix plan (after a set_send) changed bus limiter records (after a set_bus_limiter) and changed bus reverb records (after a set_bus_reverb, a set_bus_reverb_rec or a reset_bus_reverb, and once in 2^30 frames when an epoch is moved forward) and changed delay records (after a set_delay or a set_delay_rec), go
  * to the device from a ring of four pinned snapshots, and a pass waits for the upload issued four changes before its own if that has
  * not run yet. That happens only to a caller that issues passes far ahead of the GPU (process_device, submit) with a change before
  * each of five passes in a row. */
