@@ -10,34 +10,25 @@
 #include <vector>
 
 #include "../../include/aidax.h"
+#include "aidax_stage_book.h"
 
 namespace aidax {
 
-struct DelayBook {
-    using Run = std::pair<uint32_t, uint32_t>;           // streams [first, second)
+struct DelayBook : OnRuns {                              // n_on: streams whose delay is on; runs: sized once (init)
+    using Run = aidax::Run;
     uint32_t cap = 0;                                    // the capacity in frames, fixed by init
     std::vector<aidax_delay_rec> h_rec;                  // the records k_delay reads
     std::vector<aidax_delay_params> params;              // as last set by parameters; zeros for a stream set by a record of the caller's own
-    uint32_t dirty_lo = 1, dirty_hi = 0;                 // records [lo, hi] the device has not seen; empty when lo > hi
-    uint32_t n_on = 0;                                   // streams whose delay is on: a pass launches k_delay while this is not 0
-    std::vector<Run> runs;                               // sized once (init), so that a change allocates nothing
+    DirtyRange dirty;                                    // records the device has not seen
 
     void init(uint32_t n, uint32_t capacity)
     {
         cap = capacity;
         h_rec.assign(n, aidax_delay_rec{});
         params.assign(n, aidax_delay_params{});
-        runs.reserve((n + 1u) / 2u);
-        dirty_lo = 1; dirty_hi = 0; n_on = 0;
+        reserve(n);
+        dirty.clear(); n_on = 0;
     }
-    bool dirty() const { return dirty_lo <= dirty_hi; }
-    void mark(uint32_t lo, uint32_t hi)
-    {
-        const bool e = !dirty();
-        dirty_lo = e ? lo : std::min(dirty_lo, lo);
-        dirty_hi = e ? hi : std::max(dirty_hi, hi);
-    }
-    void flushed() { dirty_lo = 1; dirty_hi = 0; }
     // floats of a stream's ring row: the smallest power of two that holds the longest history a record within the capacity reads
     // (cap + 3 frames: the frame itself and the three taps behind the longest read position) next to a pass of max_frames
     static uint32_t ring_row(uint32_t capacity, uint32_t max_frames)
@@ -64,18 +55,12 @@ struct DelayBook {
     // so the caller zeroes those runs' states. *ok = false, and nothing changed: a record beyond the capacity.
     const std::vector<Run>& set(uint32_t lo, uint32_t hi, const aidax_delay_rec* rec, const aidax_delay_params* set_params, bool* ok)
     {
-        runs.clear();
+        begin_change();
         *ok = !rec || fits(*rec);
         if (!*ok) return runs;
         for (uint32_t s = lo; s < hi; ++s) {
             aidax_delay_rec& h = h_rec[s];
-            if (rec && !h.on) {
-                ++n_on;
-                if (!runs.empty() && runs.back().second == s) runs.back().second = s + 1;
-                else runs.emplace_back(s, s + 1);
-            } else if (!rec && h.on) {
-                --n_on;
-            }
+            note(s, h.on != 0u, rec != nullptr);
             if (rec) {
                 h = *rec;
                 h.on = 1u;
@@ -85,7 +70,7 @@ struct DelayBook {
                 h.on = 0u;
             }
         }
-        mark(lo, hi - 1);
+        dirty.mark(lo, hi - 1);
         return runs;
     }
 };

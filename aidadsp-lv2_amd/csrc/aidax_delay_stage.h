@@ -44,8 +44,8 @@ struct DelayStage {
         fresh.d_rec.alloc(n);
         fresh.d_state.alloc(n);
         fresh.h_state.alloc(n);
-        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(DelayRec) * n, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_state.get(), 0, sizeof(DelayState) * n, q));
+        fresh.d_rec.zero(0, n, q);
+        fresh.d_state.zero(0, n, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
         fresh.ring.alloc(sizeof(DelayRec) * n);
         fresh.book.init(n_streams, capacity);
@@ -53,18 +53,13 @@ struct DelayStage {
         *this = std::move(fresh);
     }
     // a restart's device half, on the pool's own stream behind the passes issued so far
-    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) HIP_TRY(hipMemsetAsync(d_state.get() + first, 0, sizeof(DelayState) * count, q)); }
+    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) d_state.zero(first, count, q); }
     // Behind the IR stage of a pass of n_frames > 0 that returns `d_out`: the records, if one has changed since the last upload, then
     // k_delay in place
     void after_pass(float* d_out, const StreamCtl* d_ctl, uint32_t n_active, uint32_t n_frames, hipStream_t s)
     {
         if (n_frames == 0 || !plays()) return;
-        if (book.dirty()) {
-            const size_t off = sizeof(DelayRec) * book.dirty_lo, bytes = sizeof(DelayRec) * (static_cast<size_t>(book.dirty_hi - book.dirty_lo) + 1);
-            std::memcpy(ring.take() + off, book.h_rec.data() + book.dirty_lo, bytes);
-            ring.send(d_rec.get(), off, bytes, s);
-            book.flushed();
-        }
+        ring.upload_dirty(d_rec.get(), book.h_rec.data(), book.dirty, s);
         DelayArgs a{};
         a.block = d_out; a.ring = d_ring.get(); a.rec = d_rec.get(); a.state = d_state.get(); a.ctl = d_ctl;
         a.n_active = n_active; a.n_frames = n_frames; a.mask = ring_row - 1u; a.cap = book.cap;

@@ -124,6 +124,8 @@ class DevBuf {
         reset();
         p_ = p;
     }
+    // elements [first, first + count) zeroed on q: what a stage's enable() does to each block a pass must find cleared, and a restart to its runs
+    void zero(size_t first, size_t count, hipStream_t q) const { HIP_TRY(hipMemsetAsync(p_ + first, 0, sizeof(T) * count, q)); }
     T* get() const { return p_; }
     T* release() { T* p = p_; p_ = nullptr; return p; }      // (into such a record)
     explicit operator bool() const { return p_ != nullptr; }

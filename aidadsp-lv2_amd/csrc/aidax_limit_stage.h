@@ -88,8 +88,8 @@ struct LimitStage {
         fresh.h_meter.alloc(2u * n);
         BusMeterRec* cleared = fresh.h_meter.get() + n;
         for (size_t b = 0; b < n; ++b) { cleared[b] = BusMeterRec{}; cleared[b].min_gain = 1.f; }
-        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * n * fresh.ring_row, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(LimitRec) * n, q));
+        fresh.d_ring.zero(0, n * fresh.ring_row, q);
+        fresh.d_rec.zero(0, n, q);
         HIP_TRY(hipMemcpyAsync(fresh.d_meter.get(), cleared, sizeof(BusMeterRec) * n, hipMemcpyHostToDevice, q));
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them cleared)
         fresh.ring.alloc(sizeof(LimitRec) * n);

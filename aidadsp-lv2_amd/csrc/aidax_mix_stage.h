@@ -81,7 +81,7 @@ struct MixStage {
         fresh.d_bus.alloc(block);
         fresh.d_plan.alloc(fresh.book.plan_bytes());
         fresh.h_bus.alloc(block);
-        HIP_TRY(hipMemsetAsync(fresh.d_bus.get(), 0, sizeof(float) * block, q));
+        fresh.d_bus.zero(0, block, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find it zeroed)
         fresh.ring.alloc(fresh.book.plan_bytes());
         fresh.on = true;

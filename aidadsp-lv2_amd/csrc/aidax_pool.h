@@ -1,8 +1,9 @@
-// aidax_pool.h — the stream pool's own types, shared by its three sources: aidax_pool.cpp (the core: launch — the
-// executor of a PassForm —, create / destroy, controls and stream state), aidax_pool_model.cpp (everything that builds or commits an
-// aidax_staged) and aidax_pool_io.cpp (the host-buffer entry points). Which kernels serve a pass is decided in ONE place, the HIP-free
-// aidax_pass_form.h: a slot carries the SlotForm that choose_form gave it, aidax_pool::pass_form gathers the facts (and reads the per-call
-// hooks), and launch, aidax_pool_kernel_name and aidax_pool_process all read the PassForm it returns. Private to the three sources.
+// aidax_pool.h — the stream pool's own types, shared by its four sources: aidax_pool.cpp (the core: launch — the
+// executor of a PassForm —, the pass and the order of its stages, create / destroy, controls and stream state), aidax_pool_stages.cpp (the
+// C ABI of the opt-in stages: meters, gate, tuners, buses, bus limiters, bus reverbs, stream delays), aidax_pool_model.cpp (everything that
+// builds or commits an aidax_staged) and aidax_pool_io.cpp (the host-buffer entry points). Which kernels serve a pass is decided in ONE
+// place, the HIP-free aidax_pass_form.h: a slot carries the SlotForm that choose_form gave it, aidax_pool::pass_form gathers the facts (and
+// reads the per-call hooks), and launch, aidax_pool_kernel_name and aidax_pool_process all read the PassForm it returns. Private to the four sources.
 // Issues HIP calls: include it last, like aidax_model_bank.h.
 #pragma once
 
@@ -25,6 +26,16 @@ namespace aidax {
 constexpr uint32_t kWarmupFrames = 2048;        // rt-neural-generic.cpp:1077
 constexpr uint32_t kMaxFrames = 8192;           // LDS block buffer bound (32 KiB)
 bool model_supported(const aidax_model& m);      // which models have a device path (aidax_pool.cpp)
+
+// the streams or buses [lo, hi) of n that a call names by one index or by AIDAX_ALL_STREAMS / AIDAX_ALL_BUSES; false: out of range
+static_assert(static_cast<int>(AIDAX_ALL_STREAMS) == static_cast<int>(AIDAX_ALL_BUSES), "one 'all' value for both");
+inline bool named_range(int32_t index, uint32_t n, uint32_t* lo, uint32_t* hi)
+{
+    if (index != AIDAX_ALL_STREAMS && (index < 0 || static_cast<uint32_t>(index) >= n)) return false;
+    *lo = index == AIDAX_ALL_STREAMS ? 0u : static_cast<uint32_t>(index);
+    *hi = index == AIDAX_ALL_STREAMS ? n : *lo + 1u;
+    return true;
+}
 
 // a flag written on the launch path and read by other threads (aidax_pool_kernel_name, lp_in_use from the worker): an atomic that
 // a struct assignment of its owner (a model swap is one) may copy
@@ -144,7 +155,7 @@ struct Pipeline {
 };
 
 }  // namespace aidax
-using namespace aidax;               // (a private header of three sources that say the same)
+using namespace aidax;               // (a private header of four sources that say the same)
 
 // A model on its way into (or out of) a pool. Built by aidax_pool_prepare_model on the worker thread; after
 // aidax_pool_commit_model the same object carries what the swap retired, for aidax_staged_free on the worker.

@@ -133,8 +133,8 @@ struct ReverbStage {
         const size_t ring_floats = n * kReverbLines * fresh.ring_row;
         fresh.d_ring.alloc(ring_floats);
         fresh.d_rec.alloc(n);
-        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * ring_floats, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(ReverbRec) * n, q));
+        fresh.d_ring.zero(0, ring_floats, q);
+        fresh.d_rec.zero(0, n, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them cleared)
         fresh.ring.alloc(sizeof(ReverbRec) * n);
         fresh.book.init(n_buses, delay_cap);

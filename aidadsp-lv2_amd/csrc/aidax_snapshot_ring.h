@@ -1,24 +1,19 @@
 // aidax_snapshot_ring.h — how host records reach the device: from a ring of pinned snapshots that nothing overwrites while an upload is
 // in flight, stream-ordered with the pass that follows (the pool's control records, the model bank's per-stream records, the IR plan).
-// It issues HIP calls and includes aidax_hip_host.h itself: include it where that header would go, last.
+// What is to go up is a DirtyRange (aidax_stage_book.h, no HIP). It issues HIP calls and includes aidax_hip_host.h itself: include it where
+// that header would go, last.
 #pragma once
 
 #include <algorithm>
 #include <cstring>
 #include <utility>
 
+#include "aidax_stage_book.h"
 #include "aidax_hip_host.h"
 
 namespace aidax {
 
 constexpr int kRing = 4;                                 // snapshots in flight
-
-struct DirtyRange {                                      // records [lo, hi] to upload; empty when lo > hi
-    uint32_t lo = 1, hi = 0;
-    bool empty() const { return lo > hi; }
-    void clear() { lo = 1; hi = 0; }
-    void mark(uint32_t l, uint32_t h) { const bool e = empty(); lo = e ? l : std::min(lo, l); hi = e ? h : std::max(hi, h); }
-};
 
 struct SnapshotRing {
     PinnedBuf<uint8_t> snap[kRing];
@@ -49,9 +44,11 @@ struct SnapshotRing {
         used[next] = true;
         next = (next + 1) % kRing;
     }
-    template <class Rec>
-    void upload_dirty(Rec* d, const Rec* h, DirtyRange& dirty, hipStream_t s)      // records [lo, hi] of h to the same records of d
+    // records [lo, hi] of h to the same records of d (HostRec: the host's name for the device's record, where a HIP-free book keeps it)
+    template <class Rec, class HostRec>
+    void upload_dirty(Rec* d, const HostRec* h, DirtyRange& dirty, hipStream_t s)
     {
+        static_assert(sizeof(HostRec) == sizeof(Rec), "the host's record is the device's");
         if (dirty.empty()) return;
         const size_t off = sizeof(Rec) * dirty.lo, bytes = sizeof(Rec) * (static_cast<size_t>(dirty.hi - dirty.lo) + 1);
         std::memcpy(take() + off, h + dirty.lo, bytes);

@@ -20,30 +20,22 @@ static_assert(sizeof(aidax_gate_rec) == sizeof(GateRec) && offsetof(aidax_gate_r
                   sizeof(aidax_gate_state) == sizeof(GateState) && offsetof(aidax_gate_state, atten) == offsetof(GateState, atten),
               "k_gate's record and state are aidax_gate_rec and aidax_gate_state");
 
-// The gates' host records, all of them the audio side's. `runs` is sized once (init), so that a change allocates nothing.
-struct GateBook {
-    using Run = std::pair<uint32_t, uint32_t>;           // streams [first, second)
+// The gates' host records, all of them the audio side's. n_on: streams whose gate is on; runs: sized once (init).
+struct GateBook : OnRuns {
+    using Run = aidax::Run;
     std::vector<GateRec> h_rec;
     std::vector<aidax_gate_params> params;               // as last set, kept for the streams whose gate is on
     DirtyRange dirty;                                    // records the device has not seen
-    uint32_t n_on = 0;                                   // streams whose gate is on: a pass launches k_gate while this is not 0
-    std::vector<Run> runs;
 
-    void init(uint32_t n) { h_rec.assign(n, GateRec{}); params.assign(n, aidax_gate_params{}); runs.reserve((n + 1u) / 2u); }
+    void init(uint32_t n) { h_rec.assign(n, GateRec{}); params.assign(n, aidax_gate_params{}); reserve(n); }
     // Streams [lo, hi) get the designed record and its parameters, or (designed == nullptr) their gates go off. Returns the maximal runs
     // of streams that went from off to on: they restart at unity gain, so the caller zeroes those runs' states.
     const std::vector<Run>& apply(uint32_t lo, uint32_t hi, const aidax_gate_rec* designed, const aidax_gate_params* set_params)
     {
-        runs.clear();
+        begin_change();
         for (uint32_t s = lo; s < hi; ++s) {
             GateRec& r = h_rec[s];
-            if (designed && !r.on) {
-                ++n_on;
-                if (!runs.empty() && runs.back().second == s) runs.back().second = s + 1;
-                else runs.emplace_back(s, s + 1);
-            } else if (!designed && r.on) {
-                --n_on;
-            }
+            note(s, r.on != 0u, designed != nullptr);
             if (designed) { std::memcpy(&r, designed, sizeof r); params[s] = *set_params; }
             else r.on = 0u;
         }
@@ -72,8 +64,8 @@ struct GateStage {
         fresh.d_state.alloc(n);
         fresh.d_side.alloc(n * max_frames);
         fresh.h_state.alloc(n);
-        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(GateRec) * n, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_state.get(), 0, sizeof(GateState) * n, q));
+        fresh.d_rec.zero(0, n, q);
+        fresh.d_state.zero(0, n, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
         fresh.ring.alloc(sizeof(GateRec) * n);
         fresh.book.init(n_streams);
@@ -81,7 +73,7 @@ struct GateStage {
     }
     // audio side: host records; the runs that restart are zeroed by clear_states() on the pool's own stream, behind the passes issued so far
     const std::vector<GateBook::Run>& set(uint32_t lo, uint32_t hi, const aidax_gate_rec* designed, const aidax_gate_params* params) { return book.apply(lo, hi, designed, params); }
-    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) HIP_TRY(hipMemsetAsync(d_state.get() + first, 0, sizeof(GateState) * count, q)); }
+    void clear_states(uint32_t first, uint32_t count, hipStream_t q) { if (d_state) d_state.zero(first, count, q); }
     // Ahead of the model's launch of a pass: the records it plays under, then the gated block into the side block. Returns what that
     // launch reads: the side block, or d_in while no gate is on (the pass's end markers stay with the model's launch: the gate is ahead of it)
     const float* before_pass(const float* d_in, const StreamCtl* d_ctl, uint32_t n_active, uint32_t n_frames, hipStream_t s)
@@ -110,7 +102,7 @@ struct MeterStage {
         MeterStage fresh;
         fresh.h_rec.alloc(n_streams);
         fresh.d_rec.alloc(n_streams);
-        HIP_TRY(hipMemsetAsync(fresh.d_rec.get(), 0, sizeof(MeterRec) * n_streams, q));
+        fresh.d_rec.zero(0, n_streams, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
         fresh.on = true;
         *this = std::move(fresh);
@@ -120,7 +112,7 @@ struct MeterStage {
     void read(uint32_t first, uint32_t count, aidax_stream_meter* out, bool clear, hipStream_t q)      // waits
     {
         const size_t bytes = sizeof(MeterRec) * count;
-        read_back(out, h_rec.get() + first, d_rec.get() + first, bytes, q, [&] { if (clear) HIP_TRY(hipMemsetAsync(d_rec.get() + first, 0, bytes, q)); });
+        read_back(out, h_rec.get() + first, d_rec.get() + first, bytes, q, [&] { if (clear) d_rec.zero(first, count, q); });
     }
 };
 
@@ -157,11 +149,11 @@ struct TunerStage {
         fresh.d_curve.alloc(n * fresh.curve_row);
         fresh.h_reading.alloc(n);
         fresh.h_curve.alloc(fresh.curve_row);
-        HIP_TRY(hipMemsetAsync(fresh.d_ring.get(), 0, sizeof(float) * n * fresh.ring_row, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_pos.get(), 0, sizeof(uint64_t) * n, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_on.get(), 0, sizeof(uint32_t) * n, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_reading.get(), 0, sizeof(TunerReading) * n, q));
-        HIP_TRY(hipMemsetAsync(fresh.d_curve.get(), 0, sizeof(float) * n * fresh.curve_row, q));
+        fresh.d_ring.zero(0, n * fresh.ring_row, q);
+        fresh.d_pos.zero(0, n, q);
+        fresh.d_on.zero(0, n, q);
+        fresh.d_reading.zero(0, n, q);
+        fresh.d_curve.zero(0, n * fresh.curve_row, q);
         HIP_TRY(hipStreamSynchronize(q));                // (a pass on a caller's stream must find them zeroed)
         fresh.ring.alloc(sizeof(uint32_t) * n);
         fresh.book.init(n_streams, designed);
@@ -173,20 +165,15 @@ struct TunerStage {
     void clear_streams(uint32_t first, uint32_t count, hipStream_t q)
     {
         if (!d_ring) return;
-        HIP_TRY(hipMemsetAsync(d_pos.get() + first, 0, sizeof(uint64_t) * count, q));
-        HIP_TRY(hipMemsetAsync(d_reading.get() + first, 0, sizeof(TunerReading) * count, q));
-        HIP_TRY(hipMemsetAsync(d_curve.get() + static_cast<size_t>(first) * curve_row, 0, sizeof(float) * count * curve_row, q));
+        d_pos.zero(first, count, q);
+        d_reading.zero(first, count, q);
+        d_curve.zero(static_cast<size_t>(first) * curve_row, static_cast<size_t>(count) * curve_row, q);
     }
     // Ahead of the model's launch of a pass: the `on` words it plays under, then k_tune over the block it was handed
     void before_pass(const float* d_in, uint32_t n_active, uint32_t n_frames, hipStream_t s)
     {
         if (!on || n_frames == 0 || book.n_on == 0) return;
-        if (book.dirty()) {
-            const size_t off = sizeof(uint32_t) * book.dirty_lo, bytes = sizeof(uint32_t) * (static_cast<size_t>(book.dirty_hi - book.dirty_lo) + 1);
-            std::memcpy(ring.take() + off, book.h_on.data() + book.dirty_lo, bytes);
-            ring.send(d_on.get(), off, bytes, s);
-            book.flushed();
-        }
+        ring.upload_dirty(d_on.get(), book.h_on.data(), book.dirty, s);
         const bool analyse = book.advance(n_active, n_frames);
         const aidax_tuner_rec& r = book.rec;
         TuneArgs a{};

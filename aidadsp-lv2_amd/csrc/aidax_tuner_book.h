@@ -10,34 +10,25 @@
 #include <vector>
 
 #include "../../include/aidax.h"
+#include "aidax_stage_book.h"
 
 namespace aidax {
 
-struct TunerBook {
-    using Run = std::pair<uint32_t, uint32_t>;           // streams [first, second)
+struct TunerBook : OnRuns {                              // n_on: streams whose tuner is on; runs: sized once (init)
+    using Run = aidax::Run;
     aidax_tuner_rec rec{};                               // the design, fixed by init
     std::vector<uint32_t> h_on;                          // the words k_tune reads
     std::vector<uint64_t> pos;                           // frames handed to the stream since its tuner went on or was restarted
-    uint32_t dirty_lo = 1, dirty_hi = 0;                 // `on` words [lo, hi] the device has not seen; empty when lo > hi
-    uint32_t n_on = 0;                                   // streams whose tuner is on: a pass launches k_tune while this is not 0
-    std::vector<Run> runs;                               // sized once (init), so that a change allocates nothing
+    DirtyRange dirty;                                    // `on` words the device has not seen
 
     void init(uint32_t n, const aidax_tuner_rec& designed)
     {
         rec = designed;
         h_on.assign(n, 0u);
         pos.assign(n, 0u);
-        runs.reserve((n + 1u) / 2u);
-        dirty_lo = 1; dirty_hi = 0; n_on = 0;
+        reserve(n);
+        dirty.clear(); n_on = 0;
     }
-    bool dirty() const { return dirty_lo <= dirty_hi; }
-    void mark(uint32_t lo, uint32_t hi)
-    {
-        const bool e = !dirty();
-        dirty_lo = e ? lo : std::min(dirty_lo, lo);
-        dirty_hi = e ? hi : std::max(dirty_hi, hi);
-    }
-    void flushed() { dirty_lo = 1; dirty_hi = 0; }
     // Rule 1: does a pass that takes a count from p0 to p1 analyse, and at which boundary
     static bool crosses(uint64_t p0, uint64_t p1, uint32_t window, uint32_t hop, uint64_t* boundary)
     {
@@ -49,21 +40,15 @@ struct TunerBook {
     // zeroed here, the caller zeroes those runs' device records).
     const std::vector<Run>& apply(uint32_t lo, uint32_t hi, bool on)
     {
-        runs.clear();
+        begin_change();
         bool changed = false;
         for (uint32_t s = lo; s < hi; ++s) {
-            if (on && !h_on[s]) {
-                ++n_on;
-                pos[s] = 0;
-                if (!runs.empty() && runs.back().second == s) runs.back().second = s + 1;
-                else runs.emplace_back(s, s + 1);
-            } else if (!on && h_on[s]) {
-                --n_on;
-            }
-            changed = changed || (h_on[s] != 0u) != on;
+            const bool was_on = h_on[s] != 0u;
+            if (note(s, was_on, on)) pos[s] = 0;
+            changed = changed || was_on != on;
             h_on[s] = on ? 1u : 0u;
         }
-        if (changed) mark(lo, hi - 1);
+        if (changed) dirty.mark(lo, hi - 1);             // (only when a word changed: a call that changes none uploads nothing)
         return runs;
     }
     void restart(uint32_t s) { pos[s] = 0; }             // aidax_pool_reset_stream (the caller zeroes the stream's device records)

@@ -10,6 +10,7 @@
 
 #include "aidax.h"
 #include "../aidadsp-lv2_amd/csrc/aidax_delay_book.h"
+#include "asan_on_runs_case.h"
 
 static int failures = 0, steps = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "asan_delay_harness: %s failed at line %d\n", #c, __LINE__); ++failures; } } while (0)
@@ -51,14 +52,14 @@ static void run(uint32_t n, uint32_t cap, uint32_t seed, int n_steps)
     std::vector<uint8_t> on(n, 0);
     std::vector<aidax_delay_params> params(n);
     std::vector<aidax_delay_rec> rec(n, aidax_delay_rec{}), device(n, aidax_delay_rec{});
-    EXPECT(b.n_on == 0 && !b.dirty() && b.h_rec.size() == n && b.params.size() == n && b.cap == cap);
+    EXPECT(b.n_on == 0 && b.dirty.empty() && b.h_rec.size() == n && b.params.size() == n && b.cap == cap);
     EXPECT(DelayBook::ring_row(cap, 257) >= cap + 3u + 257u && DelayBook::ring_row(cap, 257) / 2u < cap + 3u + 257u);
     for (int step = 0; step < n_steps; ++step, ++steps) {
         const uint32_t op = rnd(8);
         if (op == 7) {                                                          // a flush, as DelayStage::after_pass does it while a delay is on
-            if (b.n_on != 0 && b.dirty()) {
-                std::copy(b.h_rec.begin() + b.dirty_lo, b.h_rec.begin() + b.dirty_hi + 1, device.begin() + b.dirty_lo);
-                b.flushed();
+            if (b.n_on != 0 && !b.dirty.empty()) {
+                std::copy(b.h_rec.begin() + b.dirty.lo, b.h_rec.begin() + b.dirty.hi + 1, device.begin() + b.dirty.lo);
+                b.dirty.clear();
             }
         } else {
             const bool all = rnd(4) == 0, set = rnd(3) != 0, by_params = rnd(2) != 0;
@@ -70,7 +71,7 @@ static void run(uint32_t n, uint32_t cap, uint32_t seed, int n_steps)
             const uint64_t reach = static_cast<uint64_t>(r.m) + (r.depth_q16 >> 16) + ((r.depth_q16 & 0xffffu) ? 1u : 0u);
             const bool fits = !set || reach <= cap;
             const std::vector<aidax_delay_rec> before = b.h_rec;
-            const uint32_t dirty_lo = b.dirty_lo, dirty_hi = b.dirty_hi, n_on = b.n_on;
+            const uint32_t dirty_lo = b.dirty.lo, dirty_hi = b.dirty.hi, n_on = b.n_on;
             std::vector<std::pair<uint32_t, uint32_t>> want;
             if (fits)
                 for (uint32_t s = lo; s < hi; ++s) {
@@ -92,9 +93,9 @@ static void run(uint32_t n, uint32_t cap, uint32_t seed, int n_steps)
             const std::vector<DelayBook::Run>& got = b.set(lo, hi, set ? &r : nullptr, set && by_params ? &p : nullptr, &ok);
             EXPECT(ok == fits && got == want);
             if (fits) {
-                EXPECT(b.dirty() && b.dirty_lo <= lo && hi - 1 <= b.dirty_hi && b.dirty_hi < n);      // dirty covers [lo, hi)
+                EXPECT(!b.dirty.empty() && b.dirty.lo <= lo && hi - 1 <= b.dirty.hi && b.dirty.hi < n);      // dirty covers [lo, hi)
             } else {                                                            // a refused record changes nothing
-                EXPECT(b.dirty_lo == dirty_lo && b.dirty_hi == dirty_hi && b.n_on == n_on);
+                EXPECT(b.dirty.lo == dirty_lo && b.dirty.hi == dirty_hi && b.n_on == n_on);
                 for (uint32_t s = 0; s < n; ++s) EXPECT(same(b.h_rec[s], before[s]));
             }
         }
@@ -105,7 +106,7 @@ static void run(uint32_t n, uint32_t cap, uint32_t seed, int n_steps)
             EXPECT(same(b.h_rec[s], rec[s]));
             if (on[s]) EXPECT(same(b.params[s], params[s]) && b.fits(b.h_rec[s]));
             // what differs from the device's copy lies inside the dirty range
-            if (!same(b.h_rec[s], device[s])) EXPECT(b.dirty() && b.dirty_lo <= s && s <= b.dirty_hi);
+            if (!same(b.h_rec[s], device[s])) EXPECT(!b.dirty.empty() && b.dirty.lo <= s && s <= b.dirty.hi);
         }
         EXPECT(b.n_on == count);                                                // n_on equals the count of `on` records
     }
@@ -137,9 +138,28 @@ static void the_records_own_conditions()
     ++steps;
 }
 
+// the off-to-on rule's fixed case (asan_on_runs_case.h), with a record that fits
+static void the_runs_that_restart()
+{
+    aidax_delay_params p{};
+    lcg_state = 5u;
+    aidax_delay_rec r = some_rec(300, &p);
+    r.m = 100; r.depth_q16 = 0;
+    DelayBook seven;
+    seven.init(7, 300);
+    failures += on_runs_case("asan_delay_harness", seven, [&](uint32_t lo, uint32_t hi, bool on) -> const std::vector<DelayBook::Run>& {
+        bool ok = false;
+        const std::vector<DelayBook::Run>& runs = seven.set(lo, hi, on ? &r : nullptr, on ? &p : nullptr, &ok);
+        EXPECT(ok);
+        return runs;
+    });
+    ++steps;
+}
+
 int main()
 {
     the_records_own_conditions();
+    the_runs_that_restart();
     for (uint32_t n : { 1u, 2u, 7u, 70u })
         for (uint32_t seed : { 1u, 77u, 2024u }) run(n, n == 7u ? 64u : 300u, seed * 2654435761u + n, 400);
     std::printf("asan_delay_harness: %d steps, %d failures\n", steps, failures);

@@ -9,6 +9,7 @@
 
 #include "aidax.h"
 #include "../aidadsp-lv2_amd/csrc/aidax_stream_stages.h"
+#include "asan_on_runs_case.h"
 
 namespace aidax {
 // (aidax_model.cpp, linked for fail() and aidax_last_error(), asks the pool which models have a kernel: no model is loaded here)
@@ -90,8 +91,24 @@ static void run(uint32_t n, uint32_t seed, int n_steps)
     }
 }
 
+// the off-to-on rule's fixed case (asan_on_runs_case.h)
+static void the_runs_that_restart()
+{
+    lcg_state = 5u;
+    aidax_gate_params p = some_params();
+    aidax_gate_rec designed{};
+    EXPECT(aidax_gate_design(&p, 48000.0, &designed) == AIDAX_OK && designed.on == 1u);
+    GateBook seven;
+    seven.init(7);
+    failures += on_runs_case("asan_gate_harness", seven, [&](uint32_t lo, uint32_t hi, bool on) -> const std::vector<GateBook::Run>& {
+        return seven.apply(lo, hi, on ? &designed : nullptr, on ? &p : nullptr);
+    });
+    ++steps;
+}
+
 int main()
 {
+    the_runs_that_restart();
     for (uint32_t n : { 1u, 2u, 7u, 70u })
         for (uint32_t seed : { 1u, 77u, 2024u }) run(n, seed * 2654435761u + n, 400);
     std::printf("asan_gate_harness: %d steps, %d failures\n", steps, failures);

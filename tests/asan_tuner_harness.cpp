@@ -9,6 +9,7 @@
 
 #include "aidax.h"
 #include "../aidadsp-lv2_amd/csrc/aidax_tuner_book.h"
+#include "asan_on_runs_case.h"
 
 static int failures = 0, steps = 0;
 #define EXPECT(c) do { if (!(c)) { std::fprintf(stderr, "asan_tuner_harness: %s failed at line %d\n", #c, __LINE__); ++failures; } } while (0)
@@ -38,13 +39,14 @@ static void run(uint32_t n, uint32_t seed, int n_steps, uint32_t window, uint32_
     std::vector<uint8_t> on(n, 0);
     std::vector<uint64_t> pos(n, 0);
     std::vector<uint32_t> device(n, 0u);
-    EXPECT(b.n_on == 0 && !b.dirty() && b.h_on.size() == n && b.pos.size() == n && b.runs.capacity() >= (n + 1u) / 2u);
+    EXPECT(b.n_on == 0 && b.dirty.empty() && b.h_on.size() == n && b.pos.size() == n && b.runs.capacity() >= (n + 1u) / 2u);
     const size_t runs_capacity = b.runs.capacity();
     for (int step = 0; step < n_steps; ++step, ++steps) {
         const uint32_t op = rnd(10);
         if (op < 3) {                                                           // aidax_pool_set_tuner: one stream or all, on or off
             const bool all = rnd(4) == 0, set = rnd(3) != 0;
             const uint32_t lo = all ? 0u : rnd(n), hi = all ? n : lo + 1u;
+            const aidax::DirtyRange dirty_before = b.dirty;
             const std::vector<TunerBook::Run>& runs = b.apply(lo, hi, set);
             // the runs: maximal, ascending, exactly the streams that were off and are on now
             std::vector<uint8_t> restarted(n, 0);
@@ -65,17 +67,18 @@ static void run(uint32_t n, uint32_t seed, int n_steps, uint32_t window, uint32_
             }
             for (uint32_t s = 0; s < n; ++s)
                 if (s < lo || s >= hi) EXPECT(!restarted[s]);
-            if (changed) EXPECT(b.dirty() && b.dirty_lo <= lo && b.dirty_hi >= hi - 1u);
+            if (changed) EXPECT(!b.dirty.empty() && b.dirty.lo <= lo && b.dirty.hi >= hi - 1u);
+            else EXPECT(b.dirty.lo == dirty_before.lo && b.dirty.hi == dirty_before.hi);      // (no word changed: nothing more to upload)
             EXPECT(b.runs.capacity() == runs_capacity);                         // (a change allocates nothing)
         } else if (op == 3) {                                                   // aidax_pool_reset_stream
             const uint32_t s = rnd(n);
             b.restart(s);
             pos[s] = 0;
         } else if (op == 4) {                                                   // a flush, as TunerStage::before_pass does it
-            if (b.dirty()) {
-                EXPECT(b.dirty_hi < n);
-                for (uint32_t s = b.dirty_lo; s <= b.dirty_hi && s < n; ++s) device[s] = b.h_on[s];
-                b.flushed();
+            if (!b.dirty.empty()) {
+                EXPECT(b.dirty.hi < n);
+                for (uint32_t s = b.dirty.lo; s <= b.dirty.hi && s < n; ++s) device[s] = b.h_on[s];
+                b.dirty.clear();
             }
             for (uint32_t s = 0; s < n; ++s) EXPECT(device[s] == (on[s] ? 1u : 0u));
         } else {                                                                // a pass over a prefix, or over the whole pool
@@ -110,6 +113,14 @@ int main()
         run(n, seed++, 600, 1024u, 64u, 300u);                                  // a hop shorter than most blocks: several boundaries in a pass
         run(n, seed++, 600, 2048u, 1024u, 256u);
         run(n, seed++, 400, 4096u, 65536u, 4096u);
+    }
+    {                                                                           // the off-to-on rule's fixed case (asan_on_runs_case.h)
+        aidax_tuner_rec rec{};
+        rec.window = 1024u; rec.hop = 64u; rec.tmin = 2; rec.tmax = 511;
+        TunerBook seven;
+        seven.init(7, rec);
+        failures += on_runs_case("asan_tuner_harness", seven, [&](uint32_t lo, uint32_t hi, bool on) -> const std::vector<TunerBook::Run>& { return seven.apply(lo, hi, on); });
+        ++steps;
     }
     // counts beyond 2^32 frames: the rule is 64-bit arithmetic
     uint64_t b = 0;

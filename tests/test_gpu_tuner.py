@@ -288,6 +288,52 @@ def test_per_stream_switches(model, strings):
     twin.close()
 
 
+def test_one_interior_streams_word_changes_between_two_passes(model):
+    """the `on` words reach the device as the range that changed: of 5 streams 3 alone goes on, then 1 alone, then 3 goes off, each
+    between two passes of 64 frames (exact rows, window 1024, hop 64: every pass behind a stream's first 1024 frames analyses). After
+    every pass each stream's reading and count are the restatement's, bit for bit, and so is the curve at every analysis; a stream that
+    no call named reads zeros, and stream 3, once off, keeps the reading it had"""
+    W, S, n = 1024, 5, 64
+    tmax = W // 2 - 1
+    params, rec = _design(window=W, hop=64, f_min=SR / (tmax - 0.5), f_max=12000.0)
+    p = _pool(model, S, n, params, on=False)
+    x = _exact_rows(S, 2 * W + 4 * n, seed=1300)
+    trackers, kept, at = [None] * S, {}, 0
+
+    def passes(count):
+        nonlocal at
+        for _ in range(count):
+            blk = x[:, at:at + n]
+            _feed(p, blk, [n], trackers)
+            at += n
+            got = p.read_tuners()
+            for s, tr in enumerate(trackers):
+                if tr is None or tr.window is None:
+                    assert got[s].tobytes() == kept.get(s, bytes(got[s].nbytes)), (at, s, got[s])
+                    continue
+                assert (int(got["frame"][s]), int(got["analyses"][s])) == (tr.frame, tr.analyses), (at, s, got[s])
+                if tr.frame == tr.pos:                           # (this pass analysed)
+                    want, nsdf = th.analyse(tr.window, rec, exact=True)
+                    assert np.array_equal(_bits(p.read_tuner_curve(s)), _bits(nsdf)), (at, s)
+                    _same_reading(got[s], want, (at, s))
+                assert p.stream_tuner(s) == (True, tr.pos)
+
+    p.set_tuner(True, 3)
+    trackers[3] = th.Tracker(rec)
+    passes(W // n + 1)                                           # stream 3's first two analyses
+    p.set_tuner(True, 1)
+    trackers[1] = th.Tracker(rec)
+    passes(W // n + 1)                                           # ... and stream 1's, 3 going on
+    assert (trackers[1].analyses, trackers[3].analyses) == (2, W // n + 3)
+    kept[3] = p.read_tuners()[3].tobytes()
+    p.set_tuner(False, 3)
+    trackers[3] = None
+    passes(2)
+    assert trackers[1].analyses == 4 and p.stream_tuner(3) == (False, 2 * W + 2 * n) and p.read_tuners()["lag"][1] > 0
+    assert [p.stream_tuner(s)[0] for s in range(S)] == [False, True, False, False, False]
+    p.close()
+
+
 def _dressed_pool(model, S, tuned, params):
     """the gate (closing hard), the meters, an IR and the buses on beside the tuners"""
     p = _pool(model, S, 128, params, tuned=tuned)
